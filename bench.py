@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the suffix-array hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size BYTES]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size BYTES] [--dump-outputs DIR]
 
 A "step" is one full pass of the hot path -- SuffixTable::new, i.e. suffix-array
 construction -- over one batch of synthetic input that is ALREADY RESIDENT IN
@@ -19,6 +19,11 @@ single-GPU build of the same text; the line then says "scaling": "strong".
 Rank 0 prints the full records on lines that start with "DETAIL " (headline, then one per full-size config) and, last,
 ONE compact JSON line (< 4 KB; see DESIGN.md "Measurement" for every field) that carries, per config, {sa_ms, lcp_ms,
 fused_ms, bit_exact, engine_BpB, engine_frac, whole_path_frac, dominant kernel} inside `roofline.configs`.
+
+--dump-outputs DIR writes what the last timed step returned, as float64 .npy files (exact for u32 positions): a fixed,
+seeded sample of the suffix array (DIR/sa.npy) and the positions it was taken at (DIR/sa_index.npy); at N > 1 every rank
+writes its slice's sample as sa_rank<r>.npy / sa_rank<r>_index.npy and [offset, n] of the slice as sa_rank<r>_slice.npy.
+The inputs depend on the arguments alone, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -33,6 +38,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_SAMPLE = 1 << 21            # --dump-outputs: entries sampled over all ranks (2 float64 files of 16 MB at N = 1)
+DUMP_SEED = 0x5AF1C5
 METRIC = "MB of input text/sec for SuffixTable::new (SA-IS+LCP), 1 GPU; bit-exact SA"
 
 
@@ -117,6 +124,29 @@ def verify_sa_chunked(torch, sdev, text, sa, chunk=200_000_000, n_samples=2000, 
         prev = int(cur[-1])
         del lcp, cur, h, before, pa, pb, ca, cb
     return True, "permutation + adjacent-order (all pairs, in slices of %d) + sampled LCP bytes per slice" % chunk
+
+
+def sample_positions(n, k, seed=DUMP_SEED):
+    """Sorted, distinct positions in [0, n): all of them when n <= k, else a fixed sample of at most k drawn with `seed`."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=k, dtype=np.int64))
+
+
+def dump_outputs(torch, out_dir, arrays, rank, world):
+    """Writes `arrays` (name -> device u32/int32 tensor, or a host list of extra values) as float64 .npy files under out_dir:
+    tensors longer than DUMP_SAMPLE / world as that seeded sample plus <name>_index.npy, the positions it was taken at."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if world > 1:
+            name = name.replace("sa", f"sa_rank{rank}", 1)
+        if not torch.is_tensor(t):
+            np.save(os.path.join(out_dir, name + ".npy"), np.asarray(t, dtype=np.float64))
+            continue
+        idx = sample_positions(t.numel(), DUMP_SAMPLE // world)
+        vals = t.view(torch.int32)[torch.from_numpy(idx).to(t.device)].to(torch.int64) & 0xFFFFFFFF
+        np.save(os.path.join(out_dir, name + ".npy"), vals.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
 
 
 def _sha_u32(t):
@@ -405,7 +435,12 @@ def main():
                          "compiled in) instead of the product library; the line then carries config.dev_lib")
     ap.add_argument("--config-budget", type=float, default=150.0)
     ap.add_argument("--config-size", type=int, default=1_000_000_000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR as float64 .npy files (a seeded sample of the suffix "
+                         "array, at most 32 MB in all; see the module docstring); bench_outputs/ is ignored by git")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step (--steps >= 1)")
 
     # multi-process GPU work on this host driver needs dmabuf IPC (RCCL fails with
     # hipIpcGetMemHandle: invalid argument otherwise); exported already, kept if it is not
@@ -532,6 +567,13 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs:
+        # what the last timed step handed its caller, before any later (untimed) build reuses the buffers
+        if world == 1:
+            dump_outputs(torch, args.dump_outputs, {"sa": sa}, rank, world)
+        else:
+            part, offset, n_all = result["part"]
+            dump_outputs(torch, args.dump_outputs, {"sa": part, "sa_slice": [offset, n_all]}, rank, world)
     ms_per_step = elapsed * 1e3 / max(args.steps, 1)
     value = n_total * args.steps / elapsed / 1e6
     stats = eng.build_stats()

@@ -4,7 +4,7 @@ with AddressSanitizer against the fiber emulator (make -C tests/emu asan), drive
 same C ABI.  Not part of the pytest suite (several minutes); run by hand after kernel changes:
 
     make -C tests/emu asan
-    LD_PRELOAD=$(gcc -print-file-name=libasan.so) \\
+    LD_PRELOAD=$(clang++ -print-file-name=libclang_rt.asan-x86_64.so) \\
     ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0:halt_on_error=1 \\
     SFX_LCP_DIRECT_MIN=8 python tests/asan_check.py            # variants: add SFX_PARTITION_MIN=1 SFX_MAX_GRID=3 SFX_QUERY_PHASE_MIN=1 SFX_HYBRID_MIN=1 [SFX_HYBRID_CAP=100]
                                                                 # SFX_FORCE_KEY64=1 SFX_HT_MIN=1 [SFX_DEEP_ITERS=1 SFX_TILE_SMALL=1 SFX_SEG_SMALL=1]

@@ -168,8 +168,10 @@ static inline unsigned atomicAdd(unsigned* p, int v) { unsigned o = *p; *p = o +
 #define __HIP_MEMORY_SCOPE_AGENT 4
 #define __HIP_MEMORY_SCOPE_WORKGROUP 3
 #define __HIP_MEMORY_SCOPE_WAVEFRONT 2
+#ifndef __clang__   // (clang has both as builtins of its own, for every target)
 template <class T> static inline T __hip_atomic_load(const T* p, int, int) { return *p; }
 template <class T, class U> static inline void __hip_atomic_store(T* p, U v, int, int) { *p = (T)v; }
+#endif
 // v_mbcnt: bits of `mask` below this lane (+ add)
 static inline unsigned __builtin_amdgcn_mbcnt_lo(unsigned mask, unsigned add)
 {

@@ -16,10 +16,17 @@ Outputs
                            (tests/tests.rs:22-70, :100-168, :181-213), its doc-tests
                            (src/lib.rs:16-23, src/table.rs:191-196, :217-222, :272-278)
                            and examples (examples/basic.rs:7).
+
+    python make_golden.py --patch-pins     writes only this one:
+  upstream_patch_pins.json  sha256 of the upstream lines every hunk of rust/suffix-hip/*.patch
+                       expects at its old range, and of each patched file whole (with its
+                       line count), from the reference checkout; tests/test_rust_crate.py
+                       checks the patches against them without a checkout.
 """
 import hashlib
 import json
 import os
+import sys
 
 import numpy as np
 
@@ -82,5 +89,26 @@ def main():
     print(json.dumps(golden["fixtures"], indent=1))
 
 
+def patch_pins():
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_rust_crate import CRATE, PATCHES, PATCH_PINS, patch_hunks
+    upstream = os.path.dirname(REF)
+    pins = {"files": {}, "hunks": []}
+    for p in PATCHES:
+        for h in patch_hunks(os.path.join(CRATE, p)):
+            raw = open(os.path.join(upstream, h["file"]), "rb").read()
+            lines = raw.decode("utf-8").splitlines(keepends=True)
+            pins["files"][h["file"]] = {"lines": len(lines), "sha256": hashlib.sha256(raw).hexdigest()}
+            part = "".join(lines[h["old_start"] - 1:h["old_start"] - 1 + h["old_len"]])
+            pins["hunks"].append({"patch": p, "file": h["file"], "old_start": h["old_start"], "old_len": h["old_len"],
+                                  "sha256": hashlib.sha256(part.encode("utf-8")).hexdigest()})
+    with open(PATCH_PINS, "w") as f:
+        json.dump(pins, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--patch-pins"]:
+        patch_pins()
+    else:
+        main()

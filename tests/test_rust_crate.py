@@ -1,8 +1,10 @@
 """The cargo crate under rust/suffix-hip cannot be compiled here (no rustc / cargo in the image), so the CPU
 suite checks what can go wrong silently: (1) every function in its `extern "C"` block exists in
 include/suffix_hip.h with the same arity and argument / return types; (2) the crate has the files cargo needs;
-(3) the patches apply to the reference checkout (`patch --dry-run`; skipped where /root/reference is absent,
-i.e. on the GPU box)."""
+(3) the patches apply to upstream exactly, checked against pins of the upstream lines they touch
+(tests/golden/upstream_patch_pins.json), so no upstream checkout is needed."""
+import hashlib
+import json
 import os
 import re
 import shutil
@@ -12,6 +14,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CRATE = os.path.join(ROOT, "rust", "suffix-hip")
+PATCHES = ("table.rs.patch", "Cargo.toml.patch")
+PATCH_PINS = os.path.join(ROOT, "tests", "golden", "upstream_patch_pins.json")
 
 C2RUST = {
     "const uint8_t*": "*const u8", "uint8_t*": "*mut u8", "const uint32_t*": "*const u32", "uint32_t*": "*mut u32",
@@ -108,14 +112,83 @@ def test_crate_is_cargo_ready():
     assert "DeviceIndex::new" not in body
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src") or shutil.which("patch") is None,
-                    reason="reference checkout / patch(1) not available")
-def test_patches_apply_to_the_reference():
-    for p in ("table.rs.patch", "Cargo.toml.patch"):
-        out = subprocess.run(["patch", "--dry-run", "-p1", "-d", "/root/reference", "-i", os.path.join(CRATE, p)],
-                             capture_output=True, text=True)
-        assert out.returncode == 0, out.stdout + out.stderr
-        assert "FAILED" not in out.stdout and "fuzz" not in out.stdout, out.stdout
+def patch_hunks(path):
+    """The hunks of a unified diff: dicts of file, old_start, old_len and old (the lines the hunk expects upstream, newlines
+    kept).  Asserts that every hunk body holds exactly the line counts its @@ header states."""
+    hunks, fname, lines = [], None, open(path).read().splitlines(keepends=True)
+    i = 0
+    while i < len(lines):
+        line = lines[i]
+        if line.startswith("+++ "):
+            fname = line[4:].split("\t")[0].strip()
+            fname = fname[2:] if fname.startswith("b/") else fname
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+        if m:
+            old_start, old_len = int(m.group(1)), int(m.group(2) or 1)
+            new_len = int(m.group(4) or 1)
+            old, n_old, n_new = [], 0, 0
+            i += 1
+            while i < len(lines) and (n_old < old_len or n_new < new_len):
+                tag, body = lines[i][:1], lines[i][1:]
+                if tag in (" ", "\n"):
+                    old.append(body if tag == " " else "\n")
+                    n_old, n_new = n_old + 1, n_new + 1
+                elif tag == "-":
+                    old.append(body)
+                    n_old += 1
+                elif tag == "+":
+                    n_new += 1
+                else:
+                    break
+                i += 1
+            assert (n_old, n_new) == (old_len, new_len), (path, line, n_old, n_new)
+            hunks.append({"file": fname, "old_start": old_start, "old_len": old_len, "old": old})
+            continue
+        i += 1
+    return hunks
+
+
+def _sha(lines):
+    return hashlib.sha256("".join(lines).encode("utf-8")).hexdigest()
+
+
+def test_patches_apply_to_the_reference(tmp_path):
+    """Both patches apply to upstream exactly (no offset, no fuzz), checked without an upstream checkout: the pins hold, per
+    hunk, the sha256 of the upstream lines at the hunk's old range, and per file its line count and sha256, all taken from the
+    checkout the patches were made against (tests/golden/make_golden.py --patch-pins).  Every hunk's context and removed lines
+    must hash to its pin.  Where patch(1) is installed, it also applies both patches to a stand-in tree built from the hunks;
+    with SUFFIX_REFERENCE_DIR set, that upstream checkout must match the file pins as well."""
+    pins = json.load(open(PATCH_PINS))
+    pinned = {(h["patch"], h["file"], h["old_start"], h["old_len"]): h["sha256"] for h in pins["hunks"]}
+    seen = set()
+    standin = {}
+    for p in PATCHES:
+        hunks = patch_hunks(os.path.join(CRATE, p))
+        assert hunks, p
+        for h in hunks:
+            key = (p, h["file"], h["old_start"], h["old_len"])
+            assert key in pinned, f"{p}: hunk at {h['file']}:{h['old_start']} has no pin (regenerate the pins)"
+            assert _sha(h["old"]) == pinned[key], f"{p}: the lines of {h['file']}:{h['old_start']} differ from upstream"
+            assert h["file"] in pins["files"], h["file"]
+            assert h["old_start"] + h["old_len"] - 1 <= pins["files"][h["file"]]["lines"], key
+            seen.add(key)
+            body = standin.setdefault(h["file"], [f"// upstream line {k + 1}\n" for k in range(pins["files"][h["file"]]["lines"])])
+            body[h["old_start"] - 1:h["old_start"] - 1 + h["old_len"]] = h["old"]
+    assert seen == set(pinned), sorted(set(pinned) - seen)
+    if shutil.which("patch") is not None:
+        for fname, body in standin.items():
+            os.makedirs(os.path.dirname(str(tmp_path / fname)), exist_ok=True)
+            (tmp_path / fname).write_text("".join(body))
+        for p in PATCHES:
+            out = subprocess.run(["patch", "--dry-run", "-p1", "-d", str(tmp_path), "-i", os.path.join(CRATE, p)],
+                                 capture_output=True, text=True)
+            assert out.returncode == 0, out.stdout + out.stderr
+            assert "FAILED" not in out.stdout and "fuzz" not in out.stdout and "offset" not in out.stdout, out.stdout
+    upstream = os.environ.get("SUFFIX_REFERENCE_DIR")
+    if upstream:
+        for fname, f in pins["files"].items():
+            data = open(os.path.join(upstream, fname), "rb").read()
+            assert hashlib.sha256(data).hexdigest() == f["sha256"], f"{fname} of {upstream} is not the pinned upstream file"
 
 
 # ---- the upstream suite through the FFI, wherever a Rust toolchain exists (SURVEY.md 8(f)1, VERDICT round 5 item 5) ----------------
