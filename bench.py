@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the suffix-array hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size BYTES] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size BYTES] [--dump-outputs DIR] [--full]
 
 A "step" is one full pass of the hot path -- SuffixTable::new, i.e. suffix-array
 construction -- over one batch of synthetic input that is ALREADY RESIDENT IN
@@ -16,9 +16,15 @@ STRONG series instead: ONE text of T bytes (uniform DNA, seed 0x5AF1C5 + 4 --
 BASELINE config 4 at T = 4000000000) cut into N equal shards, at N = 1 the
 single-GPU build of the same text; the line then says "scaling": "strong".
 
-Rank 0 prints the full records on lines that start with "DETAIL " (headline, then one per full-size config) and, last,
-ONE compact JSON line (< 4 KB; see DESIGN.md "Measurement" for every field) that carries, per config, {sa_ms, lcp_ms,
-fused_ms, bit_exact, engine_BpB, engine_frac, whole_path_frac, dominant kernel} inside `roofline.configs`.
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+ONE JSON line (rank 0): metric, value, unit, higher_is_better, dtype, ms_per_step, the run's shape and its workload.
+Everything else the benchmark measures or checks runs only with --full, after the timed steps: the correctness gates, LCP
+and fused SA + LCP timings, end-to-end through host pointers, the per-kernel roofline, the memory-system probes, the CPU
+baseline, the full-size configs and, at N > 1, the per-phase times.  A --full run prints the full records on lines that
+start with "DETAIL " (headline, then one per full-size config) and, last, ONE compact JSON line (< 4 KB; see DESIGN.md
+"Measurement" for every field) that carries, per config, {sa_ms, lcp_ms, fused_ms, bit_exact, engine_BpB, engine_frac,
+whole_path_frac, dominant kernel} inside `roofline.configs`.  The options that tune those extras (--cpu-sample,
+--no-verify, --calibrate, --no-microbench, --configs, --config-budget, --config-size) are refused without --full.
 
 --dump-outputs DIR writes what the last timed step returned, as float64 .npy files (exact for u32 positions): a fixed,
 seeded sample of the suffix array (DIR/sa.npy) and the positions it was taken at (DIR/sa_index.npy); at N > 1 every rank
@@ -401,6 +407,26 @@ def fullsize_config(torch, eng, sdev, _gen, key, size, pins, dev):
     return rec
 
 
+def headline_record(args, world, strong, n_local, n_total, value, ms_per_step):
+    """The keys of every result line: the headline figure, what it was measured on and the run's shape.  A plain run prints
+    this alone; a --full run adds its records to it."""
+    workload = (f"{n_local} B synthetic DNA (sigma=4, uniform, splitmix64) per GPU, u32 indices, device-resident text -> device SA"
+                + ("" if world == 1 else f"; range-partitioned over {world} GPUs, text {n_total} B"))
+    if strong:
+        workload = (f"{n_total} B synthetic DNA (sigma=4, uniform, splitmix64 seed 0x5AF1C5 + 4"
+                    + (": BASELINE config 4's text" if n_total == 4_000_000_000 else "")
+                    + f"), ONE text cut into {world} shard(s) of {n_total // world} B, u32 indices, device-resident shards -> "
+                    + ("device SA" if world == 1 else f"one contiguous slice of the SA per GPU (range-partitioned, suffix_amd/dist.py)"))
+    return {
+        "metric": METRIC, "value": round(value, 2), "unit": "MB/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u32",
+        "data": "synthetic",
+        "config": {"workload": workload, "text_bytes_total": n_total,
+                   **({"dev_lib": os.path.basename(args.dev_lib)} if args.dev_lib else {})},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -413,15 +439,21 @@ def main():
     ap.add_argument("--ragged", action="store_true",
                     help="N > 1, tests only: rank r's shard is 4097 r + 1 bytes shorter (no multiple of the symbols per packed "
                          "word: the packed exchange assembles the words that straddle two shards)")
-    ap.add_argument("--cpu-sample", type=int, default=100_000_000,
-                    help="bytes of the same text the CPU baseline is timed on (0 = skip)")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--calibrate", action="store_true",
-                    help="also launch the known-byte-count copy / run-scatter micro-benchmarks once, so a "
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beyond the headline: correctness gates, LCP and fused "
+                         "SA + LCP timings, end-to-end, per-kernel roofline and probes, CPU baseline, full-size configs, "
+                         "per-phase times at N > 1 (see the module docstring)")
+    # --full only (default None: given without --full they are refused, not silently ignored)
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="--full: bytes of the same text the CPU baseline is timed on (default 100000000; 0 = skip)")
+    ap.add_argument("--no-verify", action="store_true", default=None, help="--full: skip the correctness gates")
+    ap.add_argument("--calibrate", action="store_true", default=None,
+                    help="--full: also launch the known-byte-count copy / run-scatter micro-benchmarks once, so a "
                          "rocprofv3 --pmc pass of this command can calibrate FETCH_SIZE / WRITE_SIZE")
-    ap.add_argument("--no-microbench", action="store_true", help="skip the scatter/gather roofline probes")
-    ap.add_argument("--configs", default="c3,c5,dup,c3r1,c5r1",
-                    help="full-size BASELINE configs reported next to the headline at N = 1 (c3 = 1 GB English-like "
+    ap.add_argument("--no-microbench", action="store_true", default=None, help="--full: skip the scatter/gather roofline probes")
+    ap.add_argument("--configs", default=None,
+                    help="--full: full-size BASELINE configs reported next to the headline at N = 1 (default "
+                         "c3,c5,dup,c3r1,c5r1: c3 = 1 GB English-like "
                          "SA + LCP, c5 = 1 GB UTF-8 + 10^6 positions(), dup = 1 GB near-duplicate documents, c3r1 / c5r1 = "
                          "configs 3 / 5 on round 1's easier inputs, for a like-for-like comparison with round 1 -- their "
                          "numpy generators take ~1 min each, so they are skipped once the run is past --config-budget seconds); "
@@ -433,14 +465,22 @@ def main():
     ap.add_argument("--dev-lib", default=None,
                     help="development A/B runs only (scripts/gpu_ab.sh): bind this build of the C ABI (libsuffix_hip_dev.so, hooks "
                          "compiled in) instead of the product library; the line then carries config.dev_lib")
-    ap.add_argument("--config-budget", type=float, default=150.0)
-    ap.add_argument("--config-size", type=int, default=1_000_000_000)
+    ap.add_argument("--config-budget", type=float, default=None, help="--full: seconds (default 150)")
+    ap.add_argument("--config-size", type=int, default=None, help="--full: bytes per config (default 1000000000)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed to DIR as float64 .npy files (a seeded sample of the suffix "
                          "array, at most 32 MB in all; see the module docstring); bench_outputs/ is ignored by git")
     args = ap.parse_args()
     if args.dump_outputs and args.steps < 1:
         ap.error("--dump-outputs needs at least one timed step (--steps >= 1)")
+    full_only = {"cpu_sample": 100_000_000, "no_verify": False, "calibrate": False, "no_microbench": False,
+                 "configs": "c3,c5,dup,c3r1,c5r1", "config_budget": 150.0, "config_size": 1_000_000_000}
+    given = ["--" + k.replace("_", "-") for k in full_only if getattr(args, k) is not None]
+    if given and not args.full:
+        ap.error(f"{', '.join(given)}: only a --full run does what these options tune")
+    for k, default in full_only.items():
+        if getattr(args, k) is None:
+            setattr(args, k, default)
 
     # multi-process GPU work on this host driver needs dmabuf IPC (RCCL fails with
     # hipIpcGetMemHandle: invalid argument otherwise); exported already, kept if it is not
@@ -576,6 +616,13 @@ def main():
             dump_outputs(torch, args.dump_outputs, {"sa": part, "sa_slice": [offset, n_all]}, rank, world)
     ms_per_step = elapsed * 1e3 / max(args.steps, 1)
     value = n_total * args.steps / elapsed / 1e6
+    head = headline_record(args, world, strong, n_local, n_total, value, ms_per_step)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     stats = eng.build_stats()
     phases = None
     if world > 1:
@@ -799,7 +846,7 @@ def main():
         t_cfg0 = time.perf_counter()
         for key in [k for k in args.configs.split(",") if k]:
             if key.endswith("r1") and time.perf_counter() - t_cfg0 > args.config_budget:
-                configs.append({"config": key, "skipped": "time budget of the default run (--config-budget)"})
+                configs.append({"config": key, "skipped": "time budget of the --full run (--config-budget)"})
                 continue
             try:
                 configs.append(fullsize_config(torch, eng, sdev, _gen, key, args.config_size, pins, dev))
@@ -808,13 +855,7 @@ def main():
 
     if rank == 0:
         # DETAIL lines first (one JSON object each, never the last line): everything round 3 packed into one 25 KB line
-        workload = (f"{n_local} B synthetic DNA (sigma=4, uniform, splitmix64) per GPU, u32 indices, device-resident text -> device SA"
-                    + ("" if world == 1 else f"; range-partitioned over {world} GPUs, text {n_total} B"))
-        if strong:
-            workload = (f"{n_total} B synthetic DNA (sigma=4, uniform, splitmix64 seed 0x5AF1C5 + 4"
-                        + (": BASELINE config 4's text" if n_total == 4_000_000_000 else "")
-                        + f"), ONE text cut into {world} shard(s) of {n_total // world} B, u32 indices, device-resident shards -> "
-                        + ("device SA" if world == 1 else f"one contiguous slice of the SA per GPU (range-partitioned, suffix_amd/dist.py)"))
+        workload = head["config"]["workload"]
         print("DETAIL " + json.dumps({"detail": "headline", "config": {"workload": workload, "text_bytes_total": n_total, "build": stats,
                                                                         "partitioned_phases_ms": phases},
                                       "roofline": roofline, "cpu_baseline": cpu, "lcp": lcp_info, "verification": how}))
@@ -844,10 +885,7 @@ def main():
             short_lcp = {"ms": lcp_info["ms_per_step"], "fused_sa_lcp_ms": lcp_info.get("fused_sa_lcp", {}).get("ms_per_step"),
                          "bit_exact_vs_oracle": lcp_info.get("bit_exact_vs_oracle")}
         out = {
-            "metric": METRIC, "value": round(value, 2), "unit": "MB/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u32",
-            "data": "synthetic",
+            **head,
             "config": {"workload": workload, "text_bytes_total": n_total, "partitioned_phases_ms": phases,
                        **({"dev_lib": os.path.basename(args.dev_lib)} if args.dev_lib else {})},
             "roofline": short_roof, "cpu_baseline": short_cpu, "lcp": short_lcp,

@@ -14,7 +14,7 @@ for kind in $KINDS; do
     envs=$(echo "$v" | tr ',' ' ')
     [ "$v" = "-" ] && envs=""
     if [ -n "${AB_BENCH:-}" ]; then
-      env $envs timeout 300 python bench.py --dev-lib $SFX_DEV_LIB --steps $AB_BENCH --warmup 3 --configs "" --cpu-sample 0 --no-microbench 2>> $OUT/ab.err | tail -1 | python -c "
+      env $envs timeout 300 python bench.py --dev-lib $SFX_DEV_LIB --steps $AB_BENCH --warmup 3 --full --configs "" --cpu-sample 0 --no-microbench 2>> $OUT/ab.err | tail -1 | python -c "
 import json,sys
 r=json.loads(sys.stdin.read())
 print(json.dumps({'variant': '$v', 'ms_per_step': r['ms_per_step'], 'MBps': r['value'], 'verified': r['verified'], 'kernels': r['roofline']['kernels'][:4]}))" >> $OUT/ab.jsonl

@@ -20,13 +20,13 @@ timeout 900 python -m pytest tests -m gpu -x -q --durations=15 > "$OUT/pytest_gp
 echo "pytest rc=$?" | tee -a "$OUT/summary.txt"; tail -25 "$OUT/pytest_gpu.log" | tee -a "$OUT/summary.txt"
 
 echo "== bench" | tee -a "$OUT/summary.txt"
-timeout 600 python bench.py --steps 5 --warmup 1 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python bench.py --steps 5 --warmup 1 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench rc=$?" | tee -a "$OUT/summary.txt"; cat "$OUT/bench.json" | tee -a "$OUT/summary.txt"; tail -5 "$OUT/bench.err" | tee -a "$OUT/summary.txt"
 
 if [ "${1:-}" != "quick" ]; then
   echo "== rocprofv3 kernel stats" | tee -a "$OUT/summary.txt"
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d "$OLDPWD/$OUT/prof" -o bench -- \
-      python "$OLDPWD/bench.py" --steps 3 --warmup 1 --cpu-sample 0 --no-verify) > "$OUT/rocprof.log" 2>&1
+      python "$OLDPWD/bench.py" --steps 3 --warmup 1 --full --cpu-sample 0 --no-verify) > "$OUT/rocprof.log" 2>&1
   echo "rocprof rc=$?" | tee -a "$OUT/summary.txt"
   find "$OUT/prof" -name "*kernel_stats*" | head -3 | tee -a "$OUT/summary.txt"
   f=$(find "$OUT/prof" -name "*kernel_stats.csv" | head -1)

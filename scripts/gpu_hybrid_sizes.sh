@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 for n in ${@:-100000000}; do
   for v in "SFX_HYBRID=1" ${HYBRID_OFF:+"SFX_HYBRID=0"}; do
     echo "== n=$n $v"
-    env $v timeout 200 python bench.py --size $n --steps 10 --warmup 2 --configs '' --cpu-sample 0 --no-microbench 2>/dev/null | python -c "
+    env $v timeout 200 python bench.py --size $n --steps 10 --warmup 2 --full --configs '' --cpu-sample 0 --no-microbench 2>/dev/null | python -c "
 import json,sys
 sys.path.insert(0,'scripts')
 import _benchout

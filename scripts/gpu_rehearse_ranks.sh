@@ -8,4 +8,4 @@ N="${1:-2}"
 SIZE="${2:-100000000}"
 export SFX_BENCH_SHARE_GPU=1
 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 \
-    --master-port 29511 bench.py --gpus "$N" --steps 3 --warmup 1 --size "$SIZE" 2>&1 | grep -E '^\{|Error|error|Traceback' | tail -5
+    --master-port 29511 bench.py --gpus "$N" --steps 3 --warmup 1 --full --size "$SIZE" 2>&1 | grep -E '^\{|Error|error|Traceback' | tail -5

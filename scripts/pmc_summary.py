@@ -4,7 +4,7 @@ usage: pmc_summary.py <dir-with-*counter_collection.csv> [...]   -> CSV on stdou
        pmc_summary.py --json OUT.json <dirs...>                   also writes the per-kernel
            HBM-traffic JSON bench.py reads (profiles/pmc_latest.json): FETCH_SIZE / WRITE_SIZE
            are reported in KiB; they are calibrated on the known byte counts of the
-           sfx::k_mb_copy launch of the same run (bench.py --calibrate), as
+           sfx::k_mb_copy launch of the same run (bench.py --full --calibrate), as
            MI355X_MICROARCH.md's HBM section prescribes (FETCH_SIZE reads half of a wide
            streaming read on gfx950; WRITE_SIZE is uncalibrated).
        pmc_summary.py --fullsize OUT.json KEY BUILDS <dirs...>    totals per build of every engine kernel of a 1 GB build,
@@ -160,7 +160,7 @@ def main(args):
     skip = ("mb_copy", "mb_gather", "mb_scatter", "mb_runscatter", "post_words")
     if json_out:
         out = {"commit": os.environ.get("SFX_COMMIT", "unknown"),
-               "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes over `bench.py --steps 1 --calibrate` "
+               "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes over `bench.py --steps 1 --full --calibrate` "
                          "(scripts/gpu_pmc.sh); counters in KiB x calibration factor from sfx::k_mb_copy (1 GiB in, 1 GiB out); "
                          "all symbols of one profile name summed, divided by their launches",
                "fetch_calibration": round(f_cal, 4), "write_calibration": round(w_cal, 4), "unmapped_symbols": sorted(unm), "kernels": {}}

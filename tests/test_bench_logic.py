@@ -167,3 +167,26 @@ def test_committed_bench_record_has_a_measured_traffic_for_every_large_kernel():
         for k in (d.get("roofline") or {}).get("kernels") or []:
             if name in seen and k["share_of_build"] >= 0.15:
                 assert k.get("traffic") and k["traffic"] >= 0.98 * k["algo_bytes_per_launch"], (name, k)
+
+
+class _Args:
+    steps, warmup, dev_lib = 20, 2, None
+
+
+def test_headline_record_carries_the_contract_keys_alone():
+    rec = bench.headline_record(_Args, 1, False, 100_000_000, 100_000_000, 76_213.456, 1.3121)
+    assert rec["value"] == 76213.46 and rec["ms_per_step"] == 1.312 and rec["unit"] == "MB/s" and rec["dtype"] == "u32"
+    assert rec["metric"] == bench.METRIC and rec["higher_is_better"] is True and rec["scaling"] == "weak"
+    assert rec["config"] == {"workload": "100000000 B synthetic DNA (sigma=4, uniform, splitmix64) per GPU, u32 indices, "
+                                         "device-resident text -> device SA", "text_bytes_total": 100_000_000}
+    strong = bench.headline_record(_Args, 2, True, 2_000_000_000, 4_000_000_000, 1.0, 1.0)
+    assert strong["scaling"] == "strong" and "ONE text cut into 2 shard(s)" in strong["config"]["workload"]
+
+
+@pytest.mark.parametrize("opt", [["--configs", ""], ["--cpu-sample", "0"], ["--no-verify"], ["--calibrate"], ["--no-microbench"],
+                                 ["--config-budget", "1"], ["--config-size", "1000"]])
+def test_options_of_the_full_run_are_refused_without_full(opt):
+    # (argument parsing comes before any import of torch or the engine: no device needed)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"] + opt, capture_output=True, text=True,
+                         timeout=60)
+    assert out.returncode == 2 and opt[0] in out.stderr and "--full" in out.stderr, out.stderr

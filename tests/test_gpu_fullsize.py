@@ -207,7 +207,7 @@ def _bench_over_rccl(extra, size="20000000", share_gpu=False):
         env["SFX_BENCH_SHARE_GPU"] = "1"                 # both ranks on cuda:0, gloo instead of RCCL (bench.py's rehearsal hook)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", size, "--configs", "", "--cpu-sample", "0"] + extra,
+                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", size, "--full", "--configs", "", "--cpu-sample", "0"] + extra,
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -269,7 +269,7 @@ def test_two_rank_bench_rehearsal_on_one_gpu(case):
         assert "ONE text cut into 2" in rec["config"]["workload"], rec["config"]
         import subprocess
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--total-size", "6000001",
-                              "--no-microbench"], capture_output=True, text=True, timeout=600)
+                              "--full", "--no-microbench"], capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-2500:]
         one = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
         assert one["scaling"] == "strong" and one["n_gpus"] == 1 and one["verified"] is True, one
@@ -277,3 +277,26 @@ def test_two_rank_bench_rehearsal_on_one_gpu(case):
     else:
         rec = _bench_over_rccl(["--input", "periodic"], size="1000000", share_gpu=True)
         assert "fallback" in rec["config"]["partitioned_phases_ms"], rec["config"]
+
+
+def test_plain_bench_run_prints_the_headline_alone(oracle, tmp_path):
+    """bench.py without --full: warm-up, timed steps, --dump-outputs and ONE JSON line with the headline keys -- none of the
+    records a --full run adds, no DETAIL lines.  The dumped sample of the last timed step is the oracle's suffix array at
+    the sampled positions."""
+    import subprocess
+    n = 3_000_000
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--size", str(n),
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-2500:]
+    assert not [l for l in out.stdout.splitlines() if l.startswith("DETAIL ")], out.stdout[-1500:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-1500:]
+    rec = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"} <= set(rec), rec
+    assert not {"roofline", "cpu_baseline", "lcp", "value_sa_plus_lcp", "end_to_end", "verified"} & set(rec), rec
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["value"] > 0 and rec["config"]["text_bytes_total"] == n, rec
+    host = _gen.dna(n)
+    exp = oracle.sais(host)
+    idx = np.load(str(tmp_path / "sa_index.npy")).astype(np.int64)
+    got = np.load(str(tmp_path / "sa.npy")).astype(np.int64)
+    assert idx.size > 0 and np.array_equal(got, exp[idx].astype(np.int64))
