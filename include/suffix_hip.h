@@ -152,6 +152,45 @@ int sfx_lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uin
 int sfx_doc_lookup_dev(const uint32_t* d_positions, uint64_t count, const uint64_t* d_doc_starts, uint64_t ndocs,
                        uint32_t* d_doc, uint32_t* d_offset, void* stream);
 
+/* ---- generalized suffix array over a document collection (README.md:60-74, without the separator) ------
+ * Documents D_0 .. D_{m-1} (any bytes, NUL and 0xFF included; empty ones allowed) are given as ONE buffer of
+ * n = sum |D_i| bytes plus doc_starts[0..ndocs) (non-decreasing, doc_starts[0] == 0, none past n; document i =
+ * text[doc_starts[i] .. doc_starts[i + 1]), the last one ending at n).  No separator byte is involved.
+ *   sa_out   all n positions doc_starts[i] + o, ordered by the TRUNCATED suffix D_i[o..] (bytes, a proper prefix
+ *            first), equal truncated suffixes by document index -- the suffix array of D_0 $_0 D_1 $_1 ... with
+ *            distinct terminators $_0 < $_1 < ... < every byte, terminator suffixes left out;
+ *   da_out   da_out[r] = the document of sa_out[r];
+ *   lcp_out  lcp_out[0] = 0, lcp_out[r] = common prefix of the truncated suffixes at ranks r - 1 and r (never past
+ *            either one's document end).
+ * With one document, sa_out / lcp_out are exactly sfx_build_sa_u32 / sfx_build_lcp_u32 of it.  da / lcp may be NULL.
+ * SFX_ERR_ARG: ndocs == 0 with n > 0, or doc_starts not as above (checked on the device, read back once);
+ * SFX_ERR_TOO_LARGE: n > u32::MAX.  n == 0 succeeds. */
+uint64_t sfx_gsa_workspace_bytes(uint64_t n, uint64_t ndocs);
+int sfx_build_gsa_u32_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_starts, uint64_t ndocs,
+                          uint32_t* d_sa, uint32_t* d_da, uint32_t* d_lcp,
+                          void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_build_gsa_u32(const uint8_t* text, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs,
+                      uint32_t* sa_out, uint32_t* da_out, uint32_t* lcp_out);
+/* Resident generalized index over (text, doc_starts, GSA, DA).  q matches at (i, o) iff |q| <= |D_i| - o and
+ * D_i[o .. o + |q|) == q: matches never span documents and form one GSA interval.  Per query: start / end (0 / 0
+ * when empty; the empty query is empty), found, any (a position, UINT32_MAX for none) and ndocs = the number of
+ * DISTINCT documents containing q.  Outputs may be NULL to skip.  The _dev create borrows its four arrays (keep them
+ * alive and unchanged); it checks doc_starts and every (table, DA) entry (SFX_ERR_ARG) and builds the previous-rank-
+ * of-the-same-document array (4 n bytes).  sfx_gindex_create copies host arrays. */
+typedef struct sfx_gindex sfx_gindex;
+int  sfx_gindex_create_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_starts, uint64_t ndocs,
+                           const uint32_t* d_sa, const uint32_t* d_da, void* stream, sfx_gindex** out);
+int  sfx_gindex_create(const uint8_t* text, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs,
+                       const uint32_t* sa, const uint32_t* da, sfx_gindex** out);
+int  sfx_gindex_query_dev(const sfx_gindex* gx, const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq,
+                          uint32_t* d_start, uint32_t* d_end, uint8_t* d_found, uint32_t* d_any,
+                          uint32_t* d_ndocs, void* stream);
+/* the same with host buffers (queries concatenated as for sfx_positions_batch) */
+int  sfx_gindex_query(const sfx_gindex* gx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq,
+                      uint32_t* start_out, uint32_t* end_out, uint8_t* found_out, uint32_t* any_out,
+                      uint32_t* ndocs_out);
+void sfx_gindex_destroy(sfx_gindex* gx);
+
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the
  * text shard [shard_begin, shard_end).

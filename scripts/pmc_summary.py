@@ -65,6 +65,11 @@ NAMES = [
     ("k_pyr_reduce", "tree_pyramid"), ("k_lcp_intervals_open", "tree_intervals_open"), ("k_lcp_intervals", "tree_intervals"),
     ("k_tree_parents", "tree_parents"), ("k_tree_leaves", "tree_leaves"), ("k_tree_level", "tree_level"),
     ("k_dir_mark", "dir_mark"), ("k_dir_block_min", "dir_block_min"), ("k_dir_scan_mins", "dir_scan_mins"), ("k_dir_fill", "dir_fill"),
+    ("k_gsa_check_docs", "gsa_check_docs"), ("k_gsa_check_index", "gsa_check_index"), ("k_gsa_affected", "gsa_affected"),
+    ("k_gsa_scan_count<", "gsa_scan"), ("k_gsa_scan_top<", "gsa_scan"), ("k_gsa_scan_apply<", "gsa_scan"), ("k_gsa_compact", "gsa_compact"),
+    ("k_gsa_fixup_keys", "gsa_fixup_sort"), ("k_gsa_merge_affected", "gsa_merge"), ("k_gsa_merge_unaffected", "gsa_merge"),
+    ("k_gsa_lcp", "gsa_lcp"), ("k_gsa_query", "gsa_query"), ("k_gsa_doc_count", "gsa_doc_count"), ("k_gsa_prev_keys", "gsa_prev"),
+    ("k_gsa_prev", "gsa_prev"),
     ("k_doc_lookup", "doc_lookup"), ("k_query_keys", "query_keys"), ("k_query_batch_tree", "query_batch_tree"),
     ("k_query_batch_dir", "query_batch_dir"), ("k_query_tree_long", "query_tree_long"), ("k_query_batch", "query_batch"),
     # -- not part of a build's profile: the polled read-back and the memory-system probes

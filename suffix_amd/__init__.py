@@ -7,6 +7,7 @@ binding, the `SuffixTable` mirror of the reference API, device-resident entry
 points for torch tensors, and the range-partitioned multi-GPU build.
 """
 from ._lib import Engine, SuffixHipError, default_engine  # noqa: F401
+from .generalized import GeneralizedSuffixTable  # noqa: F401
 from .table import SuffixTable  # noqa: F401
 
-__all__ = ["SuffixTable", "Engine", "SuffixHipError", "default_engine"]
+__all__ = ["SuffixTable", "GeneralizedSuffixTable", "Engine", "SuffixHipError", "default_engine"]

@@ -69,6 +69,14 @@ ABI = [
     ("sfx_lcp_intervals_workspace_bytes", _u64, [_u64]),
     ("sfx_lcp_intervals_dev", _int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     ("sfx_doc_lookup_dev", _int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    ("sfx_gsa_workspace_bytes", _u64, [_u64, _u64]),
+    ("sfx_build_gsa_u32_dev", _int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
+    ("sfx_build_gsa_u32", _int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    ("sfx_gindex_create_dev", _int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
+    ("sfx_gindex_create", _int, [_vp, _u64, _vp, _u64, _vp, _vp, ctypes.POINTER(_vp)]),
+    ("sfx_gindex_query_dev", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("sfx_gindex_query", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    ("sfx_gindex_destroy", None, [_vp]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),

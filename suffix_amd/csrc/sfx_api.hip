@@ -206,6 +206,22 @@ struct sfx_index {
     int tree_levels = 0;
 };
 
+struct sfx_gindex {
+    const uint8_t* d_text = nullptr;
+    const uint64_t* d_starts = nullptr;
+    const uint32_t* d_sa = nullptr;
+    const uint32_t* d_da = nullptr;
+    uint64_t n = 0, ndocs = 0;
+    uint32_t* d_prev = nullptr;     // previous rank of the same document (owned)
+    void* own[4] = {nullptr, nullptr, nullptr, nullptr};   // sfx_gindex_create: the copies of text, starts, sa, da
+    // per-batch scratch of the document counts, reused across calls: the stream of a batch waits for the previous one
+    std::mutex mu;
+    void* scratch = nullptr;
+    uint64_t scratch_bytes = 0;
+    hipEvent_t done = nullptr;
+    bool used = false;
+};
+
 namespace sfx {
 // alphabet -> dense codes, directory shape, device build; SFX_ERR_ARG if the table holds an entry >= n
 static int index_build_directory(sfx_index* ix, hipStream_t st)
@@ -606,6 +622,190 @@ int sfx_doc_lookup_dev(const uint32_t* d_positions, uint64_t count, const uint64
                        uint32_t* d_doc, uint32_t* d_offset, void* stream)
 {
     return doc_lookup_dev(d_positions, count, d_doc_starts, ndocs, d_doc, d_offset, (hipStream_t)stream);
+}
+
+// ---- generalized suffix array over documents ------------------------------------------------------------
+uint64_t sfx_gsa_workspace_bytes(uint64_t n, uint64_t ndocs)
+{
+    (void)ndocs;                                       // (the document starts are read in place)
+    return gsa_workspace_bytes(n);
+}
+int sfx_build_gsa_u32_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_starts, uint64_t ndocs, uint32_t* d_sa,
+                          uint32_t* d_da, uint32_t* d_lcp, void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    return gsa_build_dev(d_text, n, d_doc_starts, ndocs, d_sa, d_da, d_lcp, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sfx_build_gsa_u32(const uint8_t* text, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs, uint32_t* sa_out,
+                      uint32_t* da_out, uint32_t* lcp_out)
+{
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!text || !doc_starts || ndocs == 0 || !sa_out) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    DevBuf dt, dst, ds, dd, dl, dw;
+    const uint64_t wsb = gsa_workspace_bytes(n);
+    SFX_TRY(dt.alloc(n));
+    SFX_TRY(dst.alloc(ndocs * sizeof(uint64_t)));
+    SFX_TRY(ds.alloc(n * sizeof(uint32_t)));
+    if (da_out) SFX_TRY(dd.alloc(n * sizeof(uint32_t)));
+    if (lcp_out) SFX_TRY(dl.alloc(n * sizeof(uint32_t)));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(dt.p, text, n, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dst.p, doc_starts, ndocs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(gsa_build_dev((const uint8_t*)dt.p, n, (const uint64_t*)dst.p, ndocs, (uint32_t*)ds.p, (uint32_t*)dd.p, (uint32_t*)dl.p,
+                          dw.p, wsb, st));
+    SFX_HIP(hipMemcpyAsync(sa_out, ds.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (da_out) SFX_HIP(hipMemcpyAsync(da_out, dd.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (lcp_out) SFX_HIP(hipMemcpyAsync(lcp_out, dl.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+
+int sfx_gindex_create_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_starts, uint64_t ndocs, const uint32_t* d_sa,
+                          const uint32_t* d_da, void* stream, sfx_gindex** out)
+{
+    if (!out) return SFX_ERR_ARG;
+    *out = nullptr;
+    if (n > 0xFFFFFFFFull || ndocs > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n && (!d_text || !d_doc_starts || ndocs == 0 || !d_sa || !d_da)) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    sfx_gindex* gx = new sfx_gindex();
+    gx->d_text = d_text;
+    gx->d_starts = d_doc_starts;
+    gx->d_sa = d_sa;
+    gx->d_da = d_da;
+    gx->n = n;
+    gx->ndocs = ndocs;
+    int rc = SFX_OK;
+    if (n) {
+        hipStream_t st = (hipStream_t)stream;
+        do {
+            hipError_t e = hipMalloc((void**)&gx->d_prev, n * sizeof(uint32_t));
+            if (e != hipSuccess) { note_hip_error(e, "hipMalloc(prev)", __FILE__, __LINE__); gx->d_prev = nullptr; rc = SFX_ERR_HIP; break; }
+            DevBuf dw;
+            const uint64_t wsb = gindex_workspace_bytes(n);
+            rc = dw.alloc(wsb);
+            if (rc != SFX_OK) break;
+            bool bad = false;
+            rc = gindex_build_dev(d_doc_starts, ndocs, n, d_sa, d_da, gx->d_prev, dw.p, wsb, st, &bad);
+            // (the workspace returns to the pool: nothing may still use it, and the index serves other streams)
+            e = hipStreamSynchronize(st);
+            if (rc == SFX_OK && e != hipSuccess) { note_hip_error(e, "sync", __FILE__, __LINE__); rc = SFX_ERR_HIP; }
+            if (rc == SFX_OK && bad) rc = SFX_ERR_ARG;
+        } while (0);
+    }
+    if (rc != SFX_OK) { sfx_gindex_destroy(gx); return rc; }
+    *out = gx;
+    return SFX_OK;
+}
+
+int sfx_gindex_create(const uint8_t* text, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs, const uint32_t* sa,
+                      const uint32_t* da, sfx_gindex** out)
+{
+    if (!out) return SFX_ERR_ARG;
+    *out = nullptr;
+    if (n > 0xFFFFFFFFull || ndocs > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n && (!text || !doc_starts || ndocs == 0 || !sa || !da)) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    const uint64_t bytes[4] = {n, ndocs * sizeof(uint64_t), n * sizeof(uint32_t), n * sizeof(uint32_t)};
+    const void* src[4] = {text, doc_starts, sa, da};
+    int rc = SFX_OK;
+    hipStream_t st = call_stream();
+    for (int i = 0; i < 4 && rc == SFX_OK; i++) {
+        if (!bytes[i]) continue;
+        hipError_t e = hipMalloc(&p[i], bytes[i]);
+        if (e == hipSuccess) e = hipMemcpyAsync(p[i], src[i], bytes[i], hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) { note_hip_error(e, "gindex copy", __FILE__, __LINE__); rc = SFX_ERR_HIP; }
+    }
+    sfx_gindex* gx = nullptr;
+    if (rc == SFX_OK)
+        rc = sfx_gindex_create_dev((const uint8_t*)p[0], n, (const uint64_t*)p[1], ndocs, (const uint32_t*)p[2], (const uint32_t*)p[3],
+                                   st, &gx);
+    if (rc != SFX_OK) {
+        (void)hipStreamSynchronize(st);
+        for (void* q : p) if (q) (void)hipFree(q);
+        return rc;
+    }
+    for (int i = 0; i < 4; i++) gx->own[i] = p[i];
+    *out = gx;
+    return SFX_OK;
+}
+
+int sfx_gindex_query_dev(const sfx_gindex* gx, const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq, uint32_t* d_start,
+                         uint32_t* d_end, uint8_t* d_found, uint32_t* d_any, uint32_t* d_ndocs, void* stream)
+{
+    if (!gx) return SFX_ERR_ARG;
+    if (nq == 0) return SFX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (!d_ndocs)
+        return gindex_query_dev(gx->d_text, gx->n, gx->d_starts, gx->ndocs, gx->d_sa, gx->d_da, gx->d_prev, d_qbytes, d_qoff, nq, d_start,
+                                d_end, d_found, d_any, nullptr, nullptr, 0, st);
+    sfx_gindex* g = const_cast<sfx_gindex*>(gx);
+    std::lock_guard<std::mutex> lk(g->mu);
+    const uint64_t need = gindex_query_scratch_bytes(nq);
+    if (!g->done) SFX_HIP(hipEventCreateWithFlags(&g->done, hipEventDisableTiming));
+    if (g->scratch_bytes < need) {
+        if (g->scratch) {
+            if (g->used) SFX_HIP(hipEventSynchronize(g->done));
+            (void)hipFree(g->scratch);
+            g->scratch = nullptr;
+            g->scratch_bytes = 0;
+            g->used = false;
+        }
+        SFX_HIP(hipMalloc(&g->scratch, need));
+        g->scratch_bytes = need;
+    }
+    if (g->used) SFX_HIP(hipStreamWaitEvent(st, g->done, 0));
+    const int rc = gindex_query_dev(gx->d_text, gx->n, gx->d_starts, gx->ndocs, gx->d_sa, gx->d_da, gx->d_prev, d_qbytes, d_qoff, nq,
+                                    d_start, d_end, d_found, d_any, d_ndocs, g->scratch, g->scratch_bytes, st);
+    SFX_HIP(hipEventRecord(g->done, st));
+    g->used = true;
+    return rc;
+}
+
+int sfx_gindex_query(const sfx_gindex* gx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq, uint32_t* start_out,
+                     uint32_t* end_out, uint8_t* found_out, uint32_t* any_out, uint32_t* ndocs_out)
+{
+    if (!gx || (nq && !qoff)) return SFX_ERR_ARG;
+    if (nq == 0) return SFX_OK;
+    const uint64_t qtotal = qoff[nq];
+    if (qtotal && !qbytes) return SFX_ERR_ARG;
+    for (uint64_t k = 0; k < nq; k++) if (qoff[k + 1] < qoff[k]) return SFX_ERR_ARG;
+    DevBuf dq, doff, ds, de, df, da, dn;
+    SFX_TRY(dq.alloc(qtotal));
+    SFX_TRY(doff.alloc((nq + 1) * sizeof(uint64_t)));
+    if (start_out) SFX_TRY(ds.alloc(nq * 4));
+    if (end_out) SFX_TRY(de.alloc(nq * 4));
+    if (found_out) SFX_TRY(df.alloc(nq));
+    if (any_out) SFX_TRY(da.alloc(nq * 4));
+    if (ndocs_out) SFX_TRY(dn.alloc(nq * 4));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    if (qtotal) SFX_HIP(hipMemcpyAsync(dq.p, qbytes, qtotal, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(doff.p, qoff, (nq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(sfx_gindex_query_dev(gx, (const uint8_t*)dq.p, (const uint64_t*)doff.p, nq, (uint32_t*)ds.p, (uint32_t*)de.p, (uint8_t*)df.p,
+                                 (uint32_t*)da.p, (uint32_t*)dn.p, st));
+    if (start_out) SFX_HIP(hipMemcpyAsync(start_out, ds.p, nq * 4, hipMemcpyDeviceToHost, st));
+    if (end_out) SFX_HIP(hipMemcpyAsync(end_out, de.p, nq * 4, hipMemcpyDeviceToHost, st));
+    if (found_out) SFX_HIP(hipMemcpyAsync(found_out, df.p, nq, hipMemcpyDeviceToHost, st));
+    if (any_out) SFX_HIP(hipMemcpyAsync(any_out, da.p, nq * 4, hipMemcpyDeviceToHost, st));
+    if (ndocs_out) SFX_HIP(hipMemcpyAsync(ndocs_out, dn.p, nq * 4, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+
+void sfx_gindex_destroy(sfx_gindex* gx)
+{
+    if (!gx) return;
+    if (gx->used) (void)hipEventSynchronize(gx->done);
+    if (gx->done) (void)hipEventDestroy(gx->done);
+    if (gx->scratch) (void)hipFree(gx->scratch);
+    if (gx->d_prev) (void)hipFree(gx->d_prev);
+    for (void* p : gx->own) if (p) (void)hipFree(p);
+    delete gx;
 }
 
 // ---- partitioned build ---------------------------------------------------------------------

@@ -423,6 +423,19 @@ int lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_
                       uint32_t* d_leaf_parent, void* ws, uint64_t ws_bytes, hipStream_t st);
 int doc_lookup_dev(const uint32_t* d_pos, uint64_t count, const uint64_t* d_starts, uint64_t ndocs, uint32_t* d_doc,
                    uint32_t* d_offset, hipStream_t st);
+// generalized suffix array over documents without separators, and its resident index (sfx_tree.hip)
+uint64_t gsa_workspace_bytes(uint64_t n);
+int gsa_build_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, uint32_t* d_gsa, uint32_t* d_da,
+                  uint32_t* d_glcp, void* ws, uint64_t ws_bytes, hipStream_t st);
+uint64_t gindex_workspace_bytes(uint64_t n);
+// checks doc_starts and every (table, DA) entry (*bad_out), then PREV[r] = the previous rank of the same document
+int gindex_build_dev(const uint64_t* d_starts, uint64_t ndocs, uint64_t n, const uint32_t* d_sa, const uint32_t* d_da,
+                     uint32_t* d_prev, void* ws, uint64_t ws_bytes, hipStream_t st, bool* bad_out);
+uint64_t gindex_query_scratch_bytes(uint64_t nq);
+int gindex_query_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, const uint32_t* d_sa,
+                     const uint32_t* d_da, const uint32_t* d_prev, const uint8_t* d_q, const uint64_t* d_qoff, uint64_t nq,
+                     uint32_t* d_start, uint32_t* d_end, uint8_t* d_found, uint32_t* d_any, uint32_t* d_ndocs, void* scratch,
+                     uint64_t scratch_bytes, hipStream_t st);
 
 sfx_build_stats& tls_build_stats();
 

@@ -275,6 +275,27 @@ static uint64_t pyramid_words(uint64_t n)
     }
     return words;
 }
+// the levels above an LCP array (pyramid_words(n) u32 at w)
+static int pyramid_build(const uint32_t* d_lcp, uint64_t n, uint32_t* w, const char* name, hipStream_t st, Pyramid* out)
+{
+    Pyramid& py = *out;
+    py.lvl[0] = d_lcp;
+    py.len[0] = n;
+    py.levels = 1;
+    uint64_t len = n;
+    while (py.levels < kPyrMaxLevels && len > 1) {
+        const uint64_t out_len = (len + kPyrFan - 1) / kPyrFan;
+        const unsigned grid = (unsigned)dmin<uint64_t>((out_len + kBlock - 1) / kBlock, kMaxGrid);
+        SFX_LAUNCH(name, (double)len * 4, k_pyr_reduce, grid, kBlock, st, py.lvl[py.levels - 1], len, w, out_len, 1);
+        py.lvl[py.levels] = w;
+        py.len[py.levels] = out_len;
+        py.levels++;
+        w += (out_len + 63) & ~uint64_t(63);
+        len = out_len;
+    }
+    for (int l = py.levels; l < kPyrMaxLevels; l++) { py.lvl[l] = nullptr; py.len[l] = 0; }
+    return SFX_OK;
+}
 // (+ the list of boundaries whose searches leave their tile: n / 16 entries, and its counter)
 static uint64_t open_list_cap(uint64_t n) { return n / 16 + 4096; }
 uint64_t lcp_intervals_workspace_bytes(uint64_t n)
@@ -290,22 +311,7 @@ int lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_
     if (!d_lcp || !d_lb || !d_rb || !d_node || !d_parent || !d_leaf_parent) return SFX_ERR_ARG;
     if (!ws || ws_bytes < lcp_intervals_workspace_bytes(n)) return SFX_ERR_WORKSPACE;
     Pyramid py;
-    py.lvl[0] = d_lcp;
-    py.len[0] = n;
-    py.levels = 1;
-    uint32_t* w = reinterpret_cast<uint32_t*>(ws);
-    uint64_t len = n;
-    while (py.levels < kPyrMaxLevels && len > 1) {
-        const uint64_t out_len = (len + kPyrFan - 1) / kPyrFan;
-        const unsigned grid = (unsigned)dmin<uint64_t>((out_len + kBlock - 1) / kBlock, kMaxGrid);
-        SFX_LAUNCH("tree_pyramid", (double)len * 4, k_pyr_reduce, grid, kBlock, st, py.lvl[py.levels - 1], len, w, out_len, 1);
-        py.lvl[py.levels] = w;
-        py.len[py.levels] = out_len;
-        py.levels++;
-        w += (out_len + 63) & ~uint64_t(63);
-        len = out_len;
-    }
-    for (int l = py.levels; l < kPyrMaxLevels; l++) { py.lvl[l] = nullptr; py.len[l] = 0; }
+    SFX_TRY(pyramid_build(d_lcp, n, reinterpret_cast<uint32_t*>(ws), "tree_pyramid", st, &py));
     const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
     {
         char* tail = reinterpret_cast<char*>(ws) + ((pyramid_words(n) * sizeof(uint32_t) + 255) & ~uint64_t(255));
@@ -331,6 +337,546 @@ int doc_lookup_dev(const uint32_t* d_pos, uint64_t count, const uint64_t* d_star
     if (!d_pos || !d_starts || ndocs == 0 || (!d_doc && !d_offset)) return SFX_ERR_ARG;
     const unsigned grid = (unsigned)dmin<uint64_t>((count + kBlock - 1) / kBlock, kMaxGrid);
     SFX_LAUNCH("doc_lookup", (double)count * 12, k_doc_lookup, grid, kBlock, st, d_pos, count, d_starts, ndocs, d_doc, d_offset);
+    return SFX_OK;
+}
+
+// ---- generalized suffix array over a document collection (no separators) ---------------------------------------
+// Documents D_0 .. D_{m-1} are one text T plus their start offsets.  The GSA orders every (document, offset) by the
+// TRUNCATED suffix D_i[o..] (a proper prefix first, equal ones by document); DA names the document of every entry,
+// GLCP is the common prefix of neighbours inside their documents.  It is derived from the plain SA + LCP of T:
+// for the suffix s at plain rank r with L = docend(s) - s bytes left in its document, I(s) = the nearest q <= r with
+// LCP[q] < L is the first rank of the plain interval of all suffixes that start with the truncated string, and
+//   GSA = the plain suffixes sorted by (I(s), L, s).
+// (Distinct truncated strings: I is ordered as the strings unless one is a proper prefix of the other, in which case
+// both start the same interval or the shorter one's contains the longer one's, and L decides.  Equal (I, L) = equal
+// strings: the document, i.e. the position, decides -- not the plain rank, which follows the NEXT document's text.)
+// A suffix with LCP[r] < L is "unaffected": I = r, it keeps its plain place relative to the other unaffected ones.
+// Only the affected ones (tails of documents whose truncated string goes on in the text that follows) are sorted,
+// then merged in; with one document nothing is affected and no sort runs.
+constexpr uint32_t kGsaNone = 0xFFFFFFFFu;
+
+// the document of position p: the last start <= p (empty documents share their start with the next one)
+__device__ __forceinline__ uint64_t gsa_doc_of(const uint64_t* __restrict__ starts, uint64_t ndocs, uint64_t p)
+{
+    uint64_t lo = 0, hi = ndocs;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (starts[mid] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo ? lo - 1 : 0;
+}
+__device__ __forceinline__ uint64_t gsa_doc_end(const uint64_t* __restrict__ starts, uint64_t ndocs, uint64_t n, uint64_t d)
+{
+    return d + 1 < ndocs ? starts[d + 1] : n;
+}
+// min of lvl[0][lo..hi] (inclusive, 1 <= lo <= hi): at most 2 x 63 reads per level, whatever the values are
+__device__ __forceinline__ uint32_t range_min(const Pyramid& py, uint64_t lo, uint64_t hi)
+{
+    uint32_t m = 0xFFFFFFFFu;
+    for (int l = 0;; l++) {
+        const uint32_t* a = py.lvl[l];
+        if (l + 1 >= py.levels || hi - lo < 2 * kPyrFan) {
+            for (uint64_t i = lo; i <= hi; i++) m = dmin(m, a[i]);
+            return m;
+        }
+        while (lo % kPyrFan) m = dmin(m, a[lo++]);
+        while ((hi + 1) % kPyrFan) m = dmin(m, a[hi--]);
+        lo /= kPyrFan;                                   // (>= 1 block remains; block 0 of a level is never reached: lo >= 1)
+        hi = (hi + 1) / kPyrFan - 1;
+    }
+}
+
+// doc_starts: [0] == 0, non-decreasing, none past n
+__global__ void __launch_bounds__(kBlock)
+k_gsa_check_docs(const uint64_t* __restrict__ starts, uint64_t ndocs, uint64_t n, uint32_t* __restrict__ bad)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < ndocs; i += stride) {
+        const uint64_t v = starts[i];
+        if (v > n || (i == 0 ? v != 0 : v < starts[i - 1])) *bad = 1u;
+    }
+}
+// per rank: bytes left in the document, and the affected flag (LCP[r] >= L) for the scan
+__global__ void __launch_bounds__(kBlock)
+k_gsa_affected(const uint32_t* __restrict__ sa, const uint32_t* __restrict__ lcp, uint64_t n, const uint64_t* __restrict__ starts,
+               uint64_t ndocs, uint32_t* __restrict__ rem, uint32_t* __restrict__ flag)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) {
+        const uint64_t s = sa[r];
+        const uint32_t L = (uint32_t)(gsa_doc_end(starts, ndocs, n, gsa_doc_of(starts, ndocs, s)) - s);
+        rem[r] = L;
+        flag[r] = (r > 0 && lcp[r] >= L) ? 1u : 0u;
+    }
+}
+// exclusive scan of u32 values into T (in place when T is u32): partial sums per workgroup chunk, a one-workgroup
+// scan of those, then each chunk again with its carry.  out[count] = the total.
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+k_gsa_scan_count(const uint32_t* __restrict__ in, uint64_t count, uint64_t chunk, T* __restrict__ part)
+{
+    __shared__ T sh[kWavesPerBlock];
+    const uint64_t b = (uint64_t)blockIdx.x * chunk, e = dmin<uint64_t>(b + chunk, count);
+    T acc = 0;
+    for (uint64_t i = b + threadIdx.x; i < e; i += kBlock) acc += (T)in[i];
+    T total;
+    (void)block_scan_add_excl<T>(acc, sh, total);
+    if (threadIdx.x == 0) part[blockIdx.x] = total;
+}
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+k_gsa_scan_top(T* __restrict__ part, unsigned nb, T* __restrict__ out_total)
+{
+    __shared__ T sh[kWavesPerBlock];
+    T carry = 0;
+    for (unsigned base = 0; base < nb; base += kBlock) {
+        const unsigned i = base + threadIdx.x;
+        T total;
+        const T ex = block_scan_add_excl<T>(i < nb ? part[i] : (T)0, sh, total);
+        if (i < nb) part[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) *out_total = carry;
+}
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+k_gsa_scan_apply(const uint32_t* in, uint64_t count, uint64_t chunk, const T* __restrict__ part, T* out)
+{
+    __shared__ T sh[kWavesPerBlock];
+    const uint64_t b = (uint64_t)blockIdx.x * chunk, e = dmin<uint64_t>(b + chunk, count);
+    T run = part[blockIdx.x];
+    for (uint64_t base = b; base < e; base += kBlock) {            // (uniform trip count: the block scan has barriers)
+        const uint64_t i = base + threadIdx.x;
+        const T v = i < e ? (T)in[i] : (T)0;
+        T total;
+        const T ex = block_scan_add_excl<T>(v, sh, total);
+        if (i < e) out[i] = run + ex;
+        run += total;
+    }
+}
+template <class T>
+static int gsa_scan(const uint32_t* in, uint64_t count, T* out, T* part, hipStream_t st)
+{
+    const unsigned nb = (unsigned)dmin<uint64_t>((count + kBlock - 1) / kBlock, dmin<unsigned>(kMaxGrid, grid_cap()));
+    const uint64_t chunk = (count + nb - 1) / nb;
+    SFX_LAUNCH("gsa_scan", (double)count * 4, k_gsa_scan_count<T>, nb, kBlock, st, in, count, chunk, part);
+    SFX_LAUNCH("gsa_scan", (double)nb * sizeof(T), k_gsa_scan_top<T>, 1, kBlock, st, part, nb, out + count);
+    SFX_LAUNCH("gsa_scan", (double)count * (4 + sizeof(T)), k_gsa_scan_apply<T>, nb, kBlock, st, in, count, chunk,
+               (const T*)part, out);
+    return SFX_OK;
+}
+// the affected suffixes in plain-rank order: key = L << 32 | position (sorted on the position bits first), value = rank
+__global__ void __launch_bounds__(kBlock)
+k_gsa_compact(const uint32_t* __restrict__ P, const uint32_t* __restrict__ sa, const uint32_t* __restrict__ rem, uint64_t n,
+              uint64_t* __restrict__ K, uint32_t* __restrict__ V)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) {
+        const uint32_t j = P[r];
+        if (P[r + 1] == j) continue;
+        K[j] = ((uint64_t)rem[r] << 32) | sa[r];
+        V[j] = (uint32_t)r;
+    }
+}
+// between the two sort stages: key = I << lbits | L (I over the pyramid), in place; the position order stays as the
+// order of ties for the (stable) sort on these bits
+__global__ void __launch_bounds__(kBlock)
+k_gsa_fixup_keys(uint64_t* __restrict__ K, const uint32_t* __restrict__ V, uint64_t m, Pyramid py, int lbits)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < m; j += stride) {
+        const uint32_t L = (uint32_t)(K[j] >> 32);
+        const uint64_t I = prev_smaller(py, (uint64_t)V[j] + 1, L);      // (LCP[r] >= L: some q < r)
+        K[j] = (I << lbits) | L;
+    }
+}
+// output slot of a sorted affected suffix: its index among them + the unaffected ranks with a smaller (r, L, s)
+__global__ void __launch_bounds__(kBlock)
+k_gsa_merge_affected(const uint64_t* __restrict__ K, const uint32_t* __restrict__ V, uint64_t m, uint64_t n, int lbits,
+                     const uint32_t* __restrict__ P, const uint32_t* __restrict__ sa, const uint32_t* __restrict__ rem,
+                     uint32_t* __restrict__ gsa, uint32_t* __restrict__ R, uint32_t* __restrict__ bad)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t lmask = (1ull << lbits) - 1;
+    for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < m; j += stride) {
+        const uint64_t I = K[j] >> lbits;
+        const uint32_t L = (uint32_t)(K[j] & lmask);
+        const uint32_t r = V[j], s = sa[r];
+        uint64_t before = I - P[I];                                    // unaffected ranks < I
+        if (P[I + 1] == P[I]) {                                        // rank I itself, if unaffected
+            const uint32_t li = rem[I], si = sa[I];
+            if (li < L || (li == L && si < s)) before++;
+        }
+        const uint64_t o = j + before;
+        if (o >= n) { *bad = 1u; continue; }                           // (an engine bug: reported as SFX_ERR_INTERNAL, never written)
+        gsa[o] = s;
+        R[o] = r;
+    }
+}
+// output slot of an unaffected rank: its index among them + the affected suffixes with a smaller key (bisection)
+__global__ void __launch_bounds__(kBlock)
+k_gsa_merge_unaffected(const uint32_t* __restrict__ P, const uint32_t* __restrict__ sa, const uint32_t* __restrict__ rem, uint64_t n,
+                       const uint64_t* __restrict__ K, const uint32_t* __restrict__ V, uint64_t m, int lbits,
+                       uint32_t* __restrict__ gsa, uint32_t* __restrict__ R, uint32_t* __restrict__ bad)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) {
+        const uint32_t pr = P[r];
+        if (P[r + 1] != pr) continue;
+        const uint64_t key = (r << lbits) | rem[r];
+        const uint32_t s = sa[r];
+        uint64_t lo = 0, hi = m;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            const uint64_t km = K[mid];
+            if (km < key || (km == key && sa[V[mid]] < s)) lo = mid + 1; else hi = mid;
+        }
+        const uint64_t o = (r - pr) + lo;
+        if (o >= n) { *bad = 1u; continue; }                           // (as above)
+        gsa[o] = s;
+        R[o] = (uint32_t)r;
+    }
+}
+// GLCP[o] = min(plain lcp of the two neighbours' ranks, both lengths left); R == nullptr: the identity (nothing moved)
+__global__ void __launch_bounds__(kBlock)
+k_gsa_lcp(const uint32_t* __restrict__ R, const uint32_t* __restrict__ rem, Pyramid py, uint64_t n, uint32_t* __restrict__ glcp)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint32_t* lcp = py.lvl[0];
+    for (uint64_t o = (uint64_t)blockIdx.x * kBlock + threadIdx.x; o < n; o += stride) {
+        if (o == 0) { glcp[0] = 0; continue; }
+        const uint64_t ra = R ? R[o - 1] : o - 1, rb = R ? R[o] : o;
+        const uint64_t lo = dmin(ra, rb) + 1, hi = dmax(ra, rb);
+        const uint32_t v = lo == hi ? lcp[lo] : range_min(py, lo, hi);
+        glcp[o] = dmin(v, dmin(rem[ra], rem[rb]));
+    }
+}
+
+template <class A> static void gsa_phase_carve(A& a, uint64_t n, uint32_t** pyr, uint32_t** rem, uint32_t** P, uint32_t** R,
+                                               uint64_t** part, uint64_t** K0, uint32_t** V0, uint64_t** K1, uint32_t** V1,
+                                               uint32_t** scratch)
+{
+    *pyr = a.template take<uint32_t>(pyramid_words(n) + 64);
+    *rem = a.template take<uint32_t>(n);
+    *P = a.template take<uint32_t>(n + 1);
+    *R = a.template take<uint32_t>(n);
+    *part = a.template take<uint64_t>(kMaxGrid + 64);
+    *K0 = a.template take<uint64_t>(n);
+    *V0 = a.template take<uint32_t>(n);
+    *K1 = a.template take<uint64_t>(n);
+    *V1 = a.template take<uint32_t>(n);
+    *scratch = a.template take<uint32_t>(radix_scratch_words(n));
+}
+struct GsaSizer {                                  // ArenaSizer with pointer-returning take (for gsa_phase_carve)
+    uint64_t used = 0;
+    template <class T> T* take(uint64_t count) { used += (count * sizeof(T) + kArenaAlign - 1) & ~(kArenaAlign - 1); return nullptr; }
+};
+static uint64_t gsa_phase_bytes(uint64_t n)
+{
+    GsaSizer z;
+    uint32_t *a, *b, *c, *d, *v0, *v1, *sc;
+    uint64_t *p, *k0, *k1;
+    gsa_phase_carve(z, n, &a, &b, &c, &d, &p, &k0, &v0, &k1, &v1, &sc);
+    return z.used;
+}
+// [bad flag | plain SA | plain LCP | max(plain build workspace, the GSA phase)]
+uint64_t gsa_workspace_bytes(uint64_t n)
+{
+    GsaSizer z;
+    z.take<uint32_t>(64);
+    z.take<uint32_t>(n);
+    z.take<uint32_t>(n);
+    return z.used + dmax(sa_lcp_workspace_bytes(n), gsa_phase_bytes(n));
+}
+
+static int gsa_check_docs(const uint64_t* d_starts, uint64_t ndocs, uint64_t n, uint32_t* d_bad, hipStream_t st, bool* bad)
+{
+    SFX_HIP(hipMemsetAsync(d_bad, 0, sizeof(uint32_t), st));
+    const unsigned grid = (unsigned)dmin<uint64_t>((ndocs + kBlock - 1) / kBlock, kMaxGrid);
+    SFX_LAUNCH("gsa_check_docs", (double)ndocs * 8, k_gsa_check_docs, grid, kBlock, st, d_starts, ndocs, n, d_bad);
+    uint32_t h = 0;
+    SFX_TRY(read_back(&h, d_bad, sizeof(h), st));
+    *bad = h != 0;
+    return SFX_OK;
+}
+
+int gsa_build_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, uint32_t* d_gsa, uint32_t* d_da,
+                  uint32_t* d_glcp, void* ws, uint64_t ws_bytes, hipStream_t st)
+{
+    if (n > 0xFFFFFFFFull || ndocs > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!d_text || !d_starts || ndocs == 0 || !d_gsa) return SFX_ERR_ARG;
+    if (!ws || ws_bytes < gsa_workspace_bytes(n)) return SFX_ERR_WORKSPACE;
+    Arena a(ws, ws_bytes);
+    uint32_t* d_bad = a.take<uint32_t>(64);
+    uint32_t* sa = a.take<uint32_t>(n);
+    uint32_t* lcp = a.take<uint32_t>(n);
+    char* rest = a.base + a.used;
+    const uint64_t rest_bytes = a.size - a.used;
+    bool bad = false;
+    SFX_TRY(gsa_check_docs(d_starts, ndocs, n, d_bad, st, &bad));
+    if (bad) return SFX_ERR_ARG;
+    SFX_TRY(build_sa_lcp_u32_dev(d_text, n, sa, lcp, rest, rest_bytes, st));
+    // the plain build's workspace is free again: the GSA phase takes it over
+    Arena b(rest, rest_bytes);
+    uint32_t *pyr, *rem, *P, *R, *V0, *V1, *scratch;
+    uint64_t *part, *K0, *K1;
+    gsa_phase_carve(b, n, &pyr, &rem, &P, &R, &part, &K0, &V0, &K1, &V1, &scratch);
+    if (b.overflow) return SFX_ERR_INTERNAL;
+    Pyramid py;
+    SFX_TRY(pyramid_build(lcp, n, pyr, "gsa_pyramid", st, &py));
+    const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
+    SFX_LAUNCH("gsa_affected", (double)n * 16, k_gsa_affected, grid, kBlock, st, (const uint32_t*)sa, (const uint32_t*)lcp, n,
+               d_starts, ndocs, rem, P);
+    SFX_TRY(gsa_scan<uint32_t>(P, n, P, reinterpret_cast<uint32_t*>(part), st));
+    uint32_t m = 0;
+    SFX_TRY(read_back(&m, P + n, sizeof(m), st));
+    const uint32_t* Rout = nullptr;
+    if (m == 0) {
+        SFX_HIP(hipMemcpyAsync(d_gsa, sa, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    } else {
+        const unsigned mgrid = (unsigned)dmin<uint64_t>((m + kBlock - 1) / kBlock, kMaxGrid);
+        const int pbits = bits_for(n - 1), lbits = bits_for(n);
+        SFX_LAUNCH("gsa_compact", (double)n * 8 + (double)m * 12, k_gsa_compact, grid, kBlock, st, (const uint32_t*)P,
+                   (const uint32_t*)sa, (const uint32_t*)rem, n, K0, V0);
+        // stage 1: by position (the order of identical truncated suffixes); stage 2: stably by (I, L)
+        int in1 = 0;
+        SFX_TRY(radix_sort_kv64(K0, V0, K1, V1, m, 0, pbits, scratch, st, &in1, nullptr, nullptr));
+        uint64_t* K = in1 ? K1 : K0;
+        uint32_t* V = in1 ? V1 : V0;
+        SFX_LAUNCH("gsa_fixup_sort", (double)m * 12, k_gsa_fixup_keys, mgrid, kBlock, st, K, (const uint32_t*)V, (uint64_t)m, py, lbits);
+        int in1b = 0;
+        SFX_TRY(radix_sort_kv64(K, V, in1 ? K0 : K1, in1 ? V0 : V1, m, 0, pbits + lbits, scratch, st, &in1b, nullptr, nullptr));
+        if (in1b) { K = in1 ? K0 : K1; V = in1 ? V0 : V1; }
+        SFX_LAUNCH("gsa_merge", (double)m * 24, k_gsa_merge_affected, mgrid, kBlock, st, (const uint64_t*)K, (const uint32_t*)V,
+                   (uint64_t)m, n, lbits, (const uint32_t*)P, (const uint32_t*)sa, (const uint32_t*)rem, d_gsa, R, d_bad);
+        SFX_LAUNCH("gsa_merge", (double)n * 20, k_gsa_merge_unaffected, grid, kBlock, st, (const uint32_t*)P, (const uint32_t*)sa,
+                   (const uint32_t*)rem, n, (const uint64_t*)K, (const uint32_t*)V, (uint64_t)m, lbits, d_gsa, R, d_bad);
+        // a slot outside [0, n) cannot come out of a correct merge; if one did, the flag (still 0 from the document
+        // check) says so and the build fails instead of returning a table with a stale entry
+        uint32_t merge_bad = 0;
+        SFX_TRY(read_back(&merge_bad, d_bad, sizeof(merge_bad), st));
+        if (merge_bad) return SFX_ERR_INTERNAL;
+        Rout = R;
+    }
+    if (d_glcp)
+        SFX_LAUNCH("gsa_lcp", (double)n * (Rout ? 20 : 16), k_gsa_lcp, grid, kBlock, st, Rout, (const uint32_t*)rem, py, n, d_glcp);
+    if (d_da)
+        SFX_LAUNCH("gsa_doc_array", (double)n * 8, k_doc_lookup, grid, kBlock, st, (const uint32_t*)d_gsa, n, d_starts, ndocs, d_da,
+                   (uint32_t*)nullptr);
+    return SFX_OK;
+}
+
+// ---- queries on the GSA ---------------------------------------------------------------------------------------------
+// q against the truncated suffix at rank r: < 0 it sorts below q (a suffix that ends inside q included), 0 q is its
+// prefix (a match), > 0 above
+__device__ __forceinline__ int gsa_cmp(const uint8_t* __restrict__ text, uint64_t n, const uint64_t* __restrict__ starts, uint64_t ndocs,
+                                       const uint32_t* __restrict__ sa, const uint32_t* __restrict__ da, uint64_t r,
+                                       const uint8_t* __restrict__ q, uint64_t ql)
+{
+    const uint64_t s = sa[r];
+    const uint64_t L = gsa_doc_end(starts, ndocs, n, da[r]) - s;
+    const uint64_t k = dmin(L, ql);
+    for (uint64_t i = 0; i < k; i++) {
+        const uint8_t a = text[s + i], b = q[i];
+        if (a != b) return a < b ? -1 : 1;
+    }
+    return L < ql ? -1 : 0;
+}
+__global__ void __launch_bounds__(kBlock)
+k_gsa_query(const uint8_t* __restrict__ text, uint64_t n, const uint64_t* __restrict__ starts, uint64_t ndocs,
+            const uint32_t* __restrict__ sa, const uint32_t* __restrict__ da, const uint8_t* __restrict__ qb,
+            const uint64_t* __restrict__ qoff, uint64_t nq, uint32_t* __restrict__ d_start, uint32_t* __restrict__ d_end,
+            uint8_t* __restrict__ d_found, uint32_t* __restrict__ d_any, uint32_t* __restrict__ d_len)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nq; k += stride) {
+        const uint64_t q0 = qoff[k], ql = qoff[k + 1] - q0;
+        const uint8_t* q = qb + q0;
+        uint64_t lo = 0, hi = 0;
+        if (ql && n) {
+            uint64_t a = 0, b = n;                                       // first rank >= q
+            while (a < b) {
+                const uint64_t mid = (a + b) >> 1;
+                if (gsa_cmp(text, n, starts, ndocs, sa, da, mid, q, ql) < 0) a = mid + 1; else b = mid;
+            }
+            lo = a;
+            b = n;                                                       // first rank > q (not prefixed by it)
+            while (a < b) {
+                const uint64_t mid = (a + b) >> 1;
+                if (gsa_cmp(text, n, starts, ndocs, sa, da, mid, q, ql) <= 0) a = mid + 1; else b = mid;
+            }
+            hi = a;
+            if (lo == hi) lo = hi = 0;
+        }
+        if (d_start) d_start[k] = (uint32_t)lo;
+        if (d_end) d_end[k] = (uint32_t)hi;
+        if (d_found) d_found[k] = hi > lo ? 1 : 0;
+        if (d_any) d_any[k] = hi > lo ? sa[lo] : kGsaNone;
+        if (d_len) d_len[k] = (uint32_t)(hi - lo);
+    }
+}
+// document frequency: the ranks r of [start, end) whose previous rank of the same document lies before start.  The work is
+// the TOTAL interval length (prefix offs over the queries), 1024 consecutive ranks per wave, so one huge interval spreads
+// over the whole device; a wave whose ranks all belong to one query adds its count once.
+constexpr unsigned kGsaCountPerLane = 16;
+__global__ void __launch_bounds__(kBlock)
+k_gsa_doc_count(const uint64_t* __restrict__ offs, uint64_t nq, const uint32_t* __restrict__ start, const uint32_t* __restrict__ prev,
+                uint32_t* __restrict__ ndocs)
+{
+    const uint64_t total = offs[nq];
+    const uint64_t seg_len = (uint64_t)kWave * kGsaCountPerLane;
+    const uint64_t nseg = (total + seg_len - 1) / seg_len;
+    const uint64_t waves = (uint64_t)gridDim.x * kWavesPerBlock;
+    const unsigned lane = lane_id();
+    for (uint64_t seg = (uint64_t)blockIdx.x * kWavesPerBlock + wave_id(); seg < nseg; seg += waves) {
+        const uint64_t t0 = seg * seg_len;
+        const bool active = t0 + lane < total;
+        unsigned long long k = 0;
+        uint32_t cnt = 0;
+        if (active) {
+            uint64_t t = t0 + lane;
+            uint64_t a = 0, b = nq + 1;                                  // first offs[] > t, minus one
+            while (a < b) {
+                const uint64_t mid = (a + b) >> 1;
+                if (offs[mid] <= t) a = mid + 1; else b = mid;
+            }
+            k = a - 1;
+            uint32_t sk = start[k];
+            uint64_t ok = offs[k], onext = offs[k + 1];
+            for (unsigned i = 0; i < kGsaCountPerLane && t < total; i++, t += kWave) {
+                while (t >= onext) {                                     // the next non-empty interval
+                    if (cnt) atomicAdd(&ndocs[k], cnt);
+                    cnt = 0;
+                    k++;
+                    sk = start[k];
+                    ok = onext;
+                    onext = offs[k + 1];
+                }
+                const uint32_t p = prev[sk + (uint32_t)(t - ok)];
+                cnt += (p == kGsaNone || p < sk) ? 1u : 0u;
+            }
+        }
+        const unsigned long long k0 = __shfl(k, 0);
+        if (__all(!active || k == k0)) {
+            uint32_t sum = cnt;
+            for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+            if (lane == 0 && sum) atomicAdd(&ndocs[k0], sum);
+        } else if (cnt) {
+            atomicAdd(&ndocs[k], cnt);
+        }
+    }
+}
+// index checks: doc_starts as for the build, every table entry a position of the document DA names
+__global__ void __launch_bounds__(kBlock)
+k_gsa_check_index(const uint32_t* __restrict__ sa, const uint32_t* __restrict__ da, uint64_t n, const uint64_t* __restrict__ starts,
+                  uint64_t ndocs, uint32_t* __restrict__ bad)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) {
+        const uint64_t s = sa[r], d = da[r];
+        if (s >= n || d >= ndocs || starts[d] > s || gsa_doc_end(starts, ndocs, n, d) <= s) *bad = 1u;
+    }
+}
+__global__ void __launch_bounds__(kBlock)
+k_gsa_prev_keys(const uint32_t* __restrict__ da, uint64_t n, uint64_t* __restrict__ K, uint32_t* __restrict__ V)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) {
+        K[r] = da[r];
+        V[r] = (uint32_t)r;
+    }
+}
+// (DA, rank) sorted stably by DA: the previous entry of the same document is the previous rank with that DA value
+__global__ void __launch_bounds__(kBlock)
+k_gsa_prev(const uint64_t* __restrict__ K, const uint32_t* __restrict__ V, uint64_t n, uint32_t* __restrict__ prev)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += stride)
+        prev[V[k]] = (k > 0 && K[k - 1] == K[k]) ? V[k - 1] : kGsaNone;
+}
+
+uint64_t gindex_workspace_bytes(uint64_t n)
+{
+    ArenaSizer z;
+    z.take<uint32_t>(64);
+    z.take<uint64_t>(n);
+    z.take<uint32_t>(n);
+    z.take<uint64_t>(n);
+    z.take<uint32_t>(n);
+    z.take<uint32_t>(radix_scratch_words(n));
+    return z.used;
+}
+int gindex_build_dev(const uint64_t* d_starts, uint64_t ndocs, uint64_t n, const uint32_t* d_sa, const uint32_t* d_da,
+                     uint32_t* d_prev, void* ws, uint64_t ws_bytes, hipStream_t st, bool* bad_out)
+{
+    Arena a(ws, ws_bytes);
+    uint32_t* d_bad = a.take<uint32_t>(64);
+    uint64_t* K0 = a.take<uint64_t>(n);
+    uint32_t* V0 = a.take<uint32_t>(n);
+    uint64_t* K1 = a.take<uint64_t>(n);
+    uint32_t* V1 = a.take<uint32_t>(n);
+    uint32_t* scratch = a.take<uint32_t>(radix_scratch_words(n));
+    if (a.overflow) return SFX_ERR_WORKSPACE;
+    bool bad = false;
+    SFX_TRY(gsa_check_docs(d_starts, ndocs, n, d_bad, st, &bad));
+    if (!bad) {
+        const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
+        SFX_LAUNCH("gsa_check_index", (double)n * 8, k_gsa_check_index, grid, kBlock, st, d_sa, d_da, n, d_starts, ndocs, d_bad);
+        uint32_t h = 0;
+        SFX_TRY(read_back(&h, d_bad, sizeof(h), st));
+        bad = h != 0;
+    }
+    *bad_out = bad;
+    if (bad) return SFX_OK;
+    const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
+    SFX_LAUNCH("gsa_prev", (double)n * 16, k_gsa_prev_keys, grid, kBlock, st, d_da, n, K0, V0);
+    int in1 = 0;
+    SFX_TRY(radix_sort_kv64(K0, V0, K1, V1, n, 0, bits_for(ndocs - 1), scratch, st, &in1, nullptr, nullptr));
+    SFX_LAUNCH("gsa_prev", (double)n * 16, k_gsa_prev, grid, kBlock, st, (const uint64_t*)(in1 ? K1 : K0), (const uint32_t*)(in1 ? V1 : V0),
+               n, d_prev);
+    return SFX_OK;
+}
+
+// [lens nq u32 | starts nq u32 | offs nq + 1 u64 | scan partials]
+uint64_t gindex_query_scratch_bytes(uint64_t nq)
+{
+    ArenaSizer z;
+    z.take<uint32_t>(nq);
+    z.take<uint32_t>(nq);
+    z.take<uint64_t>(nq + 1);
+    z.take<uint64_t>(kMaxGrid + 64);
+    return z.used;
+}
+int gindex_query_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, const uint32_t* d_sa,
+                     const uint32_t* d_da, const uint32_t* d_prev, const uint8_t* d_q, const uint64_t* d_qoff, uint64_t nq,
+                     uint32_t* d_start, uint32_t* d_end, uint8_t* d_found, uint32_t* d_any, uint32_t* d_ndocs, void* scratch,
+                     uint64_t scratch_bytes, hipStream_t st)
+{
+    if (nq == 0) return SFX_OK;
+    if (!d_qoff || nq > 0xFFFFFFFFull) return SFX_ERR_ARG;
+    uint32_t *lens = nullptr, *qstart = d_start;
+    uint64_t *offs = nullptr, *part = nullptr;
+    if (d_ndocs) {
+        Arena a(scratch, scratch_bytes);
+        lens = a.take<uint32_t>(nq);
+        uint32_t* own_start = a.take<uint32_t>(nq);
+        offs = a.take<uint64_t>(nq + 1);
+        part = a.take<uint64_t>(kMaxGrid + 64);
+        if (!scratch || a.overflow) return SFX_ERR_WORKSPACE;
+        if (!qstart) qstart = own_start;
+    }
+    const unsigned qgrid = (unsigned)dmin<uint64_t>((nq + kBlock - 1) / kBlock, kMaxGrid);
+    SFX_LAUNCH("gsa_query", (double)nq * 32, k_gsa_query, qgrid, kBlock, st, d_text, n, d_starts, ndocs, d_sa, d_da, d_q, d_qoff, nq,
+               qstart, d_end, d_found, d_any, lens);
+    if (!d_ndocs) return SFX_OK;
+    SFX_HIP(hipMemsetAsync(d_ndocs, 0, nq * sizeof(uint32_t), st));
+    SFX_TRY(gsa_scan<uint64_t>(lens, nq, offs, part, st));
+    // (the total is on the device: the grid is sized by its bound nq x n, the kernel reads the real one)
+    const double bound = (double)nq * (double)n;
+    const double per_block = (double)kWave * kGsaCountPerLane * kWavesPerBlock;
+    const unsigned cgrid = (unsigned)dmax(1.0, dmin((double)dmin<unsigned>(kMaxGrid, grid_cap()), bound / per_block + 1.0));
+    SFX_LAUNCH("gsa_doc_count", 0.0, k_gsa_doc_count, cgrid, kBlock, st, (const uint64_t*)offs, nq, (const uint32_t*)qstart, d_prev, d_ndocs);
     return SFX_OK;
 }
 

@@ -184,6 +184,81 @@ def doc_lookup(positions, doc_starts, engine=None):
     return doc, off
 
 
+def gsa_workspace(n, ndocs, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_gsa_workspace_bytes(int(n), int(ndocs))), dtype=torch.uint8, device=device)
+
+
+def build_gsa(text, doc_starts, out_sa=None, out_da=None, out_lcp=None, workspace=None, want_da=True, want_lcp=True,
+              engine=None):
+    """Generalized suffix array of the documents text[doc_starts[i]:doc_starts[i + 1]] (no separators; doc_starts an
+    int64 tensor on the text's device, doc_starts[0] == 0): -> (sa, da, lcp), uint32 in int32 storage; da / lcp are
+    None unless wanted.  See include/suffix_hip.h for the order and the LCP."""
+    eng = engine or default_engine()
+    _check_u8(text)
+    if doc_starts.dtype != torch.int64 or doc_starts.dim() != 1 or not doc_starts.is_contiguous():
+        raise TypeError("doc_starts must be a contiguous 1-D int64 tensor")
+    n, nd = text.numel(), doc_starts.numel()
+    if text.is_cuda:
+        eng.require_device()
+    if out_sa is None:
+        out_sa = torch.empty(n, dtype=torch.int32, device=text.device)
+    if want_da and out_da is None:
+        out_da = torch.empty(n, dtype=torch.int32, device=text.device)
+    if want_lcp and out_lcp is None:
+        out_lcp = torch.empty(n, dtype=torch.int32, device=text.device)
+    if workspace is None:
+        workspace = gsa_workspace(n, nd, text.device, eng)
+    with _on(text):
+        eng.check(eng.lib.sfx_build_gsa_u32_dev(_p(text), n, _p(doc_starts), nd, _p(out_sa), _p(out_da), _p(out_lcp),
+                                                _p(workspace), workspace.numel(), _stream_ptr(text)), "sfx_build_gsa_u32_dev")
+    return out_sa, out_da, out_lcp
+
+
+class GeneralizedDeviceIndex:
+    """Resident generalized index over device tensors (text, doc_starts, GSA, DA) -- borrowed, keep them alive;
+    `query` = per query (start, end, found, any, ndocs): matches inside one document only, ndocs = the number of
+    distinct documents that contain the query (sfx_gindex_query_dev)."""
+
+    def __init__(self, text, doc_starts, sa, da, engine=None):
+        self._eng = engine or default_engine()
+        _check_u8(text)
+        self._keep = (text, doc_starts, sa, da)
+        self._text = text
+        h = ctypes.c_void_p()
+        with _on(text):
+            self._eng.check(self._eng.lib.sfx_gindex_create_dev(_p(text), text.numel(), _p(doc_starts), doc_starts.numel(), _p(sa),
+                                                                _p(da), _stream_ptr(text), ctypes.byref(h)), "sfx_gindex_create_dev")
+        self._h = h
+
+    def query(self, qbytes, qoff):
+        """qbytes: uint8 tensor, qoff: int64 tensor of nq + 1 offsets, both contiguous and on the text's device."""
+        dev = self._text.device
+        if qbytes.dtype != torch.uint8 or qbytes.dim() != 1 or not qbytes.is_contiguous():
+            raise TypeError("qbytes must be a contiguous 1-D uint8 tensor")
+        if qoff.dtype != torch.int64 or qoff.dim() != 1 or not qoff.is_contiguous() or qoff.numel() < 1:
+            raise TypeError("qoff must be a contiguous 1-D int64 tensor of nq + 1 offsets")
+        if qbytes.device != dev or qoff.device != dev:
+            raise ValueError(f"qbytes and qoff must be on the index's device ({dev})")
+        nq = qoff.numel() - 1
+        start = torch.empty(nq, dtype=torch.int32, device=dev)
+        end = torch.empty(nq, dtype=torch.int32, device=dev)
+        found = torch.empty(nq, dtype=torch.uint8, device=dev)
+        anyp = torch.empty(nq, dtype=torch.int32, device=dev)
+        ndocs = torch.empty(nq, dtype=torch.int32, device=dev)
+        with _on(self._text):
+            self._eng.check(self._eng.lib.sfx_gindex_query_dev(self._h, _p(qbytes), _p(qoff), nq, _p(start), _p(end), _p(found),
+                                                               _p(anyp), _p(ndocs), _stream_ptr(self._text)), "sfx_gindex_query_dev")
+        return start, end, found, anyp, ndocs
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._eng.lib.sfx_gindex_destroy(h)
+
+    __del__ = close
+
+
 def widen_u64(sa32, out=None, engine=None):
     """u32 index tensor (int32 storage) -> int64 tensor holding the same indices (config 4)."""
     eng = engine or default_engine()

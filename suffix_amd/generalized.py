@@ -1,0 +1,207 @@
+"""`GeneralizedSuffixTable` -- one suffix table over many documents, the capability the reference names as
+missing (/root/reference/README.md:60-74) and approximates by joining the documents with a separator byte.
+
+Here no separator is involved: documents may hold any byte, no suffix runs past the end of its document, and
+no match spans two documents.
+
+    table()          every (document, offset) as the text position doc_starts[i] + offset, ordered by the
+                     TRUNCATED suffix D_i[offset..] (a proper prefix first; equal ones by document index)
+    doc_array()      the document of every table entry
+    lcp_lens()       common prefix of neighbouring truncated suffixes (0 first)
+    positions(q)     [(doc, offset)] of every occurrence of q, in table order
+    documents(q)     sorted distinct documents containing q; document_frequency(q) = their number
+
+Construction and queries run on the GPU through the C ABI (sfx_build_gsa_u32, sfx_gindex_*); there is no CPU
+path except `new_naive`, the definition itself.
+"""
+import ctypes
+
+import numpy as np
+
+from ._lib import default_engine
+from .table import _as_bytes, _ptr
+
+_NONE = 0xFFFFFFFF
+
+
+class GeneralizedSuffixTable:
+    def __init__(self, docs, engine=None, _arrays=None):
+        self._eng = engine or default_engine()
+        docs = list(docs)
+        self._was_str = [isinstance(d, str) for d in docs]
+        self._docs = [_as_bytes(d) for d in docs]
+        self._text = b"".join(self._docs)
+        self._tarr = np.frombuffer(self._text, dtype=np.uint8)
+        starts = np.zeros(len(self._docs), dtype=np.uint64)
+        if len(self._docs) > 1:
+            starts[1:] = np.cumsum([len(d) for d in self._docs[:-1]], dtype=np.uint64)
+        self._starts = starts
+        self._index = None
+        n = self._tarr.size
+        if n > 0xFFFFFFFF:
+            raise OverflowError("GeneralizedSuffixTable: more than u32::MAX bytes in all")
+        if _arrays is not None:
+            self._table, self._da, self._lcp = _arrays
+            return
+        table = np.zeros(n, dtype=np.uint32)
+        da = np.zeros(n, dtype=np.uint32)
+        lcp = np.zeros(n, dtype=np.uint32)
+        if n:
+            self._eng.require_device()
+            self._eng.check(self._eng.lib.sfx_build_gsa_u32(_ptr(self._tarr), n, _ptr(starts), starts.size, _ptr(table),
+                                                             _ptr(da), _ptr(lcp)), "GeneralizedSuffixTable::new")
+        self._table, self._da, self._lcp = table, da, lcp
+
+    # -- constructors -----------------------------------------------------------------------
+    @classmethod
+    def new(cls, docs, engine=None):
+        return cls(docs, engine=engine)
+
+    @classmethod
+    def new_naive(cls, docs, engine=None):
+        """The definition on the host: every (document, offset) sorted by (truncated suffix, document) with Python's
+        byte comparison, the LCP by direct comparison.  O(N^2 log N) in the worst case (N = total bytes): meant for
+        collections of up to a few thousand bytes, as the known answer of tests -- never a fallback of new()."""
+        bdocs = [_as_bytes(d) for d in docs]
+        items = [(d, o) for d, doc in enumerate(bdocs) for o in range(len(doc))]
+        items.sort(key=lambda it: (bdocs[it[0]][it[1]:], it[0]))
+        starts = np.zeros(len(bdocs), dtype=np.int64)
+        if len(bdocs) > 1:
+            starts[1:] = np.cumsum([len(b) for b in bdocs[:-1]])
+        table = np.array([starts[d] + o for d, o in items], dtype=np.uint32)
+        da = np.array([d for d, _ in items], dtype=np.uint32)
+        lcp = np.zeros(len(items), dtype=np.uint32)
+        for r in range(1, len(items)):
+            a = bdocs[items[r - 1][0]][items[r - 1][1]:]
+            b = bdocs[items[r][0]][items[r][1]:]
+            k, m = 0, min(len(a), len(b))
+            while k < m and a[k] == b[k]:
+                k += 1
+            lcp[r] = k
+        return cls(docs, engine=engine, _arrays=(table, da, lcp))
+
+    def __del__(self):
+        ix, self._index = getattr(self, "_index", None), None
+        if ix:
+            try:
+                self._eng.lib.sfx_gindex_destroy(ix)
+            except Exception:
+                pass
+
+    # -- accessors --------------------------------------------------------------------------
+    def table(self):
+        return self._table
+
+    def doc_array(self):
+        return self._da
+
+    def lcp_lens(self):
+        return self._lcp
+
+    def doc_starts(self):
+        return self._starts
+
+    def len(self):
+        return int(self._table.size)
+
+    __len__ = len
+
+    def is_empty(self):
+        return self.len() == 0
+
+    def num_docs(self):
+        return len(self._docs)
+
+    def document(self, i):
+        d = self._docs[i]
+        return d.decode("utf-8") if self._was_str[i] else d
+
+    def position(self, r):
+        """-> (document, offset inside it) of table()[r]."""
+        d = int(self._da[r])
+        return d, int(self._table[r]) - int(self._starts[d])
+
+    def suffix_bytes(self, r):
+        d, o = self.position(r)
+        return self._docs[d][o:]
+
+    def suffix(self, r):
+        return self.suffix_bytes(r).decode("utf-8")
+
+    # -- queries ----------------------------------------------------------------------------
+    def _ensure_index(self):
+        if self._index is None:
+            self._eng.require_device()
+            h = ctypes.c_void_p()
+            self._eng.check(self._eng.lib.sfx_gindex_create(_ptr(self._tarr), self.len(), _ptr(self._starts), self._starts.size,
+                                                             _ptr(self._table), _ptr(self._da), ctypes.byref(h)),
+                            "sfx_gindex_create")
+            self._index = h
+        return self._index
+
+    def query_batch(self, queries):
+        """-> dict of uint32 arrays start, end (table()[start:end] = the matches; 0/0 when none), found (bool),
+        any (a position or 0xFFFFFFFF), ndocs (distinct documents containing the query)."""
+        qs = [_as_bytes(q) for q in queries]
+        nq = len(qs)
+        off = np.zeros(nq + 1, dtype=np.uint64)
+        if qs:
+            off[1:] = np.cumsum([len(q) for q in qs], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(qs), dtype=np.uint8)
+        out = {"start": np.zeros(nq, dtype=np.uint32), "end": np.zeros(nq, dtype=np.uint32),
+               "found": np.zeros(nq, dtype=np.uint8), "any": np.full(nq, _NONE, dtype=np.uint32),
+               "ndocs": np.zeros(nq, dtype=np.uint32)}
+        if nq and self.len():
+            self._eng.check(self._eng.lib.sfx_gindex_query(self._ensure_index(), _ptr(blob), _ptr(off), nq, _ptr(out["start"]),
+                                                            _ptr(out["end"]), _ptr(out["found"]), _ptr(out["any"]),
+                                                            _ptr(out["ndocs"])), "sfx_gindex_query")
+        out["found"] = out["found"].astype(bool)
+        return out
+
+    def _pairs(self, s, e):
+        d = self._da[s:e].astype(np.int64)
+        o = self._table[s:e].astype(np.int64) - self._starts[d].astype(np.int64)
+        return list(zip(d.tolist(), o.tolist()))
+
+    def positions_batch(self, queries):
+        res = self.query_batch(queries)
+        return [self._pairs(int(s), int(e)) for s, e in zip(res["start"], res["end"])]
+
+    def positions(self, query):
+        """[(document, offset)] of every occurrence of `query` inside one document, in table order."""
+        return self.positions_batch([query])[0]
+
+    def contains_batch(self, queries):
+        return self.query_batch(queries)["found"]
+
+    def contains(self, query):
+        return bool(self.contains_batch([query])[0])
+
+    def any_position_batch(self, queries):
+        res = self.query_batch(queries)
+        out = []
+        for p in res["any"].tolist():
+            if p == _NONE:
+                out.append(None)
+            else:
+                d = int(np.searchsorted(self._starts, p, side="right")) - 1
+                out.append((d, p - int(self._starts[d])))
+        return out
+
+    def any_position(self, query):
+        """(document, offset) of some occurrence, or None (the empty query included, as SuffixTable)."""
+        return self.any_position_batch([query])[0]
+
+    def documents_batch(self, queries):
+        res = self.query_batch(queries)
+        return [sorted(set(self._da[int(s):int(e)].tolist())) for s, e in zip(res["start"], res["end"])]
+
+    def documents(self, query):
+        """Sorted distinct ids of the documents that contain `query`."""
+        return self.documents_batch([query])[0]
+
+    def document_frequency_batch(self, queries):
+        return self.query_batch(queries)["ndocs"]
+
+    def document_frequency(self, query):
+        return int(self.document_frequency_batch([query])[0])
