@@ -1220,7 +1220,6 @@ k_small_groups(const uint32_t* __restrict__ V, const uint32_t* __restrict__ S, c
 constexpr uint32_t kTieRunMax = 8;
 constexpr unsigned kTieSlots = 1024;                              // counter lines of k_tie_direct (4 words each: in deep_slots)
 constexpr int kTieBatch = 2;                                      // stretches a lane lists per round of its wave
-__device__ __forceinline__ bool tie_bit(const uint32_t* __restrict__ mask, uint64_t r) { return (mask[r >> 5] >> (r & 31u)) & 1u; }
 // bits [r0, r0 + len) of a mask that other lanes mark too
 __device__ __forceinline__ void tie_mark(uint32_t* __restrict__ mask, uint64_t r0, uint32_t len)
 {
@@ -1273,14 +1272,25 @@ k_tie_direct(const uint32_t* __restrict__ tmask, uint64_t m, PackedText t, uint3
         const uint64_t q = qbase + lane;
         uint2 T = {0u, 0u};
         if (q < npairs) T = tmask2[q];
-        // the slot before this lane's 64 and the 32 behind them: the neighbouring lanes' words (the wave's ends: one more load)
-        uint32_t prev_top = (uint32_t)__shfl_up(T.y, 1) >> 31, next_w = (uint32_t)__shfl_down(T.x, 1);
-        if (lane == 0) prev_top = qbase ? tmask[qbase * 2 - 1] >> 31 : 0u;
+        // the 32 slots before this lane's 64 and the 32 behind them: the neighbouring lanes' words (the wave's ends: one more load)
+        uint32_t prev_w = (uint32_t)__shfl_up(T.y, 1), next_w = (uint32_t)__shfl_down(T.x, 1);
+        if (lane == 0) prev_w = qbase ? tmask[qbase * 2 - 1] : 0u;
         if (lane == kWave - 1) next_w = qbase + kWave <= npairs ? tmask[(qbase + kWave) * 2] : 0u;
+        const uint32_t prev_top = prev_w >> 31;
         const uint64_t lo = (uint64_t)T.x | ((uint64_t)T.y << 32);
         n_tied += (uint32_t)__popcll(lo);
         // bits [i, i + 64) of the lane's 96 (valid for the 33 bits a stretch can need)
         auto window = [&](unsigned i) -> uint64_t { return i ? (lo >> i) | ((uint64_t)next_w << (64u - i)) : lo; };
+        // A stretch longer than run_max is left where it is, and every lane marks (in lmask) and counts its own slots of it: with
+        // run_max < 32 the 32 slots on either side decide whether the stretch through a slot is long, so no lane walks a stretch
+        // (X + X ties nearly every slot: one stretch of ~m / 5).  `longm`: this lane's slots in long stretches -- the one that
+        // comes in from the slot before (its length so far: the leading tied slots of prev_w), then those that start here.
+        uint64_t longm = 0;
+        if (prev_top && (lo & 1ull)) {
+            const uint32_t in_lo = ~lo ? (uint32_t)__ffsll((unsigned long long)~lo) - 1u : 64u;
+            const uint32_t in_prev = ~prev_w ? (uint32_t)__clz((int)~prev_w) : 32u;
+            if (in_lo + in_prev > run_max) longm = in_lo == 64u ? ~0ull : (1ull << in_lo) - 1ull;
+        }
         // stretches that start here: a tied slot behind an untied one
         uint64_t slo = lo & ~((lo << 1) | (uint64_t)prev_top);
         while (__ballot(slo != 0ull) != 0ull) {
@@ -1297,10 +1307,8 @@ k_tie_direct(const uint32_t* __restrict__ tmask, uint64_t m, PackedText t, uint3
                     const uint64_t r0 = q * 64 + i;
                     n_runs++;
                     if (len > run_max) {
-                        uint64_t r = r0 + (len < 33u ? len : 33u);                // (the window holds 33 bits for sure)
-                        if (len >= 33u) { len = 33u; while (tie_bit(tmask, r)) { len++; r++; } }
-                        n_left += len;
-                        tie_mark(lmask, r0, len);
+                        // (len is exact below 96 - i, and i + len >= 64 beyond: the window is cut only past this lane's bits)
+                        longm |= (i + len >= 64u ? ~0ull : (1ull << (i + len)) - 1ull) & ~((1ull << i) - 1ull);
                     } else {
                         ent[mine++] = (uint32_t)r0 | (len << 28);              // (r0 < m <= 2^28: the hybrid route's limit)
                     }
@@ -1348,6 +1356,11 @@ k_tie_direct(const uint32_t* __restrict__ tmask, uint64_t m, PackedText t, uint3
                     if (k < len && slot_was[k] != suf[k]) slot[k] = suf[k];
             }
             wave_sync();                                                        // (the list is read to the end)
+        }
+        if (longm) {                                  // (atomics: a short stretch that stays undecided may end in these words)
+            n_left += (uint32_t)__popcll(longm);
+            if ((uint32_t)longm) atomicOr(&lmask[q * 2], (uint32_t)longm);
+            if ((uint32_t)(longm >> 32)) atomicOr(&lmask[q * 2 + 1], (uint32_t)(longm >> 32));
         }
     }
     for (int d = 32; d >= 1; d >>= 1) {
@@ -1431,12 +1444,27 @@ k_tie_list(const uint32_t* __restrict__ tmask, const uint32_t* __restrict__ hmas
         const uint32_t ex = block_scan_add_excl<uint32_t>((uint32_t)__popc(tw), part, total);
         if (phase == 1 && tw != 0u) {
             uint32_t L = (uint32_t)(running + ex), bits = tw;
+            // the head of slot r: the highest hmask bit at or below r (a run starts at its head: there is one) -- in this word, or
+            // else the last head of the words before, found once per word by a word-level scan (runs of thousands of slots)
+            const uint32_t hw = hmask[wi];
+            uint64_t head_before = ~0ull;
             while (bits != 0u) {
                 const uint32_t bit = (uint32_t)__ffs((int)bits) - 1u;
                 bits &= bits - 1u;
                 const uint64_t r = wi * 32 + bit;
-                uint64_t hr = r;
-                while (!tie_bit(hmask, hr)) hr--;                               // (a run starts at its head: there is a bit at or below)
+                const uint32_t below = hw & ((2u << bit) - 1u);                 // (bit 31: 2u << 31 wraps to 0, all bits)
+                uint64_t hr;
+                if (below != 0u) {
+                    hr = wi * 32 + 31u - (uint32_t)__clz((int)below);
+                } else {
+                    if (head_before == ~0ull) {
+                        uint64_t w = wi;
+                        uint32_t h = 0u;
+                        while (h == 0u) h = hmask[--w];
+                        head_before = w * 32 + 31u - (uint32_t)__clz((int)h);
+                    }
+                    hr = head_before;
+                }
                 V[L] = sa[r];
                 S[L] = (uint32_t)r;
                 G[L] = L - (uint32_t)(r - hr);

@@ -548,18 +548,20 @@ def suffix_tree_at_scale(eng, orc, text, device="cuda"):
     return int((ref["node"] == np.arange(len(text), dtype=np.uint32)).sum())          # internal nodes (ids = their own boundary)
 
 
-def range_slices(eng, orc, text, nranges, device="cpu", packed=False, top_bits=14):
+def range_slices(eng, orc, text, nranges, device="cpu", packed=False, top_bits=14, exp=None):
     """The range-partitioned build driven for `nranges` virtual ranks in one process: every
     range [lo, hi) of the planned key bins is built on its own and the slices must
-    concatenate to the oracle's suffix array.  Many ranges make sparse tiles in the filter
-    (direct stores), few make dense ones (LDS-compacted)."""
+    concatenate to the oracle's suffix array (`exp`, if the caller has it).  Many ranges make
+    sparse tiles in the filter (direct stores), few make dense ones (LDS-compacted).
+    Returns how many slices fell back to a whole-array build (SFX_ERR_NEEDS_RANKS)."""
     import ctypes
 
     import torch
 
     from suffix_amd import dist as sdist
     from suffix_amd.device import _p
-    exp = orc.sais(text)
+    if exp is None:
+        exp = orc.sais(text)
     n = len(text)
     t = torch.frombuffer(bytearray(text), dtype=torch.uint8).to(device)
     bb = torch.zeros(256, dtype=torch.int64, device=device)
@@ -584,6 +586,7 @@ def range_slices(eng, orc, text, nranges, device="cpu", packed=False, top_bits=1
         scratch = torch.empty(256, dtype=torch.uint8, device=device)
         eng.check(eng.lib.sfx_pack_text_dev(_p(t), n, _p(bb), _p(scratch), _p(d_packed), nw, None), "pack")
     pieces = []
+    fell_back = 0
     for lo, hi, off, cnt in sdist.plan_ranges(kb.cpu(), nranges):
         cap = max(cnt, 1)
         part = torch.empty(cap, dtype=torch.int32, device=device)
@@ -598,8 +601,10 @@ def range_slices(eng, orc, text, nranges, device="cpu", packed=False, top_bits=1
         assert off == sum(p.size for p in pieces)
         if rc == 7:          # SFX_ERR_NEEDS_RANKS: repeats too long for a slice on its own -> whole-array build (dist.py's fallback)
             pieces.append(SuffixTable(text, engine=eng).table()[off:off + cnt])
+            fell_back += 1
             continue
         eng.check(rc, "range")
         assert int(got.value) == cnt
         pieces.append(part[:cnt].cpu().numpy().view(np.uint32))
     assert np.array_equal(np.concatenate(pieces), exp)
+    return fell_back

@@ -66,6 +66,12 @@ if os.environ.get("SFX_HYBRID_MIN"):
     b13 = bytes(rngh.choice(list(b"ACGT"), 15).tolist())
     runs_of_eleven = _gen.dna(9000, seed=21).tobytes() + b"".join(b13 + bytes(rngh.choice(list(b"ACGT"), 3).tolist()) for _ in range(700))
     texts.append(runs_of_eleven)
+    # the shapes of tests/test_gpu_tie_route.py at emulator size (tests/_ties.py): planted repeats in every stretch length class,
+    # long stretches across 64- and 4096-slot windows, short ones equal beyond k_tie_direct's depth; X + X, whose few stretches of
+    # runs of two cover the array (the small-groups pass)
+    import _ties
+    tie_planted, tie_doubled = _ties.planted_dna_small().tobytes(), _ties.doubled_dna(50_003).tobytes()
+    texts += [tie_planted, tie_doubled]
     from suffix_amd import device as sdev
     for t in texts:                                     # the fused SA + LCP entry over the same initial sort (round 6: tie bits AND sorted keys)
         import torch
@@ -101,6 +107,16 @@ if os.environ.get("SFX_HYBRID_MIN"):
         assert "tie_heads" in names2 and "tie_list" in names2 and "small_groups" in names2, names2
         names2 = kernels_of(runs_of_eleven)
         assert "tie_list_count" in names2 and "tie_list" in names2 and "deep_wave" in names2, names2    # (runs of eleven: no direct pass of the list)
+        for t in (tie_planted, tie_doubled):
+            names2 = kernels_of(t)
+            st = eng.build_stats()
+            exp = oracle.sais(t)
+            w = _ties.witness(t, exp, oracle.lcp_kasai(t, exp))
+            assert "tie_direct" in names2 and "tie_heads" in names2 and "tie_list" in names2, names2
+            assert ("small_groups" in names2) or not w["small_groups_pay"], names2
+            if os.environ.get("SFX_HYBRID_KEY36", "1") == "1" and os.environ.get("SFX_HYBRID_PARTITION", "1") != "0":
+                # (the witness's key: one symbol more than the 32-bit key, SrcText36) every tie bit of the LDS sort
+                assert st["active_after_initial"] == w["tied"], (st["active_after_initial"], w["tied"])
     names = kernels_of(planted)                                       # 0.8 % of it in the three planted sub-buckets
     assert ("bucket_sort_lds" in names) == (cap > 10) and ("oversize_gather" in names) == (10 < cap < 400), names
     assert ("tie_direct" in names) == (cap >= 400 and ties_on), names   # (an oversized sub-bucket: the sorted keys, as before)
