@@ -2,7 +2,7 @@
 # A/B runs through the development library (hooks compiled in: `make -C suffix_amd/csrc dev`): one run per (text kind, variant).
 #   gpu_ab.sh OUTNAME "kind1 kind2" "VAR=a,VAR2=b" "-" ...         full-size builds (scripts/gpu_time_build.py; "-" = no hook set)
 #   AB_SCRIPT=scripts/gpu_lcp_prof.py gpu_ab.sh ...                 another per-kind script
-#   AB_BENCH=50 gpu_ab.sh OUTNAME - "SFX_PARTITION_WAVES=8" ...     the headline bench at 50 steps instead (kinds ignored)
+#   AB_BENCH=50 gpu_ab.sh OUTNAME - "SFX_HYBRID_TIES=0" ...        the headline bench at 50 steps instead (kinds ignored)
 # -> gpurun_out/OUTNAME/ab.jsonl (+ ab.err)
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/$1; mkdir -p $OUT; shift

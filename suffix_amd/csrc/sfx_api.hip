@@ -481,11 +481,10 @@ int sfx_index_query_dev(const sfx_index* ix, const uint8_t* d_qbytes, const uint
         return query_batch_dev(ix->d_text, ix->n, ix->d_sa, ix->n, d_qbytes, d_qoff, nq, d_start, d_end, d_found, d_any,
                                (hipStream_t)stream);
     if (ix->d_tree) {
-        // SFX_QUERY_ORDER=1 (development): answer large batches in the order of their first 8 bytes, so that
-        // neighbouring lanes share tree nodes and probes.  Measured on config 5's 10^6 queries: the search kernel
-        // 1.39 -> 1.23 ms, the 8-pass sort of the (key, query) pairs 0.24 ms -- not worth it, off by default
-        static const bool want_order = [] { const char* e = dev_env("SFX_QUERY_ORDER"); return e && atoi(e) != 0; }();
-        // scratch of phase 2 (the list of queries that go on; the ordering), kept across calls per (thread, device): no
+        // (Answering large batches in the order of their first 8 bytes, so that neighbouring lanes share tree nodes and probes,
+        // was measured on config 5's 10^6 queries: the search kernel 1.39 -> 1.23 ms, the 8-pass sort of the (key, query) pairs
+        // 0.24 ms -- not worth it.)
+        // scratch of phase 2 (the list of queries that go on), kept across calls per (thread, device): no
         // allocation and no host synchronisation on the hot path.  The previous batch may still be using it on another
         // stream (whose handle may be gone by now): it left an EVENT behind, and this batch's stream waits on that -- on
         // the device.  Without scratch the batch is answered in one phase.
@@ -496,7 +495,7 @@ int sfx_index_query_dev(const sfx_index* ix, const uint8_t* d_qbytes, const uint
         QueryScratch& sc = dev >= 0 ? scs[dev] : none;
         void* os = nullptr;
         if (dev >= 0 && nq >= query_two_phase_min()) {
-            const uint64_t need = query_scratch_bytes(nq, want_order);
+            const uint64_t need = query_scratch_bytes(nq);
             if (!sc.done && hipEventCreateWithFlags(&sc.done, hipEventDisableTiming) != hipSuccess) { sc.done = nullptr; (void)hipGetLastError(); }
             if (sc.done) {
                 if (sc.bytes < need) {
@@ -510,7 +509,7 @@ int sfx_index_query_dev(const sfx_index* ix, const uint8_t* d_qbytes, const uint
             }
         }
         const int qrc = query_batch_tree_dev(ix->d_text, ix->n, ix->d_sa, ix->d_tree, ix->tree_off, ix->tree_levels, d_qbytes, d_qoff, nq,
-                                             d_start, d_end, d_found, d_any, (hipStream_t)stream, os, want_order, ix->d_dir, ix->d_lut,
+                                             d_start, d_end, d_found, d_any, (hipStream_t)stream, os, ix->d_dir, ix->d_lut,
                                              ix->bits, ix->k, ix->dbits);
         if (os) { (void)hipEventRecord(sc.done, (hipStream_t)stream); sc.used = true; }
         return qrc;

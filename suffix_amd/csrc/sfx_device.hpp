@@ -136,36 +136,26 @@ __device__ __forceinline__ unsigned lanes_below(unsigned long long peers)
 
 // rank of this lane's key among the keys with the same digit that its wave has seen so
 // far in this tile (earlier rounds, then lower lanes of this round)
-template <bool RANK_ATOMIC>
+// (match masks in LDS: every lane ORs its bit into the mask of its digit.  Eight ballots per round were the alternative;
+// measured slower, profiles/r1c_radix_variants.txt)
 __device__ __forceinline__ uint32_t rank_round(unsigned d, unsigned long long* flags_w, uint32_t* cnt_w,
                                                unsigned long long mybit)
 {
-    unsigned long long peers;
-    if (RANK_ATOMIC) {
-        atomicOr(&flags_w[d], mybit);
-        wave_sync();
-        peers = flags_w[d];
-    } else {
-        peers = ~0ull;
-#pragma unroll
-        for (int b = 0; b < kRadixBitsDev; b++) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long vote = __ballot(bit);
-            peers &= bit ? vote : ~vote;
-        }
-    }
+    atomicOr(&flags_w[d], mybit);
+    wave_sync();
+    const unsigned long long peers = flags_w[d];
     const uint32_t pre = cnt_w[d];
     wave_sync();
     const unsigned below = lanes_below(peers);
     if (below == 0) {
-        if (RANK_ATOMIC) flags_w[d] = 0ull;
+        flags_w[d] = 0ull;
         cnt_w[d] = pre + (uint32_t)__popcll(peers);
     }
     wave_sync();
     return pre + below;
 }
 
-// rank_round<true> with 16-bit counts (tiles of < 65536 elements: k_radix_sweep, k_tiny_sa)
+// rank_round with 16-bit counts (tiles of < 65536 elements: k_radix_sweep, k_tiny_sa)
 __device__ __forceinline__ uint32_t rank_round16(unsigned d, unsigned long long* flags_w, uint16_t* cnt_w, unsigned long long mybit)
 {
     atomicOr(&flags_w[d], mybit);

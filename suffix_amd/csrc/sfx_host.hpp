@@ -57,7 +57,8 @@ struct ArenaSizer {
 };
 
 // ---- development hooks -----------------------------------------------------------
-// The SFX_* environment knobs (small tiles for the emulator, A/B switches for lab runs) exist only in builds
+// The SFX_* environment knobs (small tiles, capped grids and moved thresholds, so that inputs of emulator size reach the routes
+// the product takes for larger ones) exist only in builds
 // made with -DSFX_DEV_HOOKS: the kernel-logic emulator (tests/emu) and libsuffix_hip_dev.so (`make dev`).
 // The shipped libsuffix_hip.so reads no environment variable: its routes depend on (alphabet, n) alone.
 #ifdef SFX_DEV_HOOKS
@@ -65,6 +66,12 @@ inline const char* dev_env(const char* name) { return getenv(name); }
 #else
 inline const char* dev_env(const char*) { return nullptr; }
 #endif
+// SFX_TRACE=1: the builds' route decisions on stderr (a diagnostic, selects nothing)
+inline bool dev_trace()
+{
+    static const bool v = [] { const char* e = dev_env("SFX_TRACE"); return e && atoi(e) != 0; }();
+    return v;
+}
 
 // ---- launch geometry -----------------------------------------------------------
 // Streaming kernels use a fixed-size grid of persistent workgroups, each owning a
@@ -397,8 +404,8 @@ int key_tree_build_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, 
 int query_batch_tree_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint64_t* d_tree,
                          const uint64_t* level_offsets, int levels, const uint8_t* d_q, const uint64_t* d_qoff, uint64_t nq,
                          uint32_t* d_start, uint32_t* d_end, uint8_t* d_found, uint32_t* d_any, hipStream_t st,
-                         void* scratch, bool ordered, const uint32_t* d_dir, const uint16_t* d_lut256, int bits, int k, int dbits);
-uint64_t query_scratch_bytes(uint64_t nq, bool ordered);
+                         void* scratch, const uint32_t* d_dir, const uint16_t* d_lut256, int bits, int k, int dbits);
+uint64_t query_scratch_bytes(uint64_t nq);
 uint64_t query_two_phase_min();
 int byte_presence_host(const uint8_t* d_text, uint64_t n, void* d_small4k, unsigned long long* host_bins256,
                        hipStream_t st);

@@ -653,6 +653,7 @@ k_query_batch_tree(const uint8_t* __restrict__ text, uint64_t n, const uint32_t*
 {
     // `order` (optional): the queries sorted by their first 8 bytes -- neighbouring lanes then walk the same
     // tree nodes and, inside a range of suffixes sharing those bytes, probe the same SA entries and text lines
+    // (measured, not worth its sort: sfx_index_query_dev; the host passes none)
     __shared__ CoopSmem coop;
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     const unsigned lane = lane_id();
@@ -756,22 +757,6 @@ k_query_tree_long(const uint8_t* __restrict__ text, uint64_t n, const uint32_t* 
     }
 }
 
-// (first 8 bytes of query k, big-endian, zero-padded) for the ordering above
-__global__ void __launch_bounds__(kBlock)
-k_query_keys(const uint8_t* __restrict__ qbytes, const uint64_t* __restrict__ qoff, uint64_t nq, uint64_t* __restrict__ keys,
-             uint32_t* __restrict__ idx)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < nq; k += stride) {
-        const uint8_t* q = qbytes + qoff[k];
-        const uint64_t m = qoff[k + 1] - qoff[k];
-        uint64_t key = 0;
-        for (unsigned j = 0; j < 8; j++) key = (key << 8) | (j < m ? (uint64_t)q[j] : 0ull);
-        keys[k] = key;
-        idx[k] = (uint32_t)k;
-    }
-}
-
 // words (u64) of one allocation that holds all levels, each padded to whole nodes plus one spare node
 uint64_t key_tree_words(uint64_t n)
 {
@@ -806,8 +791,7 @@ int key_tree_build_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, 
     *levels_out = l + 1;
     return SFX_OK;
 }
-// scratch of a batch: the list of phase 2 (a counter, then nq entries); with `ordered`, behind it the query
-// ordering: 2 * nq u64 + 2 * nq u32 + radix_scratch_words(nq) u32
+// scratch of a batch: the list of phase 2 (a counter, then nq entries)
 // smaller batches are finished in place (one launch); SFX_QUERY_PHASE_MIN (tests) moves the threshold
 uint64_t query_two_phase_min()
 {
@@ -817,17 +801,11 @@ uint64_t query_two_phase_min()
     }();
     return v;
 }
-static uint64_t query_work_bytes(uint64_t nq) { return (256 + nq * sizeof(LongQuery) + 255) & ~uint64_t(255); }
-uint64_t query_scratch_bytes(uint64_t nq, bool ordered)
-{
-    uint64_t b = query_work_bytes(nq);
-    if (ordered) b += 2 * nq * sizeof(uint64_t) + 2 * nq * sizeof(uint32_t) + radix_scratch_words(nq) * sizeof(uint32_t) + 1024;
-    return b;
-}
+uint64_t query_scratch_bytes(uint64_t nq) { return (256 + nq * sizeof(LongQuery) + 255) & ~uint64_t(255); }
 int query_batch_tree_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint64_t* d_tree,
                          const uint64_t* level_offsets, int levels, const uint8_t* d_q, const uint64_t* d_qoff, uint64_t nq,
                          uint32_t* d_start, uint32_t* d_end, uint8_t* d_found, uint32_t* d_any, hipStream_t st, void* scratch,
-                         bool ordered, const uint32_t* d_dir, const uint16_t* d_lut256, int bits, int k, int dbits)
+                         const uint32_t* d_dir, const uint16_t* d_lut256, int bits, int k, int dbits)
 {
     if (nq == 0) return SFX_OK;
     if (!d_qoff || !d_tree || levels < 1 || levels > kTreeMaxLevels) return SFX_ERR_ARG;
@@ -844,29 +822,14 @@ int query_batch_tree_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa
     // the directory narrows the descents when its key lies inside the tree's 16 bytes (always, except for 1-bit symbols)
     static const bool want_dir = [] { const char* e = dev_env("SFX_TREE_DIR"); return !e || atoi(e) != 0; }();
     DirParams dp = {want_dir && d_lut256 && k <= (int)kTreeKeyBytes ? d_dir : nullptr, d_lut256, bits, k, dbits};
-    const uint32_t* order = nullptr;
     const bool two_phase = scratch && nq >= query_two_phase_min() && nq <= 0xFFFFFFFFull;
     uint32_t* work_count = two_phase ? reinterpret_cast<uint32_t*>(scratch) : nullptr;
     LongQuery* work = two_phase ? reinterpret_cast<LongQuery*>(reinterpret_cast<char*>(scratch) + 256) : nullptr;
     if (two_phase) SFX_HIP(hipMemsetAsync(work_count, 0, sizeof(uint32_t), st));
-    if (two_phase && ordered) {
-        // sort (first 8 bytes, query number): 8 passes over 12-byte elements of a small array
-        char* w = reinterpret_cast<char*>(scratch) + query_work_bytes(nq);
-        uint64_t* k0 = reinterpret_cast<uint64_t*>(w);
-        uint64_t* k1 = k0 + nq;
-        uint32_t* v0 = reinterpret_cast<uint32_t*>(k1 + nq);
-        uint32_t* v1 = v0 + nq;
-        uint32_t* scr = v1 + nq;
-        scr = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(scr) + 255) & ~uintptr_t(255));
-        SFX_LAUNCH("query_keys", (double)nq * 28, k_query_keys, grid, kBlock, st, d_q, d_qoff, nq, k0, v0);
-        int in1 = 0;
-        SFX_TRY(radix_sort_kv64(k0, v0, k1, v1, nq, 0, 64, scr, st, &in1, nullptr, nullptr));
-        order = in1 ? v1 : v0;
-    }
     // two descents of one 128-byte line per level (a second one at the bottom levels of queries longer than 8
     // bytes), a few probes of 2 lines beyond 16 bytes
     SFX_LAUNCH("query_batch_tree", (double)nq * (2.0 * (levels + 3) * 128 + 2 * 256), k_query_batch_tree, grid, kBlock, st, d_text, n,
-               d_sa, t, d_q, d_qoff, nq, d_start, d_end, d_found, d_any, order, work, work_count, dp);
+               d_sa, t, d_q, d_qoff, nq, d_start, d_end, d_found, d_any, (const uint32_t*)nullptr, work, work_count, dp);
     if (two_phase)
         SFX_LAUNCH("query_tree_long", (double)nq * 0.4 * 40 * 256, k_query_tree_long, grid, kBlock, st, d_text, n, d_sa, d_q,
                    d_qoff, (const LongQuery*)work, (const uint32_t*)work_count, d_start, d_end, d_found, d_any);

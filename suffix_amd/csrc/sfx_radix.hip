@@ -34,8 +34,8 @@
 //           match mask in LDS (ds_or_b64 of the lane bit, read back, lowest lane
 //           of each digit clears the mask and advances the wave's digit count) --
 //           ~10 VALU + 5 LDS instructions per key instead of the ~50 VALU of an
-//           8-ballot match (the ballot form is kept as a variant);
-//   scan    thread d sums digit d over the 4 waves, block scan -> tile-local
+//           8-ballot match;
+//   scan    thread d sums digit d over the waves, block scan -> tile-local
 //           bucket starts; bucket heads from look-back (one-sweep) or from the
 //           running cursor kept in thread d's register (chunked);
 //   reorder elements go to their tile-local slot in LDS, are read back in slot
@@ -368,7 +368,7 @@ k_radix_scan(uint32_t* __restrict__ hist, unsigned nblocks, uint32_t* __restrict
 // ---- tile engine ---------------------------------------------------------------------
 // The match masks of the ranking (NW x 256 u64) live in the first 2 KiB x NW of `stage`:
 // ranking is over before anything is staged, and every wave clears its own row before it ranks.
-template <int KPT, bool HAS_VAL, int NW, bool RANK_ATOMIC>
+template <int KPT, bool HAS_VAL, int NW>
 struct RadixSmem {
     uint32_t cnt[NW][kRadix];                           // per-wave digit counts, then tile-local bases
     uint32_t off[kRadix];                               // global bucket head minus tile-local bucket start
@@ -436,8 +436,7 @@ __device__ __forceinline__ uint32_t lookback_finish(uint32_t* status, uint32_t t
     }
 }
 
-// NW = waves per workgroup (4 or 8): thread d < 256 owns bucket d; a 512-thread workgroup
-// sorts 8192-element tiles, i.e. 256-byte runs per bucket.
+// NW = waves per workgroup (16; 4 for the small segment tiles of the tests): thread d < 256 owns bucket d.
 #ifndef SFX_RADIX_MIN_WAVES
 #define SFX_RADIX_MIN_WAVES 1
 #endif
@@ -461,7 +460,7 @@ struct SegArgs {
     int pass, npass;
 };
 
-template <class Src, class Dst, int KPT, bool ONESWEEP, bool RANK_ATOMIC, int NW, bool SEG = false>
+template <class Src, class Dst, int KPT, bool ONESWEEP, int NW, bool SEG = false>
 __global__ void __launch_bounds__(NW * kWave, SFX_RADIX_MIN_WAVES)
 k_radix_pass(Src src, Dst dst, uint64_t m, int shift, unsigned mask, uint64_t chunk,
              const uint32_t* __restrict__ hist, const uint32_t* __restrict__ digit_total,
@@ -470,7 +469,7 @@ k_radix_pass(Src src, Dst dst, uint64_t m, int shift, unsigned mask, uint64_t ch
     constexpr bool HAS_VAL = Src::kHasVal;
     constexpr int kThreads = NW * kWave;
     constexpr int kTile = kThreads * KPT;
-    __shared__ RadixSmem<KPT, HAS_VAL, NW, RANK_ATOMIC> s;
+    __shared__ RadixSmem<KPT, HAS_VAL, NW> s;
     const unsigned tid = threadIdx.x, lane = lane_id(), w = wave_id();
     const unsigned long long mybit = 1ull << lane;
     const bool owner = tid < (unsigned)kRadix;                   // thread d owns bucket d
@@ -554,7 +553,7 @@ k_radix_pass(Src src, Dst dst, uint64_t m, int shift, unsigned mask, uint64_t ch
             if (HAS_VAL) val[r] = nval[r];
         }
         if (!ONESWEEP && next < limit) load_tile(next);
-        if (RANK_ATOMIC) {                                  // this wave's match masks (aliased onto the stage)
+        {                                                   // this wave's match masks (aliased onto the stage)
 #pragma unroll
             for (int k = 0; k < kRadix / kWave; k++) my_flags[k * kWave + lane] = 0ull;
             wave_sync();
@@ -565,7 +564,7 @@ k_radix_pass(Src src, Dst dst, uint64_t m, int shift, unsigned mask, uint64_t ch
 #pragma unroll
         for (int r = 0; r < KPT; r++) {
             if (!SEG || w * (kWave * KPT) + r * kWave < nvalid)
-                pos[r] = rank_round<RANK_ATOMIC>(digit_of(key[r], shift, mask), my_flags, s.cnt[w], mybit);
+                pos[r] = rank_round(digit_of(key[r], shift, mask), my_flags, s.cnt[w], mybit);
             else
                 pos[r] = 0;
         }
@@ -787,7 +786,6 @@ k_radix_sweep(Src src, Dst dst, uint64_t m, int shift, unsigned mask, const uint
 // 50.0.  The whole 12288-element tile (24 per thread) needs 236 bytes of scratch under the 128 registers that two workgroups
 // per CU leave a thread, 10- and 12-wave workgroups spill at 14 per thread: 14 x 8 is the geometry.
 constexpr int kDuoKPT = 14, kDuoNW = 8;
-constexpr int kDuoKPTE64 = 16;                                     // 8-byte elements: 8192-element tiles (18 and 20 per thread spill)
 template <int KPT, int NW, bool HAS_VAL>
 struct DuoSmem {
     static constexpr int kHalf = NW * kWave * KPT / 2;
@@ -941,9 +939,6 @@ k_radix_sweep_duo(Src src, Dst dst, uint64_t m, int shift, unsigned mask, const 
 // pass is tile (v - first tile of b) of bucket b, found by bisecting the running tile counts.
 constexpr unsigned kCursorPad = 16;                                  // words between two cursors of the first pass
 constexpr unsigned kPartClasses = 8;                                 // stretches of the input of the first pass = XCDs
-#ifndef SFX_PART_ABL
-#define SFX_PART_ABL 0                                               // lab/partition_lab.hip: 1 no LDS atomics, 2 no global atomics, 4 no stores, 8 no loads
-#endif
 template <int KPT, int NW>
 struct PartSmem {
     uint64_t stage[NW * kWave * KPT];                                // (the match masks of the ranking alias its first NW x 2 KiB)
@@ -961,7 +956,7 @@ struct PartSmem {
 // (Ranking: the match masks of the one-sweep pass.  One returning LDS atomic per element was the first version -- the LDS
 // retires about one of them per clock and CU: 8.4 us per 16384-element tile against 4.6 for the masks, lab/partition_lab.hip.)
 template <class Src, int KPT, int NW, bool SUB>
-__global__ void __launch_bounds__(NW * kWave) SFX_WAVES_PER_EU(4, 4)      // (16 waves per CU: one workgroup of 16 or two of 8)
+__global__ void __launch_bounds__(NW * kWave) SFX_WAVES_PER_EU(4, 4)      // (16 waves per CU: one workgroup of 16, two of 8 or four of 4)
 k_partition(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t* __restrict__ cursor,
             const uint32_t* __restrict__ bstart16, uint64_t class_len)
 {
@@ -1058,7 +1053,7 @@ k_partition(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t
         for (int k = 0; k < kRadix / kWave; k++) my_flags[k * kWave + lane] = 0ull;
         wave_sync();
 #pragma unroll
-        for (int r = 0; r < KPT; r++) pos[r] = (SFX_PART_ABL & 1) ? 0u : rank_round16(digit_of(key[r], shift, 255u), my_flags, s.cnt[w], mybit);
+        for (int r = 0; r < KPT; r++) pos[r] = rank_round16(digit_of(key[r], shift, 255u), my_flags, s.cnt[w], mybit);
         __syncthreads();
         uint32_t real_count = 0, tile_ex = 0, mine = 0;
         {
@@ -1079,8 +1074,7 @@ k_partition(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t
                 real_count = tile_count - ((tid == 255u) ? (uint32_t)(kTile - nvalid) : 0u);
                 tile_ex = ex;
                 // (the reservation is in flight while the tile is staged)
-                if (SFX_PART_ABL & 2) mine = (uint32_t)begin + ex;
-                else if (real_count) mine = atomicAdd(&cursor[SUB ? ((top << 8) | tid) : (top * kRadix + tid) * kCursorPad], real_count);
+                if (real_count) mine = atomicAdd(&cursor[SUB ? ((top << 8) | tid) : (top * kRadix + tid) * kCursorPad], real_count);
             }
         }
         __syncthreads();
@@ -1101,7 +1095,7 @@ k_partition(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t
             for (int r = r0; r < r0 + kOut; r++) pos[r] = s.off[digit_of(key[r], shift, 255u)] + ((unsigned)r * kThreads + t);
 #pragma unroll
             for (int r = r0; r < r0 + kOut; r++)
-                if (!(SFX_PART_ABL & 4) && (unsigned)r * kThreads + t < nvalid) out[(SFX_PART_ABL ? pos[r] % m : pos[r])] = key[r];
+                if ((unsigned)r * kThreads + t < nvalid) out[pos[r]] = key[r];
         }
         if (owner) {
 #pragma unroll
@@ -1554,7 +1548,7 @@ k_bucket_sort(const uint64_t* __restrict__ X, const uint32_t* __restrict__ bstar
             wave_sync();
 #pragma unroll
             for (int r = 0; r < KPT; r++)
-                if ((unsigned)r < kpt) pos[r] = rank_round<true>(digit_of(key[r], shift, mask), my_flags, s.cnt[w], mybit);
+                if ((unsigned)r < kpt) pos[r] = rank_round(digit_of(key[r], shift, mask), my_flags, s.cnt[w], mybit);
             __syncthreads();
             {
                 uint32_t c[NW], tile_count = 0;
@@ -1621,30 +1615,18 @@ k_bucket_sort(const uint64_t* __restrict__ X, const uint32_t* __restrict__ bstar
 }
 
 // ---- host side -------------------------------------------------------------------------
-// Tuning knobs (development only; read once per process):
-//   SFX_RADIX_SWEEP  1 = one-sweep (default), 0 = chunked
-//   SFX_RADIX_KPT    elements per thread of the E64 passes: 11 (default), 16 or 8
-//   SFX_RADIX_KPT_TEXT  ... of the text-fed pass: 16 (default), 11 or 8
-//   SFX_RADIX_RANK   1 = LDS match masks (default), 0 = 8-ballot match
-//   SFX_RADIX_NW     waves per workgroup: 4, 8 or 16 (default); tile = 64 * NW * KPT elements
-struct RadixTuning { int sweep, kpt, rank, nw, kpt_text, kpt_kv, kv12, duo, duo_e64; };
-static RadixTuning radix_tuning()
+// Two hooks of the tests (read once per process) force what the engine otherwise chooses from the input:
+//   SFX_RADIX_SWEEP=0  the chunked schedule (the product's from 2^30 elements or more than kMaxPasses passes up)
+//   SFX_RADIX_KV12=0   (key array, value array) in every pass of a 64-bit-key sort (what a caller without adjacent arrays gets)
+static bool radix_sweep_allowed()
 {
-    static const RadixTuning t = [] {
-        RadixTuning r = {1, 16, 1, 16, 16, 12, 1, 1, 0}; // measured best on MI355X (round 4, lab/radix_lab2.hip): 1024-thread
-                                                // workgroups, 16384-element E64 tiles (512-byte runs), 12288-element KV tiles
-        if (const char* e = dev_env("SFX_RADIX_SWEEP")) r.sweep = atoi(e) ? 1 : 0;
-        if (const char* e = dev_env("SFX_RADIX_KPT")) r.kpt = (atoi(e) >= 8 && atoi(e) <= 16) ? atoi(e) : 8;
-        if (const char* e = dev_env("SFX_RADIX_RANK")) r.rank = atoi(e) ? 1 : 0;
-        if (const char* e = dev_env("SFX_RADIX_KPT_TEXT")) r.kpt_text = (atoi(e) >= 8 && atoi(e) <= 16) ? atoi(e) : 16;
-        if (const char* e = dev_env("SFX_RADIX_KPT_KV")) r.kpt_kv = (atoi(e) >= 8 && atoi(e) <= 12) ? atoi(e) : 8;
-        if (const char* e = dev_env("SFX_RADIX_KV12")) r.kv12 = atoi(e) ? 1 : 0;         // 0: (key array, value array) in every pass
-        if (const char* e = dev_env("SFX_RADIX_DUO_E64")) r.duo_e64 = atoi(e) ? 1 : 0;   // 1: the E64 -> E64 one-sweep passes by k_radix_sweep_duo (development)
-        if (const char* e = dev_env("SFX_RADIX_DUO")) r.duo = atoi(e) ? 1 : 0;           // 0: the KV passes by k_radix_sweep (one workgroup per CU)
-        if (const char* e = dev_env("SFX_RADIX_NW")) r.nw = atoi(e) == 16 ? 16 : (atoi(e) == 8 ? 8 : 4);
-        return r;
-    }();
-    return t;
+    static const bool v = [] { const char* e = dev_env("SFX_RADIX_SWEEP"); return !e || atoi(e) != 0; }();
+    return v;
+}
+static bool radix_kv12_allowed()
+{
+    static const bool v = [] { const char* e = dev_env("SFX_RADIX_KV12"); return !e || atoi(e) != 0; }();
+    return v;
 }
 
 uint64_t radix_scratch_words(uint64_t m)
@@ -1668,111 +1650,61 @@ struct RadixScratch {
     }
 };
 
-template <class Src, class Dst, int KPT, bool ONESWEEP, bool RANK_ATOMIC, int NW>
-static int launch_pass(const char* name, double algo_bytes, const Src& src, const Dst& dst, uint64_t m, int shift,
-                       unsigned mask, const RadixScratch& scr, int pass, hipStream_t st)
+// One pass of a device-wide sort.  Workgroups of 16 waves (1024 threads; 4 and 8 were measured, profiles/r1c_radix_variants.txt);
+// what varies is the number of elements per thread and, for the one-sweep schedule, the kernel:
+//   sources without values (E64 elements, text-fed 32-bit keys): one-sweep 16 per thread (16384-element tiles, 512-byte runs:
+//     round 4, lab/radix_lab2.hip), chunked 11 -- the chunked schedule keeps the next tile's elements in registers as well and 16
+//     per thread spill there (2 * 10^9 bytes of DNA 107.9 ms at 16, 84.1 at 11, 88.7 at 8);
+//   key/value sources not fed from text (12-byte elements): one-sweep by k_radix_sweep_duo -- 7168-element tiles held by 512
+//     threads, two workgroups per CU -- except the first pass of a compressed-key sort, which reads 8 bytes per element where
+//     the others read 12 (5.31 ms with k_radix_sweep at 12 per thread, 5.57 with the duo kernel).  12 per thread is what the LDS
+//     holds; 10 was the largest tile without spills in k_radix_sweep until its output loop stopped leaving sixteen hoisted LDS
+//     addresses in scratch (SFX_OPAQUE_VGPR): config 3's eight passes 53.8 / 52.2 / 51.9 ms at 10 / 11 / 12.  Chunked (m >= 2^30):
+//     8 per thread -- the prefetched tile's registers again; 1.5 * 10^9 bytes of English-like text 204.7 / 186.4 / 185.9 ms at
+//     10 / 9 / 8;
+//   text-fed 64-bit keys (SrcText64): 8 per thread in both schedules.
+// (8-byte elements through the duo kernel were measured too, profiles/r5_duo_e64_ab.jsonl: the rank-update partition passes of
+// the near-duplicate documents 70.8 -> 67.0 ms, but the E64 passes of 1 GB of DNA 12.6 -> 13.2 and those of config 5 23.2 ->
+// 25.2 -- 8 bytes per element leave a 8192-element tile 256-byte runs, and that costs what the overlap gives.  Not built.)
+constexpr int kPassNW = 16;
+template <class Src>
+constexpr bool kDuoSrc = Src::kHasVal && !Src::kFromText && !std::is_same<Src, SrcKeyIota>::value;
+template <class Src>
+constexpr int kSweepKPT = !Src::kHasVal ? 16 : (Src::kFromText ? 8 : 12);   // (k_radix_sweep; the duo kernel: kDuoKPT)
+template <class Src>
+constexpr int kChunkedKPT = !Src::kHasVal ? 11 : 8;
+
+template <class Src, class Dst>
+static int run_pass(const char* name, double algo_bytes, const Src& src, const Dst& dst, uint64_t m, int shift,
+                    unsigned mask, const RadixScratch& scr, int pass, bool sweep, hipStream_t st)
 {
-    constexpr int kThreads = NW * kWave;
-    constexpr int kTile = kThreads * KPT;
-    if constexpr (ONESWEEP) {
-        const uint64_t tiles = (m + kTile - 1) / kTile;
-        const unsigned grid = (unsigned)dmin<uint64_t>(tiles, kMaxGrid);
-        // (the status words are zeroed once, for the tile count of the kernel that runs: the two-workgroup kernels have smaller tiles)
-        auto zero_status = [&](uint64_t t) { return hipMemsetAsync(scr.status, 0, t * kRadix * sizeof(uint32_t), st); };
-        if constexpr (RANK_ATOMIC && NW == 16 && KPT == 12 && Src::kHasVal && !Src::kFromText && !std::is_same<Src, SrcKeyIota>::value) {
-            // (7168-element tiles held by 512 threads, two workgroups per CU: k_radix_sweep_duo.  Not the first pass of a compressed-key
-            // sort, which reads 8 bytes per element where the others read 12: 5.31 ms with k_radix_sweep, 5.57 with this)
-            if (radix_tuning().duo) {
-                const uint64_t dtile = (uint64_t)kDuoKPT * kDuoNW * kWave;
-                const uint64_t dtiles = (m + dtile - 1) / dtile;
-                const unsigned dgrid = (unsigned)dmin<uint64_t>(dtiles, kMaxGrid);
-                SFX_HIP(zero_status(dtiles));
-                SFX_LAUNCH(name, algo_bytes, (k_radix_sweep_duo<Src, Dst, kDuoKPT, kDuoNW>), dgrid, kDuoNW * kWave, st, src, dst, m, shift,
-                           mask, (const uint32_t*)(scr.totals + pass * kRadix), scr.status, scr.tickets + pass);
-                return SFX_OK;
-            }
-        }
-        if constexpr (RANK_ATOMIC && NW == 16 && KPT == 16 && std::is_same<Src, SrcE64>::value && std::is_same<Dst, DstE64>::value) {
-            // (8-byte elements in, 8-byte elements out: 8192-element tiles held by 512 threads, two workgroups per CU -- development
-            // only, SFX_RADIX_DUO_E64=1.  Measured on 10^9 bytes each (profiles/r5_duo_e64_ab.jsonl): the rank-update partition passes
-            // of the near-duplicate documents 70.8 -> 67.0 ms, but the E64 passes of 1 GB of DNA 12.6 -> 13.2 and those of config 5
-            // 23.2 -> 25.2: 8 bytes per element leave a 8192-element tile 256-byte runs, and that costs what the overlap gives)
-            if (radix_tuning().duo_e64) {
-                const uint64_t dtile = (uint64_t)kDuoKPTE64 * kDuoNW * kWave;
-                const uint64_t dtiles = (m + dtile - 1) / dtile;
-                const unsigned dgrid = (unsigned)dmin<uint64_t>(dtiles, kMaxGrid);
-                SFX_HIP(zero_status(dtiles));
-                SFX_LAUNCH(name, algo_bytes, (k_radix_sweep_duo<Src, Dst, kDuoKPTE64, kDuoNW>), dgrid, kDuoNW * kWave, st, src, dst, m,
-                           shift, mask, (const uint32_t*)(scr.totals + pass * kRadix), scr.status, scr.tickets + pass);
-                return SFX_OK;
-            }
-        }
-        SFX_HIP(zero_status(tiles));
-        if constexpr (RANK_ATOMIC && NW == 16 && kTile < 65536) {
-            SFX_LAUNCH(name, algo_bytes, (k_radix_sweep<Src, Dst, KPT, NW>), grid, kThreads, st, src, dst, m, shift, mask,
-                       (const uint32_t*)(scr.totals + pass * kRadix), scr.status, scr.tickets + pass);
-        } else {
-            SFX_LAUNCH(name, algo_bytes, (k_radix_pass<Src, Dst, KPT, true, RANK_ATOMIC, NW>), grid, kThreads, st, src, dst, m,
-                       shift, mask, (uint64_t)0, (const uint32_t*)nullptr, (const uint32_t*)(scr.totals + pass * kRadix),
-                       scr.status, scr.tickets + pass);
-        }
-    } else {
+    if (!sweep) {
+        constexpr int kThreads = kPassNW * kWave, kTile = kThreads * kChunkedKPT<Src>;
         Chunking ch = make_chunking(m, kTile);
         const uint64_t chunk = ch.tiles_per_block * kTile;
         SFX_LAUNCH("radix_hist", (double)m * 8.0, (k_radix_hist_chunk<Src>), ch.blocks, kBlock, st, src, m, shift,
                    mask, chunk, scr.partial);
         SFX_LAUNCH("radix_scan", (double)kRadix * ch.blocks * 8, k_radix_scan, kRadix, kBlock, st, scr.partial,
                    ch.blocks, scr.totals);
-        SFX_LAUNCH(name, algo_bytes, (k_radix_pass<Src, Dst, KPT, false, RANK_ATOMIC, NW>), ch.blocks, kThreads, st, src,
+        SFX_LAUNCH(name, algo_bytes, (k_radix_pass<Src, Dst, kChunkedKPT<Src>, false, kPassNW>), ch.blocks, kThreads, st, src,
                    dst, m, shift, mask, chunk, (const uint32_t*)scr.partial, (const uint32_t*)scr.totals,
                    (uint32_t*)nullptr, (uint32_t*)nullptr);
+        return SFX_OK;
+    }
+    // (the status words are zeroed once, for the tile count of the kernel that runs: the two-workgroup kernel has smaller tiles)
+    constexpr int kThreads = kDuoSrc<Src> ? kDuoNW * kWave : kPassNW * kWave;
+    constexpr int kTile = kThreads * (kDuoSrc<Src> ? kDuoKPT : kSweepKPT<Src>);
+    const uint64_t tiles = (m + kTile - 1) / kTile;
+    const unsigned grid = (unsigned)dmin<uint64_t>(tiles, kMaxGrid);
+    SFX_HIP(hipMemsetAsync(scr.status, 0, tiles * kRadix * sizeof(uint32_t), st));
+    if constexpr (kDuoSrc<Src>) {
+        SFX_LAUNCH(name, algo_bytes, (k_radix_sweep_duo<Src, Dst, kDuoKPT, kDuoNW>), grid, kThreads, st, src, dst, m, shift,
+                   mask, (const uint32_t*)(scr.totals + pass * kRadix), scr.status, scr.tickets + pass);
+    } else {
+        SFX_LAUNCH(name, algo_bytes, (k_radix_sweep<Src, Dst, kSweepKPT<Src>, kPassNW>), grid, kThreads, st, src, dst, m, shift, mask,
+                   (const uint32_t*)(scr.totals + pass * kRadix), scr.status, scr.tickets + pass);
     }
     return SFX_OK;
-}
-
-template <class Src, class Dst>
-static int run_pass(const char* name, double algo_bytes, const Src& src, const Dst& dst, uint64_t m, int shift,
-                    unsigned mask, const RadixScratch& scr, int pass, bool sweep, hipStream_t st)
-{
-    const RadixTuning t = radix_tuning();
-#define SFX_PASS(KPT, SW, RK, NW) launch_pass<Src, Dst, KPT, SW, RK, NW>(name, algo_bytes, src, dst, m, shift, mask, scr, pass, st)
-#define SFX_PASS_NW(KPT, NW)                                                                     \
-    do {                                                                                         \
-        if (sweep) return t.rank ? SFX_PASS(KPT, true, true, NW) : SFX_PASS(KPT, true, false, NW);  \
-        return t.rank ? SFX_PASS(KPT, false, true, NW) : SFX_PASS(KPT, false, false, NW);           \
-    } while (0)
-    if (t.nw == 16) {
-        if constexpr (!Src::kHasVal) {                           // (KV elements: 8 per thread, LDS)
-            // elements per thread swept from 8 to 16 on hardware (profiles/r1c_radix_variants.txt):
-            // 11 wins for the E64 passes, 16 for the text-fed pass; the other sizes are not built
-            // (the chunked schedule keeps the next tile's elements in registers as well: 16 per thread spill there -- 2 * 10^9 bytes
-            // of DNA 107.9 ms at 16, 84.1 at 11, 88.7 at 8)
-            const int kk = !sweep ? (t.kpt > 11 ? 11 : t.kpt) : (Src::kFromText ? t.kpt_text : t.kpt);
-            if (kk == 16) SFX_PASS_NW(16, 16);
-            if (kk == 11) SFX_PASS_NW(11, 16);
-        }
-        if constexpr (Src::kHasVal && !Src::kFromText) {
-            // KV passes (12-byte elements): 10 per thread was the largest tile without spills in k_radix_sweep until its output
-            // loop stopped leaving sixteen hoisted LDS addresses in scratch (SFX_OPAQUE_VGPR); 12 is what the LDS holds.  Config 3's
-            // eight passes: 53.8 / 52.2 / 51.9 ms at 10 / 11 / 12.
-            // (round 3's kernel: 9; 8 / 9 / 10 measured 106.2 / 102.0 / 105.1 ms over the 23 KV passes of config 3 then)
-            // (11 and 12: the one-sweep kernel only -- the tile of the other schedules' kernel does not fit the LDS)
-            if (t.kpt_kv == 12 && sweep && t.rank) return SFX_PASS(12, true, true, 16);
-            if (t.kpt_kv == 11 && sweep && t.rank) return SFX_PASS(11, true, true, 16);
-            // (chunked schedule, m >= 2^30: 8 per thread -- the prefetched tile's registers again; 1.5 * 10^9 bytes of English-like
-            // text 204.7 / 186.4 / 185.9 ms at 10 / 9 / 8)
-            static const int kv_chunked = [] { const char* e = dev_env("SFX_RADIX_KPT_KV_CHUNKED"); return e ? atoi(e) : 8; }();
-            if (sweep && t.kpt_kv >= 10) SFX_PASS_NW(10, 16);
-            if (!sweep && kv_chunked >= 10) SFX_PASS_NW(10, 16);
-            if (sweep ? t.kpt_kv == 9 : kv_chunked == 9) SFX_PASS_NW(9, 16);
-        }
-        SFX_PASS_NW(8, 16);
-    }
-    if (t.nw == 8) { if (t.kpt == 16) SFX_PASS_NW(16, 8); SFX_PASS_NW(8, 8); }
-    if (t.kpt == 16) SFX_PASS_NW(16, 4);
-    SFX_PASS_NW(8, 4);
-#undef SFX_PASS_NW
-#undef SFX_PASS
 }
 
 // one-sweep preparation: digit totals of every pass + zeroed tickets
@@ -1812,7 +1744,7 @@ static int prepare_sweep_windows(const PackedText& t, const RadixScratch& scr, h
 
 static bool use_sweep(uint64_t m, int npass)
 {
-    return radix_tuning().sweep && m < (1ull << 30) && npass <= kMaxPasses;
+    return radix_sweep_allowed() && m < (1ull << 30) && npass <= kMaxPasses;
 }
 
 // The hybrid route of a text-fed E64 sort with split output (see k_bucket_sort).  Applies to texts between
@@ -1832,11 +1764,15 @@ constexpr int kBucketNW = 16, kBucketKPT = 16;                // the largest geo
 // LDS sort reads e0; when the route gives way nothing has been touched but e1 and the scratch.
 // will a slice of m explicit elements whose keys fit key_bits bits take the hybrid route (hybrid_sort_e64_text's own entry test)?
 // Then its sub-bucket histogram supplies the digit totals and the producer of the elements need not count digits.
-bool radix_e64_hybrid_expected(uint64_t m, int key_bits)
+static bool hybrid_size_ok(uint64_t m)
 {
     static const int enabled = [] { const char* e = dev_env("SFX_HYBRID"); return e ? atoi(e) : 1; }();
     static const uint64_t min_m = [] { const char* e = dev_env("SFX_HYBRID_MIN"); return e ? (uint64_t)strtoull(e, nullptr, 10) : (1ull << 25); }();
-    return enabled && key_bits >= 24 && m >= min_m && m <= (1ull << 28);
+    return enabled && m >= min_m && m <= (1ull << 28);
+}
+bool radix_e64_hybrid_expected(uint64_t m, int key_bits)
+{
+    return hybrid_size_ok(m) && key_bits >= 24;
 }
 static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_lo, int bit_hi, const RadixScratch& scr,
                                 hipStream_t st, sfx_build_stats* stats, const PackedText& text, uint32_t* split_v,
@@ -1846,8 +1782,6 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
     *done = false;
     *windows_ready = false;
     const bool from_elems = elem_bits > 0;
-    static const int enabled = [] { const char* e = dev_env("SFX_HYBRID"); return e ? atoi(e) : 1; }();
-    static const uint64_t min_m = [] { const char* e = dev_env("SFX_HYBRID_MIN"); return e ? (uint64_t)strtoull(e, nullptr, 10) : (1ull << 25); }();
     static const uint32_t cap = [] {
         const char* e = dev_env("SFX_HYBRID_CAP");
         const uint32_t full = kBucketNW * kWave * kBucketKPT;
@@ -1855,7 +1789,7 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
         return v >= 1 && v < full ? v : full;
     }();
     const int key_bits = from_elems ? elem_bits : bit_hi - bit_lo;
-    if (!enabled || bit_lo != 32 || key_bits < 24 || key_bits > bit_hi - bit_lo || m < min_m || m > (1ull << 28)) return SFX_OK;
+    if (!hybrid_size_ok(m) || bit_lo != 32 || key_bits < 24 || key_bits > bit_hi - bit_lo) return SFX_OK;
     if (!from_elems && (key_bits != text.kbits || m != text.n)) return SFX_OK;
     const int low_bits = key_bits - 16;
     const int top_hi = bit_lo + key_bits;                      // the sub-bucket = element bits [top_hi - 16, top_hi)
@@ -1914,18 +1848,18 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
         }
         return SFX_OK;
     }
-    const bool sweep = true;
-    static const int partition = [] { const char* e = dev_env("SFX_HYBRID_PARTITION"); return e ? atoi(e) : 1; }();
     // With no oversized sub-bucket the LDS sort can name the tied elements itself (k_bucket_sort<.., true>): no sorted keys are
-    // written, the caller orders the ties from the mask (TieRecords, sfx_host.hpp).  SFX_HYBRID_TIES=0 (development): the
-    // sorted keys, as rounds 3-5.
+    // written, the caller orders the ties from the mask (TieRecords, sfx_host.hpp).  SFX_HYBRID_TIES=0 (tests): the
+    // sorted keys, what an oversized sub-bucket makes the route write.
     static const int ties_on = [] { const char* e = dev_env("SFX_HYBRID_TIES"); return e ? atoi(e) : 1; }();
     const bool tie_mode = ties && ties_on && nover == 0;
-    // ... and then nobody reads a 32-bit key out of an element again: a text-fed sort lets the key grow into the four bits that the
-    // suffix index (m <= 2^28) leaves free -- two more symbols of DNA, a sixteenth of the ties (SrcText36).  SFX_HYBRID_KEY36=0
-    // (development): 32 + 32 bits.
-    // One symbol more comes out of the two packed words the 32-bit key is read from; two symbols of DNA (SFX_HYBRID_KEY36=2) need
-    // a third word now and then -- a 12-byte load per element: the text-fed pass 0.347 -> 0.381 ms for 0.048 -> 0.033 in k_tie_direct.
+    // ... and then nobody reads a 32-bit key out of an element again: a text-fed sort lets the key grow by one symbol into the four
+    // bits that the suffix index (m <= 2^28) leaves free (SrcText36) -- it comes out of the two packed words the 32-bit key is read
+    // from.  SFX_HYBRID_KEY36=0 (tests): 32 + 32 bits, what symbols wider than 4 bits get.  Two symbols of DNA
+    // (SFX_HYBRID_KEY36=2, tests) need a third word now and then, a 12-byte load per element: the text-fed pass 0.347 -> 0.381 ms
+    // for 0.048 -> 0.033 in k_tie_direct -- measured, not the default.
+    // SFX_HYBRID_PARTITION=0 (tests): the stable one-sweep passes of rounds 2-3 instead of the partition passes.
+    static const int partition = [] { const char* e = dev_env("SFX_HYBRID_PARTITION"); return e ? atoi(e) : 1; }();
     static const int key36_on = [] { const char* e = dev_env("SFX_HYBRID_KEY36"); return e ? atoi(e) : 1; }();
     int extra = 0;
     if (tie_mode && key36_on && partition && !from_elems && text.kbits == 32 && text.bits <= 4 && m <= (1ull << 28))
@@ -1935,80 +1869,58 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
     if (partition) {
         // two partition passes (k_partition: no order inside a sub-bucket, none needed): top 8 bits, then the next 8 inside
         // every top-8 bucket; cursors behind the oversize list
-        constexpr int kPKpt = 16, kPNw = 16;
+        constexpr int kPKpt = 16;
         SFX_LAUNCH("partition_cursors", (double)kH16Bins * 8, k_partition_cursors, kH16Bins / kBlock, kBlock, st, (const uint32_t*)bins,
                    (const uint32_t*)class_top8, cursor16, cursor8);
-        const uint64_t tile = (uint64_t)kPKpt * kPNw * kWave;
-        // (one workgroup per CU, each striding over the tiles: 128 KB of LDS leave room for no second one)
         static const unsigned cus = [] {
-            const char* e = dev_env("SFX_PARTITION_GRID");
-            if (e && atoi(e) > 0) return (unsigned)atoi(e);
             int dev = 0, n = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
             return (unsigned)n;
         }();
-        const unsigned grid1 = (unsigned)dmin<uint64_t>((m + tile - 1) / tile, dmin(cus, grid_cap()));
-        const unsigned grid2 = (unsigned)dmin<uint64_t>((m + tile - 1) / tile + kRadix, dmin(cus, grid_cap()));
-        // A full build's two passes run as TWO workgroups of 8 waves per CU (round 5): 8192-element tiles, 72 KB of LDS each, the
-        // same 128 registers per thread -- one workgroup loads and ranks while the other writes (what k_radix_sweep_duo does for the
-        // stable passes; here the whole tile fits the LDS and the kernel is the same template).  Headline, 50 steps each
+        // The two passes run as TWO workgroups of 8 waves per CU (round 5), each striding over the tiles: 8192-element tiles, 72 KB
+        // of LDS each, 128 registers per thread -- one workgroup loads and ranks while the other writes (what k_radix_sweep_duo does
+        // for the stable passes; here the whole tile fits the LDS).  Headline, 50 steps each
         // (profiles/r5_partition_duo_bench.jsonl): 1.566 / 1.577 ms with one workgroup of 16 waves, 1.523 / 1.523 with two of 8 (the
         // text-fed pass 0.400 -> 0.353 ms, the element-fed one 0.400 -> 0.373); the runs of consecutive tiles meet in one XCD's L2
-        // either way, so the shorter run of a smaller tile costs little here.  SFX_PARTITION_WAVES=16 / 8 / 4 (development).
+        // either way, so the shorter run of a smaller tile costs little here.  SFX_PARTITION_WAVES=16 / 4 (tests): one workgroup
+        // of 16 waves (round 4's geometry) / four of 4.
         static const int pwaves = [] { const char* e = dev_env("SFX_PARTITION_WAVES"); const int v = e ? atoi(e) : 8; return (v == 16 || v == 4) ? v : 8; }();
-        if (pwaves != 16) {
-#define SFX_PARTITION_PAIR(DNW)                                                                                                         \
-            do {                                                                                                                            \
-                const uint64_t dtile = (uint64_t)kPKpt * (DNW) * kWave;                                                                     \
-                const unsigned per_cu = 16u / (DNW);                                                                                        \
-                const unsigned g1 = (unsigned)dmin<uint64_t>((m + dtile - 1) / dtile, dmin(per_cu * cus, grid_cap()));                     \
-                const unsigned g2 = (unsigned)dmin<uint64_t>((m + dtile - 1) / dtile + kRadix, dmin(per_cu * cus, grid_cap()));            \
-                if (from_elems) {                                                                                                           \
-                    SFX_LAUNCH("radix_scatter_u32", (double)m * 16.0, (k_partition<SrcE64, kPKpt, DNW, false>), g1, (DNW) * kWave, st,      \
-                               SrcE64{e0}, e1, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);                                   \
-                    SFX_LAUNCH("radix_scatter_u32", (double)m * 16.0, (k_partition<SrcE64, kPKpt, DNW, true>), g2, (DNW) * kWave, st,       \
-                               SrcE64{e1}, e0, m, top_hi - 16, cursor16, (const uint32_t*)bins, class_len);                                 \
-                    uint64_t* t = e0; e0 = e1; e1 = t;     /* (from here on: e1 = the array grouped by its top 16 bits, e0 = free) */      \
-                } else {                                                                                                                    \
-                    if (extra)                                                                                                              \
-                        SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0), (k_partition<SrcText36, kPKpt, DNW, false>), \
-                                   g1, (DNW) * kWave, st, SrcText36{text, extra, wide_key}, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len); \
-                    else                                                                                                                    \
-                    SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0), (k_partition<SrcText32, kPKpt, DNW, false>),  \
-                               g1, (DNW) * kWave, st, SrcText32{text}, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);        \
-                    SFX_LAUNCH("radix_scatter_u32", (double)m * 16.0, (k_partition<SrcE64, kPKpt, DNW, true>), g2, (DNW) * kWave, st,       \
-                               SrcE64{e0}, e1, m, top_hi - 16, cursor16, (const uint32_t*)bins, class_len);                                 \
-                }                                                                                                                           \
-            } while (0)
-            if (pwaves == 4) SFX_PARTITION_PAIR(4);
-            else SFX_PARTITION_PAIR(8);
-#undef SFX_PARTITION_PAIR
-        } else
-        if (from_elems) {
-            SFX_LAUNCH("radix_scatter_u32", (double)m * 16.0, (k_partition<SrcE64, kPKpt, kPNw, false>), grid1, kPNw * kWave, st, SrcE64{e0}, e1,
-                       m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
-            SFX_LAUNCH("radix_scatter_u32", (double)m * 16.0, (k_partition<SrcE64, kPKpt, kPNw, true>), grid2, kPNw * kWave, st, SrcE64{e1}, e0,
-                       m, top_hi - 16, cursor16, (const uint32_t*)bins, class_len);
-            uint64_t* t = e0; e0 = e1; e1 = t;                 // (from here on: e1 = the array grouped by its top 16 bits, e0 = free)
-        } else {
-            if (extra)
-                SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0), (k_partition<SrcText36, kPKpt, kPNw, false>), grid1,
-                           kPNw * kWave, st, SrcText36{text, extra, wide_key}, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
-            else
-            SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0), (k_partition<SrcText32, kPKpt, kPNw, false>), grid1,
-                       kPNw * kWave, st, SrcText32{text}, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
-            SFX_LAUNCH("radix_scatter_u32", (double)m * 16.0, (k_partition<SrcE64, kPKpt, kPNw, true>), grid2, kPNw * kWave, st, SrcE64{e0}, e1,
-                       m, top_hi - 16, cursor16, (const uint32_t*)bins, class_len);
-        }
+        auto partition_pair = [&](auto nw) -> int {
+            constexpr int kPNw = decltype(nw)::value;
+            const uint64_t tile = (uint64_t)kPKpt * kPNw * kWave;
+            const unsigned per_cu = 16u / kPNw;
+            const unsigned g1 = (unsigned)dmin<uint64_t>((m + tile - 1) / tile, dmin(per_cu * cus, grid_cap()));
+            const unsigned g2 = (unsigned)dmin<uint64_t>((m + tile - 1) / tile + kRadix, dmin(per_cu * cus, grid_cap()));
+            if (from_elems) {
+                SFX_LAUNCH("radix_scatter_u32", (double)m * 16.0, (k_partition<SrcE64, kPKpt, kPNw, false>), g1, kPNw * kWave, st,
+                           SrcE64{e0}, e1, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
+                SFX_LAUNCH("radix_scatter_u32", (double)m * 16.0, (k_partition<SrcE64, kPKpt, kPNw, true>), g2, kPNw * kWave, st,
+                           SrcE64{e1}, e0, m, top_hi - 16, cursor16, (const uint32_t*)bins, class_len);
+                uint64_t* t = e0; e0 = e1; e1 = t;             // (from here on: e1 = the array grouped by its top 16 bits, e0 = free)
+            } else {
+                if (extra)
+                    SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0), (k_partition<SrcText36, kPKpt, kPNw, false>),
+                               g1, kPNw * kWave, st, SrcText36{text, extra, wide_key}, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
+                else
+                    SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0), (k_partition<SrcText32, kPKpt, kPNw, false>),
+                               g1, kPNw * kWave, st, SrcText32{text}, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
+                SFX_LAUNCH("radix_scatter_u32", (double)m * 16.0, (k_partition<SrcE64, kPKpt, kPNw, true>), g2, kPNw * kWave, st,
+                           SrcE64{e0}, e1, m, top_hi - 16, cursor16, (const uint32_t*)bins, class_len);
+            }
+            return SFX_OK;
+        };
+        if (pwaves == 16) SFX_TRY(partition_pair(std::integral_constant<int, 16>{}));
+        else if (pwaves == 4) SFX_TRY(partition_pair(std::integral_constant<int, 4>{}));
+        else SFX_TRY(partition_pair(std::integral_constant<int, 8>{}));
     } else if (from_elems) {
-        SFX_TRY(run_pass("radix_scatter_u32", (double)m * 16.0, SrcE64{e0}, DstE64{e1}, m, top_hi - 16, 255u, scr, 0, sweep, st));
-        SFX_TRY(run_pass("radix_scatter_u32", (double)m * 16.0, SrcE64{e1}, DstE64{e0}, m, top_hi - 8, 255u, scr, 1, sweep, st));
+        SFX_TRY(run_pass("radix_scatter_u32", (double)m * 16.0, SrcE64{e0}, DstE64{e1}, m, top_hi - 16, 255u, scr, 0, true, st));
+        SFX_TRY(run_pass("radix_scatter_u32", (double)m * 16.0, SrcE64{e1}, DstE64{e0}, m, top_hi - 8, 255u, scr, 1, true, st));
         uint64_t* t = e0; e0 = e1; e1 = t;                     // (from here on: e1 = the array sorted by its top 16 bits, e0 = free)
     } else {
         SrcText32 tsrc = {text};
         SFX_TRY(run_pass("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0), tsrc, DstE64{e0}, m, top_hi - 16, 255u, scr, 0,
-                         sweep, st));
-        SFX_TRY(run_pass("radix_scatter_u32", (double)m * 16.0, SrcE64{e0}, DstE64{e1}, m, top_hi - 8, 255u, scr, 1, sweep, st));
+                         true, st));
+        SFX_TRY(run_pass("radix_scatter_u32", (double)m * 16.0, SrcE64{e0}, DstE64{e1}, m, top_hi - 8, 255u, scr, 1, true, st));
     }
     uint32_t* split_k = reinterpret_cast<uint32_t*>(e0);       // (the first half of e0; the oversized sub-buckets are sorted in the second)
     const uint64_t* over_sorted = nullptr;
@@ -2091,15 +2003,11 @@ unsigned radix_e64_presort_hist(uint64_t m, int bit_lo, int bit_hi)
 }
 // the bits of the suffix index that scatter_pairs_u32 partitions by, and how many producer workgroups may count
 // them (0: the sort counts for itself)
-static int scatter_part_bits()
-{
-    static const int v = [] { const char* e = dev_env("SFX_PARTITION_BITS"); int x = e ? atoi(e) : 24; return x >= 8 && x <= 24 ? x : 24; }();
-    return v;
-}
+constexpr int kScatterPartBits = 24;
 unsigned scatter_pairs_presort_hist(uint64_t m, uint64_t n, int* lo_out, int* nb_out)
 {
     const int nb = bits_for(n > 1 ? n - 1 : 1);
-    const int lo = nb > scatter_part_bits() ? nb - scatter_part_bits() : 0;
+    const int lo = nb > kScatterPartBits ? nb - kScatterPartBits : 0;
     *lo_out = lo;
     *nb_out = nb;
     if (m == 0 || m > 0xFFFFFFFFull) return 0;
@@ -2482,10 +2390,9 @@ static bool kv12_pair(const uint64_t* k0, const uint32_t* v0, const uint64_t* k1
     if (!region(k0, v0, &lo0, &hi0) || !region(k1, v1, &lo1, &hi1)) return false;
     return hi0 <= lo1 || hi1 <= lo0;
 }
-static void kv_trace(uint64_t m, int npass, bool e12)                  // SFX_TRACE=1 (development)
+static void kv_trace(uint64_t m, int npass, bool e12)
 {
-    static const bool trace = [] { const char* e = dev_env("SFX_TRACE"); return e && atoi(e) != 0; }();
-    if (trace) fprintf(stderr, "[sfx] 64-bit-key sort: m=%llu passes=%d elements=%s\n", (unsigned long long)m, npass, e12 ? "kv12" : "k+v");
+    if (dev_trace()) fprintf(stderr, "[sfx] 64-bit-key sort: m=%llu passes=%d elements=%s\n", (unsigned long long)m, npass, e12 ? "kv12" : "k+v");
 }
 template <class Src>
 static int kv_pass_out(const char* name, double algo, const Src& src, bool out12, KV12* out_e, uint64_t* out_k, uint32_t* out_v,
@@ -2526,7 +2433,7 @@ int radix_sort_ht64(uint64_t* k0, uint32_t* v0, uint64_t* k1, uint32_t* v1, uint
     }
     // passes 1 .. npass - 2 read and write 12-byte elements, the first writes them, the last reads them (and leaves the sorted
     // keys as an array of their own, the suffixes in last_v / the value array of that side): region "0" = k0 + v0, "1" = k1 + v1
-    const bool e12 = radix_tuning().kv12 && npass >= 2 && kv12_pair(k0, v0, k1, v1, m, kv12_cap);
+    const bool e12 = radix_kv12_allowed() && npass >= 2 && kv12_pair(k0, v0, k1, v1, m, kv12_cap);
     kv_trace(m, npass, e12);
     uint64_t* kin = k0; uint32_t* vin = v0;
     uint64_t* kout = k1; uint32_t* vout = v1;
@@ -2566,7 +2473,7 @@ int radix_sort_kv64(uint64_t* k0, uint32_t* v0, uint64_t* k1, uint32_t* v1, uint
         else SFX_TRY(prepare_sweep("radix_hist_all_u64", (double)m * 8.0, SrcKV{k0, v0}, m, bit_lo, bit_hi, npass, scr, st));
     }
     // (12-byte elements between the first and the last pass: see radix_sort_ht64)
-    const bool e12 = radix_tuning().kv12 && npass >= 2 && kv12_pair(k0, v0, k1, v1, m, kv12_cap);
+    const bool e12 = radix_kv12_allowed() && npass >= 2 && kv12_pair(k0, v0, k1, v1, m, kv12_cap);
     kv_trace(m, npass, e12);
     uint64_t* kin = k0; uint32_t* vin = v0;
     uint64_t* kout = k1; uint32_t* vout = v1;
@@ -2722,7 +2629,7 @@ static int seg_passes(uint64_t* A, uint64_t* B, const SegSort& q, uint32_t* stat
         SegArgs sa = {reinterpret_cast<const SegTile*>(q.tiles), q.counters, q.segexcl, p, 4};
         const uint64_t* src = (p & 1) ? B : A;
         uint64_t* dst = (p & 1) ? A : B;
-        SFX_LAUNCH("seg_radix_pass", algo, (k_radix_pass<SrcE64, DstE64, KPT, true, true, NW, true>), kMaxGrid / 4, NW * kWave, st,
+        SFX_LAUNCH("seg_radix_pass", algo, (k_radix_pass<SrcE64, DstE64, KPT, true, NW, true>), kMaxGrid / 4, NW * kWave, st,
                    SrcE64{src}, DstE64{dst}, (uint64_t)0, 32 + 8 * p, 255u, (uint64_t)0, (const uint32_t*)nullptr,
                    (const uint32_t*)nullptr, status, q.counters + 4 + p, sa);
     }
@@ -2793,7 +2700,7 @@ int scatter_pairs_u32(uint64_t* pairs, uint64_t* tmp, uint64_t m, uint64_t n, ui
     // measured at n = 10^9 (ms, sort + scatter): direct scatter 44; 8 bits 50; 12 bits 52; 16 bits 37;
     // 20 bits (3 passes, 4 KB windows) 34; 24 bits (still 3 passes, 256-byte windows: the writes
     // coalesce into whole lines) 26
-    const int part_bits = scatter_part_bits();
+    const int part_bits = kScatterPartBits;
     const int lo = nb > part_bits ? nb - part_bits : 0;
     int in1 = 0;
     // (hist_blocks: the producer of the pairs counted the digits, scatter_pairs_presort_hist)

@@ -1743,6 +1743,12 @@ static bool ht_codes(const double* wd, int ns, uint32_t* ent, double* avg_out)
     return true;
 }
 
+// SFX_HT_CTX (tests): 0 never, 1 the build's own decision (default), 2 always
+static int ht_ctx_force()
+{
+    static const int v = [] { const char* e = dev_env("SFX_HT_CTX"); return e ? atoi(e) : 1; }();
+    return v;
+}
 // Context codes for a text whose pair counts are big[prev * sigma + cur] (dense symbols; `base` = its order-0 code, whose ent
 // gives the first symbol of every key).  The predecessors are put into at most kHtCtxClasses classes -- the high nibble of their
 // byte value to begin with (UTF-8 lead and continuation bytes, the ASCII ranges), then a few rounds of moving every predecessor
@@ -1841,7 +1847,7 @@ static bool ht_ctx_build(const std::vector<unsigned long long>& big, int sigma, 
     out->avg_ctx = bits / pairs;
     const double sym_ctx = 1.0 + (64.0 - kHtCtxCountBits - out->avg_len) / out->avg_ctx;
     const double sym_0 = (double)kHtKeyBits / out->avg_len;
-    static const int force = [] { const char* e = dev_env("SFX_HT_CTX"); return e ? atoi(e) : 1; }();   // 0: never, 2: always (development)
+    const int force = ht_ctx_force();
     if (force == 0) return false;
     out->ctx = (force == 2 || sym_ctx >= 1.10 * sym_0) ? 1 : 0;
     return out->ctx != 0;
@@ -2325,9 +2331,7 @@ static int refine(const PackedText& pt, int cpk, SaBuffers& b, uint32_t* sa, uin
         SFX_TRY(round_apply<uint64_t>(b.K0, V_cur, S_cur, m, b, sa, rank_mode ? isa : nullptr, S_next, V_next, nullptr,
                                       st, 2, n, stats, kept, tr.Hd, deep_round ? hd_of(b, S_next) : nullptr, 0u,
                                       HtDepth{nullptr, 0, 0}, min_depth, rank_mode ? b.F8 : nullptr, tr.part_pairs, rank_changes));
-        // SFX_TRACE=1 (development): one line per round
-        static const bool trace = [] { const char* e = dev_env("SFX_TRACE"); return e && atoi(e) != 0; }();
-        if (trace)
+        if (dev_trace())                                       // (one line per round)
             fprintf(stderr, "round %d %s h=%llu m=%llu lds=%llu large=%llu kept=%llu kept_groups=%llu gathers=%llu rank_changes=%llu\n", rounds,
                     rank_mode ? "rank" : "text", (unsigned long long)h, (unsigned long long)m,
                     (unsigned long long)stats.tile_sorted, (unsigned long long)stats.large_sorted, (unsigned long long)kept,
@@ -2338,17 +2342,12 @@ static int refine(const PackedText& pt, int cpk, SaBuffers& b, uint32_t* sa, uin
         if (!rank_mode && kept > 0) {
             // a text round is worth another one while it keeps resolving; a stalled one costs about
             // (kept + launch overheads) against ~n for the rank array
-            // SFX_SWITCH=text|rank is a development hook: never / always switch after the first round
-            static const int force = [] { const char* e = dev_env("SFX_SWITCH"); return !e ? 0 : (e[0] == 't' ? 1 : (e[0] == 'r' ? 2 : 0)); }();
             // (two thirds kept: measured on 1 GB of mixed-script UTF-8, whose first round keeps 75 % -- a second text
             // round costs more than the rank array it postpones)
             if (kept * 3 > m * 2) stalled += kept + (4u << 20);
             // (the depths of the deep rounds are 16-bit; a text that deep is a repeat anyway)
             const bool too_deep = h + 2 * (uint64_t)wsym > 60000;
-            // SFX_TEXT_ROUNDS_MIN=<k> (development): at least k text rounds before the switch
-            static const uint32_t min_text = [] { const char* e = dev_env("SFX_TEXT_ROUNDS_MIN"); return e ? (uint32_t)atoi(e) : 0u; }();
-            // (too_deep overrides SFX_SWITCH=text: the depths are 16-bit whatever the hook asks for -- ADVICE round 5)
-            if (isa && (force != 1 || too_deep) && (stalled * 2 > n || force == 2 || too_deep) && (too_deep || stats.text_rounds >= min_text)) {
+            if (isa && (stalled * 2 > n || too_deep)) {
                 // switching to ranks: slot = rank for resolved suffixes, head slot for the rest
                 uint32_t md = 0;
                 SFX_TRY(read_back(&md, b.ht + 256, sizeof(md), st));
@@ -2449,9 +2448,7 @@ static int sort_and_refine(const PackedText& pt, int cpk, uint64_t count, bool f
         {
             const uint64_t waves = (nwords / 2 + kWave - 1) / kWave + 1;          // (a wave: 64 lanes x 2 mask words)
             const unsigned grid = (unsigned)dmin<uint64_t>((waves + kWavesPerBlock - 1) / kWavesPerBlock, 4 * kMaxGrid);
-            // SFX_TIE_RUN_MAX=<2 .. 8> (development): the longest stretch k_tie_direct takes
-            static const uint32_t run_max = [] { const char* e = dev_env("SFX_TIE_RUN_MAX"); const int v = e ? atoi(e) : (int)kTieRunMax; return (uint32_t)(v >= 2 && v <= (int)kTieRunMax ? v : (int)kTieRunMax); }();
-            SFX_LAUNCH("tie_direct", (double)count * 0.125, k_tie_direct, grid, kBlock, st, ties.tmask, count, pt, sa, lines, run_max, ties.lmask);
+            SFX_LAUNCH("tie_direct", (double)count * 0.125, k_tie_direct, grid, kBlock, st, ties.tmask, count, pt, sa, lines, kTieRunMax, ties.lmask);
             SFX_LAUNCH("tie_totals", 0.0, k_tie_totals, 1, kBlock, st, (const uint32_t*)lines, b.totals);
         }
         uint32_t host_totals[3] = {0, 0, 0};
@@ -2492,7 +2489,7 @@ static int sort_and_refine(const PackedText& pt, int cpk, uint64_t count, bool f
             const unsigned grid = (unsigned)dmin<uint64_t>((kept + kBlock * 4 - 1) / (kBlock * 4), kMaxGrid);
             SFX_LAUNCH("depth_fill", (double)kept * 2, k_fill_u16, grid, kBlock, st, hd_of(b, S_cur), kept, (uint16_t)cpk);
         }
-        return refine(pt, cpk, b, sa, isa, S_cur, V_next, kept, st, stats, lcp_fuse, false);
+        return refine(pt, cpk, b, sa, isa, S_cur, V_next, kept, st, stats, lcp_fuse);
     }
     SFX_TRY(round_totals<KeyT>(Kr, count, b, st, &kept, &groups, fuse));
     stats.active_after_initial = kept;
@@ -2618,8 +2615,8 @@ static int build_sa_impl(const uint8_t* d_text, uint64_t n, uint32_t* d_sa, void
             static const uint64_t ctx_min = [] { const char* e = dev_env("SFX_HT_CTX_MIN"); return e ? (uint64_t)strtoull(e, nullptr, 10) : (1ull << 26); }();
             // (the bigram pass is only paid where contexts can buy 10 %: the count's 4 bits cost 4 / length symbols, and the order-1
             // entropy of text whose order-0 code already averages under 5 bits -- English-like: 4.6 -- is never that far below it)
-            static const int ctx_force = [] { const char* e = dev_env("SFX_HT_CTX"); return e ? atoi(e) : 1; }();
-            static const bool trace = [] { const char* e = dev_env("SFX_TRACE"); return e && atoi(e) != 0; }();
+            const int ctx_force = ht_ctx_force();
+            const bool trace = dev_trace();
             bool ctx_try = !lcp_fuse && ctx_force != 0 && (ht.avg_len >= 5.0 || ctx_force == 2) && (int)alpha.sigma <= kHtCtxSigmaMax && n >= ctx_min &&
                            kHtKeyBits == 64;
             if (ctx_try && ctx_force != 2) {

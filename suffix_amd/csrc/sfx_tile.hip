@@ -265,7 +265,7 @@ k_tile_sort(KeyFn keyfn, const uint32_t* __restrict__ G, uint64_t m, uint32_t* _
             for (int r = 0; r < KPT; r++) {
                 pos[r] = 0;
                 if (w * (kWave * KPT) + r * kWave < nb)     // (rounds that hold nothing but padding are skipped)
-                    pos[r] = rank_round<true>((unsigned)(key[r] >> shift) & mask, my_flags, s.cnt[w], mybit);
+                    pos[r] = rank_round((unsigned)(key[r] >> shift) & mask, my_flags, s.cnt[w], mybit);
             }
             __syncthreads();
             {
@@ -418,7 +418,7 @@ k_seg_single(KeyFn keyfn, const uint2* __restrict__ segs, uint32_t nseg, uint32_
             wave_sync();
 #pragma unroll
             for (int r = 0; r < KPT; r++)
-                if ((unsigned)r < kpt) pos[r] = rank_round<true>((unsigned)(key[r] >> shift) & 255u, my_flags, s.cnt[w], mybit);
+                if ((unsigned)r < kpt) pos[r] = rank_round((unsigned)(key[r] >> shift) & 255u, my_flags, s.cnt[w], mybit);
             __syncthreads();
             {
                 uint32_t c[NW], tile_count = 0;
@@ -925,14 +925,15 @@ static bool tile_small()
     static const bool v = [] { const char* e = dev_env("SFX_TILE_SMALL"); return e && atoi(e) != 0; }();
     return v;
 }
-// SFX_TILE_GEOM (development): 0 = 1024 threads x 8 (8192-element windows, one workgroup per CU),
-// 1 = 1024 x 4 (4096, two per CU), 2 = 512 x 8 (4096, two per CU), 3 = 512 x 4 (2048, four per CU: the
-// default); SFX_TILE_PAIR = 32 (default) | 64: all-pairs threshold.  Measured on 1 GB of English-like
-// text (tile_sort ms, profiles/r2_tile_geometry_sweep.jsonl): 66 / 76 / 50 / 34 at pair 64, 62 / 72 / 46 / 33
-// at pair 32 -- small workgroups hide the gather latency better and leave fewer members to the radix passes
-static int tile_geom()
+// The geometry: 512 threads x 4 (2048-element windows, four workgroups per CU), all-pairs ranking up to kPairMaxDefault members.
+// Measured on 1 GB of English-like text (tile_sort ms, profiles/r2_tile_geometry_sweep.jsonl) for 1024 x 8 (8192-element windows,
+// one workgroup per CU) / 1024 x 4 / 512 x 8 / 512 x 4: 66 / 76 / 50 / 34 at an all-pairs threshold of 64, 62 / 72 / 46 / 33 at 32 --
+// small workgroups hide the gather latency better and leave fewer members to the radix passes
+constexpr int kTileNW = 8, kTileKPT = 4;
+// SFX_TILE_GEOM=1 (tests): 1024 x 4; SFX_TILE_PAIR=32 (tests): the all-pairs threshold of round 2
+static bool tile_geom_1024x4()
 {
-    static const int v = [] { const char* e = dev_env("SFX_TILE_GEOM"); int x = e ? atoi(e) : 3; return x >= 0 && x <= 5 ? x : 3; }();
+    static const bool v = [] { const char* e = dev_env("SFX_TILE_GEOM"); return e && atoi(e) == 1; }();
     return v;
 }
 static int tile_pair()
@@ -961,14 +962,12 @@ static int large_phase(const KeyFn& keyfn, const TileRound& r, uint32_t nseg, ui
                        sfx_build_stats* stats)
 {
     if (nseg == 0) return SFX_OK;
-    // buckets that fit one tile of the segmented sort are sorted inside LDS by one workgroup each (SFX_SEG_SINGLE=0:
-    // development, everything through the segmented passes)
-    static const bool singles = [] { const char* e = dev_env("SFX_SEG_SINGLE"); return !e || atoi(e) != 0; }();
+    // buckets that fit one tile of the segmented sort are sorted inside LDS by one workgroup each
     const uint32_t te = seg_tile_elems(false);
     // three size classes: 256 threads x 16, 1024 x 11 (one tile of the segmented sort), 1024 x 16 (the LDS holds no more);
     // with the small tiles of the tests (4096) only the first
-    const uint32_t top = !singles ? 0u : (te > 4096u ? 16384u : 4096u);
-    if (singles) {
+    const uint32_t top = te > 4096u ? 16384u : 4096u;
+    {
         const uint2* segs = reinterpret_cast<const uint2*>(r.seg.segs);
         const unsigned grid = (unsigned)dmin<uint64_t>(nseg, (uint64_t)grid_cap() * 2);
         // (most large buckets are small ones: up to 1024 members a workgroup needs 12 KB of LDS instead of 37 -- thirteen
@@ -1011,19 +1010,11 @@ static int tile_round_impl(const KeyFn& keyfn, const TileRound& r, uint64_t m, h
     if (m > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
     SFX_HIP(hipMemsetAsync(r.counters, 0, 3 * sizeof(unsigned long long), st));     // ([3]: gathers of the deep rounds so far)
     uint64_t tmax = 0;
-    if (tile_small()) {
-        SFX_TRY((launch_tile<4, 1, 32, KeyFn>(keyfn, r, m, st, &tmax)));
-    } else {
-        const int g = tile_geom(), pm = tile_pair();
-#define SFX_TILE(NW, KPT) (pm == 32 ? launch_tile<NW, KPT, 32, KeyFn>(keyfn, r, m, st, &tmax) : launch_tile<NW, KPT, 64, KeyFn>(keyfn, r, m, st, &tmax))
-        if (g == 1) SFX_TRY(SFX_TILE(16, 4));
-        else if (g == 2) SFX_TRY(SFX_TILE(8, 8));
-        else if (g == 3) SFX_TRY(SFX_TILE(8, 4));
-        else if (g == 4) SFX_TRY(SFX_TILE(4, 4));
-        else if (g == 5) SFX_TRY(SFX_TILE(4, 2));
-        else SFX_TRY(SFX_TILE(16, 8));
-#undef SFX_TILE
-    }
+    if (tile_small()) SFX_TRY((launch_tile<4, 1, 32, KeyFn>(keyfn, r, m, st, &tmax)));
+    else if (tile_geom_1024x4() && tile_pair() == 32) SFX_TRY((launch_tile<16, 4, 32, KeyFn>(keyfn, r, m, st, &tmax)));
+    else if (tile_geom_1024x4()) SFX_TRY((launch_tile<16, 4, 64, KeyFn>(keyfn, r, m, st, &tmax)));
+    else if (tile_pair() == 32) SFX_TRY((launch_tile<kTileNW, kTileKPT, 32, KeyFn>(keyfn, r, m, st, &tmax)));
+    else SFX_TRY((launch_tile<kTileNW, kTileKPT, kPairMaxDefault, KeyFn>(keyfn, r, m, st, &tmax)));
     unsigned long long host[2] = {0, 0};                      // elements sorted in LDS, buckets left to the segmented sort
     SFX_TRY(read_back(host, r.counters, sizeof(host), st));
     if (host[0] > m || host[1] > m / (tmax + 1)) return SFX_ERR_INTERNAL;
@@ -1036,11 +1027,12 @@ static int tile_round_impl(const KeyFn& keyfn, const TileRound& r, uint64_t m, h
 }
 
 // ---- a deep text round -----------------------------------------------------------------------
-// SFX_DEEP_KPT (development): window positions per lane of k_deep_wave, 4 / 8 (default) / 16; the emulator's small-tile
-// hook selects 2 (128-position windows) so that small inputs reach the large path and the residue rules
-static int deep_kpt()
+// Window positions per lane of k_deep_wave: 4 (256-position windows); the emulator's small-tile hook selects 2 (128-position
+// windows) so that small inputs reach the large path and the residue rules
+constexpr int kDeepKPT = 4;
+static bool deep_kpt8()                                      // SFX_DEEP_KPT=8 (tests): 512-position windows
 {
-    static const int v = [] { const char* e = dev_env("SFX_DEEP_KPT"); int x = e ? atoi(e) : 4; return (x == 4 || x == 8) ? x : 4; }();
+    static const bool v = [] { const char* e = dev_env("SFX_DEEP_KPT"); return e && atoi(e) == 8; }();
     return v;
 }
 static int deep_max_iter()
@@ -1097,8 +1089,8 @@ int deep_round_text(const PackedText& pt, const TileRound& r, uint64_t m, hipStr
     SFX_HIP(hipMemsetAsync(r.counters, 0, 3 * sizeof(unsigned long long), st));
     uint64_t own_max = 0;
     if (tile_small()) SFX_TRY(launch_deep<2>(keyfn, r, m, st, &own_max));
-    else if (deep_kpt() == 8) SFX_TRY(launch_deep<8>(keyfn, r, m, st, &own_max));
-    else SFX_TRY(launch_deep<4>(keyfn, r, m, st, &own_max));
+    else if (deep_kpt8()) SFX_TRY(launch_deep<8>(keyfn, r, m, st, &own_max));
+    else SFX_TRY(launch_deep<kDeepKPT>(keyfn, r, m, st, &own_max));
     unsigned long long host[2] = {0, 0};                      // members finished or refined by the waves, large buckets
     SFX_TRY(read_back(host, r.counters, sizeof(host), st));
     if (host[0] > m || host[1] > m / (own_max + 1)) return SFX_ERR_INTERNAL;

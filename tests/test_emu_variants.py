@@ -1,12 +1,17 @@
 """Non-default code paths of the engine, on the CPU emulator: the tuning / test-hook
 environment variables are read once per process, so every variant runs in a subprocess.
-  SFX_RADIX_SWEEP / _NW / _KPT / _RANK   radix schedules, tile geometries, ranking methods
+  SFX_RADIX_SWEEP / SFX_RADIX_KV12       chunked radix schedule; (key array, value array) passes of the 64-bit-key sorts
   SFX_MAX_GRID                           multi-tile chunks per workgroup on small inputs
   SFX_PARTITION_MIN                      partitioned (cache-confined) rank / Phi scatters
   SFX_LCP_DIRECT_MIN                     sampled choice between direct and Phi/PLCP LCP, cap + fallback
   SFX_TILE_SMALL / SFX_FORCE_KEY64       small LDS windows of the refinement rounds; 64-bit initial keys
   SFX_SEG_SMALL                          small tiles in the segmented sort of the large buckets
-  SFX_HYBRID_MIN / _GEOM / _CAP / _PARTITION   hybrid initial sort (two device-wide passes + LDS sort of the sub-buckets)
+  SFX_HYBRID_MIN / _GEOM / _CAP / _TIES / _KEY36 / _PARTITION, SFX_PARTITION_WAVES
+                                         hybrid initial sort (two device-wide passes + LDS sort of the sub-buckets)
+  SFX_HT_MIN / SFX_HT_CTX / _CTX_MIN / _CTX_PILOT  compressed 64-bit keys, context codes
+  SFX_FORCE_COMPOSITE / SFX_START_RANKS  rank rounds through the composite-key sort; rank rounds from the first round on
+  SFX_TILE_GEOM / _PAIR, SFX_DEEP_ITERS / _KPT / _MAX_DEPTH   tile geometry of the rank rounds; deep text rounds
+  SFX_INDEX_TREE / SFX_QUERY_PHASE_MIN   directory-only index; two-phase query batches
 Every run compares SA and LCP with the oracle on a few texts that exercise the path."""
 import os
 import subprocess
@@ -207,8 +212,8 @@ print("OK")
 
 VARIANTS = {
     "chunked-multi-tile": {"SFX_RADIX_SWEEP": "0", "SFX_MAX_GRID": "2", "TEST_TEXTS": "2"},
-    "one-sweep-4-waves-kpt16-ballot": {"SFX_RADIX_NW": "4", "SFX_RADIX_KPT": "16", "SFX_RADIX_RANK": "0", "TEST_TEXTS": "2"},
-    "one-sweep-8-waves-kpt8": {"SFX_RADIX_NW": "8", "SFX_RADIX_KPT": "8", "SFX_MAX_GRID": "3", "TEST_TEXTS": "2"},
+    # the one-sweep schedule with the grid capped: every workgroup takes several tickets
+    "one-sweep-multi-tile": {"SFX_MAX_GRID": "3", "TEST_TEXTS": "2"},
     "partitioned-scatter": {"SFX_PARTITION_MIN": "1"},
     "direct-lcp": {"SFX_LCP_DIRECT_MIN": "8"},
     # the byte-window kernel at both window widths (round 5: 32 bytes where the sample's mean LCP is >= 16 bytes, sfx_lcp.hip), whatever
@@ -221,15 +226,11 @@ VARIANTS = {
     "small-tiles-key64-multi-tile": {"SFX_TILE_SMALL": "1", "SFX_FORCE_KEY64": "1", "SFX_MAX_GRID": "3", "SFX_SEG_SMALL": "1"},
     "key64": {"SFX_FORCE_KEY64": "1"},
     # 64-bit keys: the middle passes move 12-byte (key, suffix) elements (KV12, round 5) -- here through the chunked schedule's
-    # kernel with multi-tile chunks, and the (key array, value array) form of rounds 1-4 in every pass
+    # kernel with multi-tile chunks, and the (key array, value array) form of rounds 1-4 in every pass; the one-sweep duo kernel
+    # with multi-tile inputs: 64-bit keys on every text with the grid capped
     "key64-chunked-multi-tile": {"SFX_FORCE_KEY64": "1", "SFX_RADIX_SWEEP": "0", "SFX_MAX_GRID": "2", "TEST_TEXTS": "3"},
     "key64-split-arrays": {"SFX_FORCE_KEY64": "1", "SFX_RADIX_KV12": "0", "TEST_TEXTS": "3"},
-    # ... and k_radix_sweep (one workgroup per CU) instead of k_radix_sweep_duo (two, the default of the one-sweep KV passes since
-    # round 5); the duo kernel with multi-tile inputs: 64-bit keys on every text with the grid capped
-    "key64-one-workgroup-per-cu": {"SFX_FORCE_KEY64": "1", "SFX_RADIX_DUO": "0", "TEST_TEXTS": "3"},
     "key64-duo-multi-tile": {"SFX_FORCE_KEY64": "1", "SFX_MAX_GRID": "2"},
-    # the same kernel over 8-byte elements (development route: measured, not adopted), incl. the rank-update partition passes
-    "e64-duo-multi-tile": {"SFX_RADIX_DUO_E64": "1", "SFX_MAX_GRID": "2", "SFX_PARTITION_MIN": "1", "SFX_HYBRID": "0"},
     # hybrid initial sort forced on small inputs
     "hybrid-initial-sort": {"SFX_HYBRID_MIN": "1"},
     # ... with the partition passes as one 16-wave workgroup per CU (round 4's geometry) / four 4-wave ones instead of two 8-wave ones
@@ -250,10 +251,8 @@ VARIANTS = {
     # per workgroup
     "hybrid-initial-sort-oversized": {"SFX_HYBRID_MIN": "1", "SFX_HYBRID_CAP": "100", "SFX_MAX_GRID": "3", "SFX_HYBRID_GEOM": "1"},
     "index-directory-only": {"SFX_INDEX_TREE": "0", "TEST_TEXTS": "0"},
-    # queries longer than the tree's keys listed for a second launch (batches of >= 4096 by default), with and
-    # without the (opt-in) ordering of the batch
+    # queries longer than the tree's keys listed for a second launch (batches of >= 4096 by default)
     "index-two-phase-queries": {"SFX_QUERY_PHASE_MIN": "1", "TEST_TEXTS": "0"},
-    "index-two-phase-ordered": {"SFX_QUERY_PHASE_MIN": "1", "SFX_QUERY_ORDER": "1", "TEST_TEXTS": "0"},
     # rank rounds from the first round on (SFX_START_RANKS: a development route -- measured in round 5 on texts whose 64-bit keys leave
     # >= 95 % of the suffixes tied and NOT adopted, sort_and_refine), over compressed 64-bit keys; with the fused LCP (the deep-round
     # texts) the values are bounds from the start
@@ -310,6 +309,20 @@ def variant_runs(request, tmp_path_factory):
     futures = {name: pool.submit(_run_variant, name, str(script)) for name in wanted if name in VARIANTS}
     yield futures, str(script)
     pool.shutdown(wait=False, cancel_futures=True)
+
+
+def test_every_knob_named_is_read_by_the_engine():
+    """A variant (or the sanitizer run) that names a knob the sources no longer read would run the default route and pass."""
+    import re
+    csrc = os.path.join(ROOT, "suffix_amd", "csrc")
+    read = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".hpp")):
+            read.update(re.findall(r'dev_env\("(SFX_[A-Z0-9_]+)"\)', open(os.path.join(csrc, f)).read()))
+    named = {k for env in VARIANTS.values() for k in env if k.startswith("SFX_")} | {"SFX_TINY"}
+    named.update(re.findall(r"SFX_[A-Z0-9_]+", open(os.path.join(HERE, "asan_check.py")).read()))
+    named -= {"SFX_DEV_HOOKS", "SFX_EMULATED"}                # (compile-time macros, not knobs)
+    assert read and named <= read, sorted(named - read)
 
 
 @pytest.mark.parametrize("name", sorted(VARIANTS))
