@@ -191,6 +191,41 @@ int  sfx_gindex_query(const sfx_gindex* gx, const uint8_t* qbytes, const uint64_
                       uint32_t* ndocs_out);
 void sfx_gindex_destroy(sfx_gindex* gx);
 
+/* ---- what is repeated: repeat lengths and repeated spans from SA + LCP (no text access) -----------------
+ * S_p = the suffix at text position p: to the end of the text for a plain table, to the end of p's document for a
+ * collection (the truncated suffix of sfx_build_gsa_u32, whose sa / lcp / da are what is passed here).
+ *   rep[p]  the longest common prefix of S_p with any S_q the scope allows, 0 if it allows none:
+ *             SFX_REP_ANY        q != p                          = max(lcp[r], lcp[r + 1]), r = the rank of p
+ *             SFX_REP_EARLIER    q < p as text positions         the longest-previous-factor (LPF) array
+ *             SFX_REP_OTHER_DOC  q in another document (needs d_da; one document: all zeros)
+ *           lcp[0] counts as 0 whatever it holds (as for sfx_lcp_intervals_dev), and so does lcp[n].
+ *   src[p]  (d_src may be NULL) a position q that attains rep[p]: allowed by the scope, S_p and S_q share rep[p] bytes;
+ *           UINT32_MAX where rep[p] == 0.  WHICH witness is arbitrary by contract, as for any_position.
+ * All device pointers, n u32 each.  SFX_ERR_ARG: an unknown scope, OTHER_DOC without d_da, or a table entry >= n
+ * (checked on the device, read back once; nothing is written out of bounds even for a table that is no permutation).
+ * The call synchronises the stream for that read-back.  n == 0 succeeds. */
+enum { SFX_REP_ANY = 0, SFX_REP_EARLIER = 1, SFX_REP_OTHER_DOC = 2 };
+uint64_t sfx_repeat_lens_workspace_bytes(uint64_t n, int scope);
+int sfx_repeat_lens_dev(const uint32_t* d_sa, const uint32_t* d_lcp, const uint32_t* d_da /* OTHER_DOC only, else NULL */,
+                        uint64_t n, int scope, uint32_t* d_rep, uint32_t* d_src /* may be NULL */,
+                        void* d_workspace, uint64_t workspace_bytes, void* stream);
+/* Spans: byte i is COVERED iff some p <= i < p + rep[p] has rep[p] >= min_len (min_len >= 1).  The report lists the
+ * maximal runs of covered bytes as [begin[k], end[k]) in ascending order; with d_doc_starts (as for sfx_build_gsa_u32)
+ * a run also ends at every document start.  Every run is at least min_len long: n / min_len + 1 entries always suffice.
+ * *count_out (a HOST pointer) = the total number of spans; only the first `capacity` are written and nothing past them --
+ * a caller that sees count > capacity calls again with more room.  Keeping the first copy of every span of >= L bytes
+ * is EARLIER at min_len = L.  SFX_ERR_ARG: min_len == 0, doc_starts not as sfx_build_gsa_u32 wants them. */
+uint64_t sfx_repeat_spans_workspace_bytes(uint64_t n);
+int sfx_repeat_spans_dev(const uint32_t* d_rep, uint64_t n, uint32_t min_len,
+                         const uint64_t* d_doc_starts /* may be NULL */, uint64_t ndocs,
+                         uint32_t* d_begin, uint32_t* d_end, uint64_t capacity, uint64_t* count_out /* host */,
+                         void* d_workspace, uint64_t workspace_bytes, void* stream);
+/* the same with host buffers, staged through HBM */
+int sfx_repeat_lens_u32(const uint32_t* sa, const uint32_t* lcp, const uint32_t* da, uint64_t n, int scope,
+                        uint32_t* rep_out, uint32_t* src_out);
+int sfx_repeat_spans_u32(const uint32_t* rep, uint64_t n, uint32_t min_len, const uint64_t* doc_starts, uint64_t ndocs,
+                         uint32_t* begin_out, uint32_t* end_out, uint64_t capacity, uint64_t* count_out);
+
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the
  * text shard [shard_begin, shard_end).

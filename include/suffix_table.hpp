@@ -8,7 +8,7 @@
 //   new_ / new_naive (doc-hidden upstream, :93-100: the definition, sorted on the host -- the reference's own test oracle,
 //   tests/tests.rs:18-20; never a fallback of new_) / from_parts / into_parts / lcp_lens / table / text / len / is_empty /
 //   suffix / suffix_bytes / contains / positions / any_position,
-// plus the additive positions_batch / contains_batch.  Errors that are panics
+// plus the additive positions_batch / contains_batch and repeat_lens / repeated_spans.  Errors that are panics
 // in the reference (assert! :380, assert_eq! :117) are std::runtime_error /
 // std::length_error here.  Text is indexed by BYTES (:379).
 #pragma once
@@ -124,6 +124,30 @@ public:
                                       s.data(), e.data()), "positions_batch");
         std::vector<std::pair<uint32_t, uint32_t>> out(qs.size());
         for (size_t k = 0; k < qs.size(); k++) out[k] = {s[k], e[k]};
+        return out;
+    }
+
+    // additive: rep[p] = the longest common prefix of the suffix at byte p with any other suffix (SFX_REP_ANY) or with any
+    // suffix that starts earlier (SFX_REP_EARLIER: the longest-previous-factor array), see suffix_hip.h
+    std::vector<uint32_t> repeat_lens(int scope = SFX_REP_ANY) const
+    {
+        if (scope != SFX_REP_ANY && scope != SFX_REP_EARLIER) throw std::invalid_argument("repeat_lens: scope must be SFX_REP_ANY or SFX_REP_EARLIER");
+        const std::vector<uint32_t> lcp = lcp_lens();
+        std::vector<uint32_t> rep(table_.size(), 0u);
+        check(sfx_repeat_lens_u32(table_.data(), lcp.data(), nullptr, table_.size(), scope, rep.data(), nullptr), "repeat_lens");
+        return rep;
+    }
+    // additive: [begin, end) of the maximal runs of bytes inside a repeat of at least min_len bytes, ascending
+    std::vector<std::pair<uint32_t, uint32_t>> repeated_spans(uint32_t min_len, int scope = SFX_REP_ANY) const
+    {
+        if (min_len == 0) throw std::invalid_argument("repeated_spans: min_len must be at least 1");
+        const std::vector<uint32_t> rep = repeat_lens(scope);
+        const uint64_t cap = rep.size() / min_len + 1;                               // every run is at least min_len long
+        std::vector<uint32_t> b(cap), e(cap);
+        uint64_t count = 0;
+        check(sfx_repeat_spans_u32(rep.data(), rep.size(), min_len, nullptr, 0, b.data(), e.data(), cap, &count), "repeated_spans");
+        std::vector<std::pair<uint32_t, uint32_t>> out((size_t)count);
+        for (size_t k = 0; k < out.size(); k++) out[k] = {b[k], e[k]};
         return out;
     }
 

@@ -72,6 +72,10 @@ NAMES = [
     ("k_gsa_fixup_keys", "gsa_fixup_sort"), ("k_gsa_merge_affected", "gsa_merge"), ("k_gsa_merge_unaffected", "gsa_merge"),
     ("k_gsa_lcp", "gsa_lcp"), ("k_gsa_query", "gsa_query"), ("k_gsa_doc_count", "gsa_doc_count"), ("k_gsa_prev_keys", "gsa_prev"),
     ("k_gsa_prev", "gsa_prev"),
+    ("k_rep_any", "rep_any"), ("k_rep_earlier_open", "rep_earlier_open"), ("k_rep_earlier", "rep_earlier"),
+    ("k_rep_doc_heads", "rep_doc_runs"), ("k_rep_run_starts", "rep_doc_runs"), ("k_rep_other_doc", "rep_other_doc"),
+    ("k_rep_spans_max_", "rep_spans_max"), ("k_rep_spans_mark", "rep_spans_mark"), ("k_rep_spans_flag", "rep_spans_flag"),
+    ("k_rep_spans_emit", "rep_spans"),
     ("k_doc_lookup", "doc_lookup"), ("k_query_batch_tree", "query_batch_tree"),
     ("k_query_batch_dir", "query_batch_dir"), ("k_query_tree_long", "query_tree_long"), ("k_query_batch", "query_batch"),
     # -- not part of a build's profile: the polled read-back and the memory-system probes

@@ -77,6 +77,12 @@ ABI = [
     ("sfx_gindex_query_dev", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("sfx_gindex_query", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("sfx_gindex_destroy", None, [_vp]),
+    ("sfx_repeat_lens_workspace_bytes", _u64, [_u64, _int]),
+    ("sfx_repeat_lens_dev", _int, [_vp, _vp, _vp, _u64, _int, _vp, _vp, _vp, _u64, _vp]),
+    ("sfx_repeat_spans_workspace_bytes", _u64, [_u64]),
+    ("sfx_repeat_spans_dev", _int, [_vp, _u64, _u32, _vp, _u64, _vp, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64, _vp]),
+    ("sfx_repeat_lens_u32", _int, [_vp, _vp, _vp, _u64, _int, _vp, _vp]),
+    ("sfx_repeat_spans_u32", _int, [_vp, _u64, _u32, _vp, _u64, _vp, _vp, _u64, ctypes.POINTER(_u64)]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),
@@ -97,6 +103,8 @@ ABI = [
     ("sfx_get_option", _u64, [_int]),
 ]
 SFX_OPT_TINY_MAX = 1
+SFX_REP_ANY, SFX_REP_EARLIER, SFX_REP_OTHER_DOC = 0, 1, 2
+REP_SCOPES = {"any": SFX_REP_ANY, "earlier": SFX_REP_EARLIER, "other_doc": SFX_REP_OTHER_DOC}
 
 
 class SuffixHipError(RuntimeError):

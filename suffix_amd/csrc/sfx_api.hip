@@ -662,6 +662,83 @@ int sfx_build_gsa_u32(const uint8_t* text, uint64_t n, const uint64_t* doc_start
     return SFX_OK;
 }
 
+// ---- repeat lengths, repeated spans ---------------------------------------------------------------------
+uint64_t sfx_repeat_lens_workspace_bytes(uint64_t n, int scope) { return repeat_lens_workspace_bytes(n, scope); }
+int sfx_repeat_lens_dev(const uint32_t* d_sa, const uint32_t* d_lcp, const uint32_t* d_da, uint64_t n, int scope, uint32_t* d_rep,
+                        uint32_t* d_src, void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    return repeat_lens_dev(d_sa, d_lcp, d_da, n, scope, d_rep, d_src, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+uint64_t sfx_repeat_spans_workspace_bytes(uint64_t n) { return repeat_spans_workspace_bytes(n); }
+int sfx_repeat_spans_dev(const uint32_t* d_rep, uint64_t n, uint32_t min_len, const uint64_t* d_doc_starts, uint64_t ndocs,
+                         uint32_t* d_begin, uint32_t* d_end, uint64_t capacity, uint64_t* count_out, void* d_workspace,
+                         uint64_t workspace_bytes, void* stream)
+{
+    return repeat_spans_dev(d_rep, n, min_len, d_doc_starts, ndocs, d_begin, d_end, capacity, count_out, d_workspace, workspace_bytes,
+                            (hipStream_t)stream);
+}
+int sfx_repeat_lens_u32(const uint32_t* sa, const uint32_t* lcp, const uint32_t* da, uint64_t n, int scope, uint32_t* rep_out,
+                        uint32_t* src_out)
+{
+    if (scope != SFX_REP_ANY && scope != SFX_REP_EARLIER && scope != SFX_REP_OTHER_DOC) return SFX_ERR_ARG;
+    if (scope == SFX_REP_OTHER_DOC && !da && n) return SFX_ERR_ARG;
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!sa || !lcp || !rep_out) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    const bool docs = scope == SFX_REP_OTHER_DOC;
+    DevBuf ds, dl, dd, dr, dq, dw;
+    const uint64_t wsb = repeat_lens_workspace_bytes(n, scope), bytes = n * sizeof(uint32_t);
+    SFX_TRY(ds.alloc(bytes));
+    SFX_TRY(dl.alloc(bytes));
+    if (docs) SFX_TRY(dd.alloc(bytes));
+    SFX_TRY(dr.alloc(bytes));
+    if (src_out) SFX_TRY(dq.alloc(bytes));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(ds.p, sa, bytes, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dl.p, lcp, bytes, hipMemcpyHostToDevice, st));
+    if (docs) SFX_HIP(hipMemcpyAsync(dd.p, da, bytes, hipMemcpyHostToDevice, st));
+    SFX_TRY(repeat_lens_dev((const uint32_t*)ds.p, (const uint32_t*)dl.p, (const uint32_t*)dd.p, n, scope, (uint32_t*)dr.p, (uint32_t*)dq.p,
+                            dw.p, wsb, st));
+    SFX_HIP(hipMemcpyAsync(rep_out, dr.p, bytes, hipMemcpyDeviceToHost, st));
+    if (src_out) SFX_HIP(hipMemcpyAsync(src_out, dq.p, bytes, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+int sfx_repeat_spans_u32(const uint32_t* rep, uint64_t n, uint32_t min_len, const uint64_t* doc_starts, uint64_t ndocs,
+                         uint32_t* begin_out, uint32_t* end_out, uint64_t capacity, uint64_t* count_out)
+{
+    if (!count_out || min_len == 0) return SFX_ERR_ARG;
+    *count_out = 0;
+    if (n > 0xFFFFFFFFull || ndocs > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!rep || (capacity && (!begin_out || !end_out)) || (doc_starts && ndocs == 0)) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    if (capacity > n / min_len + 1) capacity = n / min_len + 1;          // (no report is longer)
+    DevBuf dr, dst, db, de, dw;
+    const uint64_t wsb = repeat_spans_workspace_bytes(n);
+    SFX_TRY(dr.alloc(n * sizeof(uint32_t)));
+    if (doc_starts) SFX_TRY(dst.alloc(ndocs * sizeof(uint64_t)));
+    SFX_TRY(db.alloc(capacity * sizeof(uint32_t)));
+    SFX_TRY(de.alloc(capacity * sizeof(uint32_t)));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    SFX_HIP(hipMemcpyAsync(dr.p, rep, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (doc_starts) SFX_HIP(hipMemcpyAsync(dst.p, doc_starts, ndocs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(repeat_spans_dev((const uint32_t*)dr.p, n, min_len, (const uint64_t*)dst.p, ndocs, (uint32_t*)db.p, (uint32_t*)de.p, capacity,
+                             count_out, dw.p, wsb, st));
+    const uint64_t k = dmin<uint64_t>(*count_out, capacity);
+    if (k) {
+        SFX_HIP(hipMemcpyAsync(begin_out, db.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(end_out, de.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+
 int sfx_gindex_create_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_starts, uint64_t ndocs, const uint32_t* d_sa,
                           const uint32_t* d_da, void* stream, sfx_gindex** out)
 {

@@ -443,6 +443,13 @@ int gindex_query_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts
                      const uint32_t* d_da, const uint32_t* d_prev, const uint8_t* d_q, const uint64_t* d_qoff, uint64_t nq,
                      uint32_t* d_start, uint32_t* d_end, uint8_t* d_found, uint32_t* d_any, uint32_t* d_ndocs, void* scratch,
                      uint64_t scratch_bytes, hipStream_t st);
+// repeat lengths (scope: SFX_REP_*) and repeated spans from SA + LCP (sfx_tree.hip)
+uint64_t repeat_lens_workspace_bytes(uint64_t n, int scope);
+int repeat_lens_dev(const uint32_t* d_sa, const uint32_t* d_lcp, const uint32_t* d_da, uint64_t n, int scope, uint32_t* d_rep,
+                    uint32_t* d_src, void* ws, uint64_t ws_bytes, hipStream_t st);
+uint64_t repeat_spans_workspace_bytes(uint64_t n);
+int repeat_spans_dev(const uint32_t* d_rep, uint64_t n, uint32_t min_len, const uint64_t* d_starts, uint64_t ndocs, uint32_t* d_begin,
+                     uint32_t* d_end, uint64_t capacity, uint64_t* count_out, void* ws, uint64_t ws_bytes, hipStream_t st);
 
 sfx_build_stats& tls_build_stats();
 

@@ -275,8 +275,9 @@ static uint64_t pyramid_words(uint64_t n)
     }
     return words;
 }
-// the levels above an LCP array (pyramid_words(n) u32 at w)
-static int pyramid_build(const uint32_t* d_lcp, uint64_t n, uint32_t* w, const char* name, hipStream_t st, Pyramid* out)
+// the levels above an LCP array (pyramid_words(n) u32 at w); first_is_zero = 0: above any array, entry 0 as it is
+static int pyramid_build(const uint32_t* d_lcp, uint64_t n, uint32_t* w, const char* name, hipStream_t st, Pyramid* out,
+                         int first_is_zero = 1)
 {
     Pyramid& py = *out;
     py.lvl[0] = d_lcp;
@@ -286,7 +287,7 @@ static int pyramid_build(const uint32_t* d_lcp, uint64_t n, uint32_t* w, const c
     while (py.levels < kPyrMaxLevels && len > 1) {
         const uint64_t out_len = (len + kPyrFan - 1) / kPyrFan;
         const unsigned grid = (unsigned)dmin<uint64_t>((out_len + kBlock - 1) / kBlock, kMaxGrid);
-        SFX_LAUNCH(name, (double)len * 4, k_pyr_reduce, grid, kBlock, st, py.lvl[py.levels - 1], len, w, out_len, 1);
+        SFX_LAUNCH(name, (double)len * 4, k_pyr_reduce, grid, kBlock, st, py.lvl[py.levels - 1], len, w, out_len, first_is_zero);
         py.lvl[py.levels] = w;
         py.len[py.levels] = out_len;
         py.levels++;
@@ -877,6 +878,420 @@ int gindex_query_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts
     const double per_block = (double)kWave * kGsaCountPerLane * kWavesPerBlock;
     const unsigned cgrid = (unsigned)dmax(1.0, dmin((double)dmin<unsigned>(kMaxGrid, grid_cap()), bound / per_block + 1.0));
     SFX_LAUNCH("gsa_doc_count", 0.0, k_gsa_doc_count, cgrid, kBlock, st, (const uint64_t*)offs, nq, (const uint32_t*)qstart, d_prev, d_ndocs);
+    return SFX_OK;
+}
+
+// ---- repeat lengths and repeated spans from SA + LCP (include/suffix_hip.h) ----------------------------------------
+// rep[p] = the longest common prefix of the suffix at text position p (truncated at its document's end in a collection)
+// with any suffix the scope allows; no text access: the common prefix of two ranks is the minimum of the LCP values
+// between them, and the best partner on either side of a rank is the NEAREST allowed one.
+//   ANY        the two neighbours;
+//   EARLIER    the nearest ranks on either side that hold a smaller position (LPF): all-nearest-smaller-values on the
+//              SA VALUES, over a second min-pyramid, then two range minima on the LCP pyramid;
+//   OTHER_DOC  the ranks just outside the run of equal DA values the rank stands in.
+// Every kernel that scatters by position refuses a table entry >= n (flag, read back once; never written).
+constexpr uint32_t kRepNone = 0xFFFFFFFFu;
+
+__device__ __forceinline__ void rep_store(uint32_t* __restrict__ rep, uint32_t* __restrict__ src, uint64_t p, uint32_t left, uint32_t right,
+                                          uint32_t wl, uint32_t wr)
+{
+    const uint32_t m = dmax(left, right);
+    rep[p] = m;
+    if (src) src[p] = m == 0 ? kRepNone : (left >= right ? wl : wr);
+}
+__global__ void __launch_bounds__(kBlock)
+k_rep_any(const uint32_t* __restrict__ sa, const uint32_t* __restrict__ lcp, uint64_t n, uint32_t* __restrict__ rep,
+          uint32_t* __restrict__ src, uint32_t* __restrict__ bad)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) {
+        const uint64_t p = sa[r];
+        if (p >= n) { *bad = 1u; continue; }
+        const uint32_t left = r ? lcp[r] : 0u, right = r + 1 < n ? lcp[r + 1] : 0u;       // (lcp[0] and lcp[n] count as 0)
+        rep_store(rep, src, p, left, right, left ? sa[r - 1] : kRepNone, right ? sa[r + 1] : kRepNone);
+    }
+}
+
+// nearest q < from with lvl[0][q] < v, or -1: "none" is an answer here (prev_smaller's boundary 0 is an LCP convention, and
+// this pyramid stands on suffix-array values)
+__device__ __forceinline__ int64_t rep_prev_smaller(const Pyramid& py, uint64_t from, uint32_t v)
+{
+    int l = 0;
+    int64_t idx = (int64_t)from - 1;
+    for (;;) {
+        if (idx < 0) return -1;
+        bool found = false;
+        for (;;) {
+            if (py.lvl[l][idx] < v) { found = true; break; }
+            if (idx % kPyrFan == 0) break;
+            idx--;
+        }
+        if (found) break;
+        idx = idx / kPyrFan - 1;                             // (the top level is one block: -1 there)
+        l++;
+    }
+    while (l > 0) {
+        l--;
+        int64_t c = dmin<int64_t>(idx * kPyrFan + kPyrFan - 1, (int64_t)py.len[l] - 1);
+        while (py.lvl[l][c] >= v) c--;
+        idx = c;
+    }
+    return idx;
+}
+// min of tile values [lo, hi] (tile coordinates, lo <= hi) under the binary min-tree of k_lcp_intervals
+__device__ __forceinline__ uint32_t iv_range_min(const uint32_t* tr, int lo, int hi)
+{
+    uint32_t m = 0xFFFFFFFFu;
+    unsigned l = (unsigned)(kIvTile + lo), r = (unsigned)(kIvTile + hi + 1);
+    while (l < r) {
+        if (l & 1u) m = dmin(m, tr[l++]);
+        if (r & 1u) m = dmin(m, tr[--r]);
+        l >>= 1;
+        r >>= 1;
+    }
+    return m;
+}
+// rank r (position v = sa[r] < n) through the two global pyramids
+__device__ __forceinline__ void rep_earlier_finish(const Pyramid& ps, const Pyramid& pl, uint64_t n, uint64_t r, uint32_t* __restrict__ rep,
+                                                   uint32_t* __restrict__ src)
+{
+    const uint32_t v = ps.lvl[0][r];
+    const int64_t a = rep_prev_smaller(ps, r, v);
+    const uint64_t b = next_smaller(ps, r, v, false, n);
+    const uint32_t left = a < 0 ? 0u : range_min(pl, (uint64_t)a + 1, r);
+    const uint32_t right = b >= n ? 0u : range_min(pl, r + 1, b);
+    rep_store(rep, src, v, left, right, a < 0 ? kRepNone : ps.lvl[0][a], b >= n ? kRepNone : ps.lvl[0][b]);
+}
+// The shape of k_lcp_intervals: a workgroup stages kIvTile SA values and their LCP values in LDS, each under a binary
+// min-tree; a rank whose two nearest smaller positions lie inside the tile is answered there (two tree searches, two tree
+// range minima, the same few LDS reads for every lane).  A rank whose search leaves the tile is LISTED and finished by a
+// dense second launch over the global pyramids (what does not fit the list is finished in place).
+__global__ void __launch_bounds__(kBlock)
+k_rep_earlier(Pyramid ps, Pyramid pl, uint64_t n, uint64_t tiles_per_block, uint32_t* __restrict__ rep, uint32_t* __restrict__ src,
+              uint32_t* __restrict__ open_list, uint64_t open_cap, unsigned long long* __restrict__ open_count, uint32_t* __restrict__ bad)
+{
+    __shared__ uint32_t ts[2 * kIvTile];
+    __shared__ uint32_t tl[2 * kIvTile];
+    __shared__ uint32_t esc[kIvTile];
+    __shared__ uint32_t n_esc;
+    __shared__ unsigned long long esc_base;
+    const uint32_t* sa = ps.lvl[0];
+    const uint32_t* lcp = pl.lvl[0];
+    const uint64_t tile0 = (uint64_t)blockIdx.x * tiles_per_block;
+    for (uint64_t tile = tile0; tile < tile0 + tiles_per_block; tile++) {
+        const uint64_t base = tile * kIvTile;
+        if (base >= n) break;
+        if (threadIdx.x == 0) n_esc = 0;
+        for (unsigned i = threadIdx.x; i < (unsigned)kIvTile; i += kBlock) {
+            const uint64_t g = base + i;
+            ts[kIvTile + i] = g < n ? sa[g] : 0xFFFFFFFFu;               // (past the end: smaller than nothing)
+            tl[kIvTile + i] = (g == 0 || g >= n) ? 0u : lcp[g];
+        }
+        __syncthreads();
+        for (unsigned w = kIvTile / 2; w >= 1; w >>= 1) {
+            for (unsigned k = w + threadIdx.x; k < 2 * w; k += kBlock) {
+                ts[k] = dmin(ts[2 * k], ts[2 * k + 1]);
+                tl[k] = dmin(tl[2 * k], tl[2 * k + 1]);
+            }
+            __syncthreads();
+        }
+        for (unsigned i = threadIdx.x; i < (unsigned)kIvTile; i += kBlock) {
+            const uint64_t r = base + i;
+            if (r >= n) break;
+            const uint32_t v = ts[kIvTile + i];
+            if (v >= n) { *bad = 1u; continue; }
+            if (v == 0) { rep_store(rep, src, 0, 0u, 0u, kRepNone, kRepNone); continue; }     // nothing is earlier
+            const int jl = iv_prev_smaller(ts, (int)i, v);
+            const int jr = iv_next_smaller(ts, (int)i, v, false);
+            if ((jl < 0 && base > 0) || (jr >= kIvTile && base + kIvTile < n)) {
+                esc[atomicAdd(&n_esc, 1u)] = (uint32_t)r;
+                continue;
+            }
+            const uint32_t left = jl < 0 ? 0u : iv_range_min(tl, jl + 1, (int)i);
+            const uint32_t right = jr >= kIvTile ? 0u : iv_range_min(tl, (int)i + 1, jr);
+            rep_store(rep, src, v, left, right, jl < 0 ? kRepNone : ts[kIvTile + jl], jr >= kIvTile ? kRepNone : ts[kIvTile + jr]);
+        }
+        __syncthreads();
+        const uint32_t cnt = n_esc;
+        if (cnt) {
+            if (threadIdx.x == 0) esc_base = atomicAdd(open_count, (unsigned long long)cnt);
+            __syncthreads();
+            const unsigned long long at = esc_base;
+            for (unsigned k = threadIdx.x; k < cnt; k += kBlock) {
+                if (at + k < open_cap) open_list[at + k] = esc[k];
+                else rep_earlier_finish(ps, pl, n, esc[k], rep, src);
+            }
+        }
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(kBlock)
+k_rep_earlier_open(Pyramid ps, Pyramid pl, uint64_t n, const uint32_t* __restrict__ open_list, uint64_t open_cap,
+                   const unsigned long long* __restrict__ open_count, uint32_t* __restrict__ rep, uint32_t* __restrict__ src)
+{
+    unsigned long long cnt = *open_count;
+    if (cnt > open_cap) cnt = open_cap;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < cnt; k += stride) rep_earlier_finish(ps, pl, n, open_list[k], rep, src);
+}
+
+// OTHER_DOC: head flags of the runs of equal DA values (scanned into run ids), the first rank of every run, then per rank
+// the two range minima to just outside its run
+__global__ void __launch_bounds__(kBlock)
+k_rep_doc_heads(const uint32_t* __restrict__ sa, const uint32_t* __restrict__ da, uint64_t n, uint32_t* __restrict__ flag,
+                uint32_t* __restrict__ bad)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) {
+        if (sa[r] >= n) *bad = 1u;
+        flag[r] = (r == 0 || da[r] != da[r - 1]) ? 1u : 0u;
+    }
+}
+// P = the exclusive scan of the head flags (P[n] = the number of runs): run_start[k] = first rank of run k, [runs] = n
+__global__ void __launch_bounds__(kBlock)
+k_rep_run_starts(const uint32_t* __restrict__ P, uint64_t n, uint32_t* __restrict__ run_start)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) {
+        if (P[r + 1] != P[r]) run_start[P[r]] = (uint32_t)r;
+        if (r == 0) run_start[P[n]] = (uint32_t)n;
+    }
+}
+__global__ void __launch_bounds__(kBlock)
+k_rep_other_doc(const uint32_t* __restrict__ sa, Pyramid pl, uint64_t n, const uint32_t* __restrict__ P,
+                const uint32_t* __restrict__ run_start, uint32_t* __restrict__ rep, uint32_t* __restrict__ src)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint32_t* lcp = pl.lvl[0];
+    for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride) {
+        const uint64_t p = sa[r];
+        if (p >= n) continue;                                            // (flagged by k_rep_doc_heads)
+        const uint32_t k = P[r + 1] - 1;
+        const uint64_t s = run_start[k], e = run_start[k + 1];           // a = s - 1, b = e
+        const uint32_t left = s == 0 ? 0u : (s == r ? lcp[r] : range_min(pl, s, r));
+        const uint32_t right = e >= n ? 0u : (e == r + 1 ? lcp[e] : range_min(pl, r + 1, e));
+        rep_store(rep, src, p, left, right, s == 0 ? kRepNone : sa[s - 1], e >= n ? kRepNone : sa[e]);
+    }
+}
+
+// [bad flag | LCP pyramid | EARLIER: SA pyramid, counter, list | OTHER_DOC: P (n + 1), run starts (n + 1), scan partials]
+struct RepLensWs {
+    uint32_t *bad, *pyr_lcp, *pyr_sa, *open_list, *P, *run_start, *part;
+    unsigned long long* open_count;
+};
+template <class A> static void rep_lens_carve(A& a, uint64_t n, int scope, RepLensWs* w)
+{
+    *w = RepLensWs();
+    w->bad = a.template take<uint32_t>(64);
+    if (scope == SFX_REP_ANY) return;
+    w->pyr_lcp = a.template take<uint32_t>(pyramid_words(n) + 64);
+    if (scope == SFX_REP_EARLIER) {
+        w->pyr_sa = a.template take<uint32_t>(pyramid_words(n) + 64);
+        w->open_count = a.template take<unsigned long long>(32);
+        w->open_list = a.template take<uint32_t>(open_list_cap(n));
+    } else {
+        w->P = a.template take<uint32_t>(n + 1);
+        w->run_start = a.template take<uint32_t>(n + 1);
+        w->part = a.template take<uint32_t>(kMaxGrid + 64);
+    }
+}
+uint64_t repeat_lens_workspace_bytes(uint64_t n, int scope)
+{
+    if (scope != SFX_REP_ANY && scope != SFX_REP_EARLIER && scope != SFX_REP_OTHER_DOC) return 0;
+    GsaSizer z;
+    RepLensWs w;
+    rep_lens_carve(z, n, scope, &w);
+    return z.used;
+}
+int repeat_lens_dev(const uint32_t* d_sa, const uint32_t* d_lcp, const uint32_t* d_da, uint64_t n, int scope, uint32_t* d_rep,
+                    uint32_t* d_src, void* ws, uint64_t ws_bytes, hipStream_t st)
+{
+    if (scope != SFX_REP_ANY && scope != SFX_REP_EARLIER && scope != SFX_REP_OTHER_DOC) return SFX_ERR_ARG;
+    if (scope == SFX_REP_OTHER_DOC && !d_da && n) return SFX_ERR_ARG;
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!d_sa || !d_lcp || !d_rep) return SFX_ERR_ARG;
+    if (!ws || ws_bytes < repeat_lens_workspace_bytes(n, scope)) return SFX_ERR_WORKSPACE;
+    Arena a(ws, ws_bytes);
+    RepLensWs w;
+    rep_lens_carve(a, n, scope, &w);
+    if (a.overflow) return SFX_ERR_INTERNAL;
+    SFX_HIP(hipMemsetAsync(w.bad, 0, sizeof(uint32_t), st));
+    const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
+    if (scope == SFX_REP_ANY) {
+        SFX_LAUNCH("rep_any", (double)n * (d_src ? 20 : 12), k_rep_any, grid, kBlock, st, d_sa, d_lcp, n, d_rep, d_src, w.bad);
+    } else if (scope == SFX_REP_EARLIER) {
+        Pyramid pl, ps;
+        SFX_TRY(pyramid_build(d_lcp, n, w.pyr_lcp, "rep_pyramid", st, &pl));
+        SFX_TRY(pyramid_build(d_sa, n, w.pyr_sa, "rep_pyramid", st, &ps, 0));
+        const uint64_t cap = open_list_cap(n);
+        SFX_HIP(hipMemsetAsync(w.open_count, 0, sizeof(unsigned long long), st));
+        Chunking ch = make_chunking(n, kIvTile, 4 * kMaxGrid);
+        SFX_LAUNCH("rep_earlier", (double)n * (d_src ? 16 : 12), k_rep_earlier, ch.blocks, kBlock, st, ps, pl, n, ch.tiles_per_block, d_rep,
+                   d_src, w.open_list, cap, w.open_count, w.bad);
+        SFX_LAUNCH("rep_earlier_open", 0.0, k_rep_earlier_open, grid, kBlock, st, ps, pl, n, (const uint32_t*)w.open_list, cap,
+                   (const unsigned long long*)w.open_count, d_rep, d_src);
+    } else {
+        SFX_LAUNCH("rep_doc_runs", (double)n * 12, k_rep_doc_heads, grid, kBlock, st, d_sa, d_da, n, w.P, w.bad);
+        SFX_TRY(gsa_scan<uint32_t>(w.P, n, w.P, w.part, st));
+        uint32_t runs = 0;
+        SFX_TRY(read_back(&runs, w.P + n, sizeof(runs), st));
+        if (runs <= 1) {                                     // one document: nothing is in another one, no search
+            SFX_HIP(hipMemsetAsync(d_rep, 0, n * sizeof(uint32_t), st));
+            if (d_src) SFX_HIP(hipMemsetAsync(d_src, 0xFF, n * sizeof(uint32_t), st));
+        } else {
+            Pyramid pl;
+            SFX_TRY(pyramid_build(d_lcp, n, w.pyr_lcp, "rep_pyramid", st, &pl));
+            SFX_LAUNCH("rep_doc_runs", (double)n * 8 + (double)runs * 4, k_rep_run_starts, grid, kBlock, st, (const uint32_t*)w.P, n,
+                       w.run_start);
+            SFX_LAUNCH("rep_other_doc", (double)n * (d_src ? 24 : 16), k_rep_other_doc, grid, kBlock, st, d_sa, pl, n,
+                       (const uint32_t*)w.P, (const uint32_t*)w.run_start, d_rep, d_src);
+        }
+    }
+    uint32_t bad = 0;
+    SFX_TRY(read_back(&bad, w.bad, sizeof(bad), st));
+    return bad ? SFX_ERR_ARG : SFX_OK;
+}
+
+// Spans: byte i is covered iff some qualifying p <= i (rep[p] >= min_len) reaches past it, i.e. iff the prefix MAXIMUM of
+// p + rep[p] over the qualifying p <= i exceeds i.  The scan has the three phases of gsa_scan with max in place of add;
+// a run begins at a covered byte whose predecessor is not covered or that starts a document; the k-th end belongs to
+// the k-th begin, so one sum scan of the begin flags places both.
+__device__ __forceinline__ uint32_t rep_span_reach(const uint32_t* __restrict__ rep, uint64_t p, uint32_t min_len, uint64_t n)
+{
+    const uint32_t v = rep[p];
+    return v >= min_len ? (uint32_t)dmin<uint64_t>(p + v, n) : 0u;       // (<= n: fits, whatever the caller's array holds)
+}
+__global__ void __launch_bounds__(kBlock)
+k_rep_spans_max_count(const uint32_t* __restrict__ rep, uint64_t n, uint32_t min_len, uint64_t chunk, uint32_t* __restrict__ part)
+{
+    __shared__ uint32_t sh[kWavesPerBlock];
+    const uint64_t b = (uint64_t)blockIdx.x * chunk, e = dmin<uint64_t>(b + chunk, n);
+    uint32_t acc = 0;
+    for (uint64_t i = b + threadIdx.x; i < e; i += kBlock) acc = dmax(acc, rep_span_reach(rep, i, min_len, n));
+    uint32_t total;
+    (void)block_scan_max_excl<uint32_t>(acc, sh, total);
+    if (threadIdx.x == 0) part[blockIdx.x] = total;
+}
+__global__ void __launch_bounds__(kBlock)
+k_rep_spans_max_top(uint32_t* __restrict__ part, unsigned nb)
+{
+    __shared__ uint32_t sh[kWavesPerBlock];
+    uint32_t carry = 0;
+    for (unsigned base = 0; base < nb; base += kBlock) {
+        const unsigned i = base + threadIdx.x;
+        uint32_t total;
+        const uint32_t ex = block_scan_max_excl<uint32_t>(i < nb ? part[i] : 0u, sh, total);
+        if (i < nb) part[i] = dmax(carry, ex);
+        carry = dmax(carry, total);
+    }
+}
+__global__ void __launch_bounds__(kBlock)
+k_rep_spans_max_apply(const uint32_t* __restrict__ rep, uint64_t n, uint32_t min_len, uint64_t chunk, const uint32_t* __restrict__ part,
+                      uint32_t* __restrict__ M)
+{
+    __shared__ uint32_t sh[kWavesPerBlock];
+    const uint64_t b = (uint64_t)blockIdx.x * chunk, e = dmin<uint64_t>(b + chunk, n);
+    uint32_t run = part[blockIdx.x];
+    for (uint64_t base = b; base < e; base += kBlock) {                // (uniform trip count: the block scan has barriers)
+        const uint64_t i = base + threadIdx.x;
+        const uint32_t v = i < e ? rep_span_reach(rep, i, min_len, n) : 0u;
+        uint32_t total;
+        const uint32_t ex = block_scan_max_excl<uint32_t>(v, sh, total);
+        if (i < e) M[i] = dmax(run, dmax(ex, v));
+        run = dmax(run, total);
+    }
+}
+// document starts: ndocs writes into a zeroed byte per position (empty documents write the same byte again)
+__global__ void __launch_bounds__(kBlock)
+k_rep_spans_mark(const uint64_t* __restrict__ starts, uint64_t ndocs, uint64_t n, uint8_t* __restrict__ mark)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < ndocs; i += stride) {
+        const uint64_t s = starts[i];
+        if (s < n) mark[s] = 1;
+    }
+}
+__global__ void __launch_bounds__(kBlock)
+k_rep_spans_flag(const uint32_t* __restrict__ M, const uint8_t* __restrict__ mark, uint64_t n, uint32_t* __restrict__ flag)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const bool cov = M[i] > i, prev = i > 0 && M[i - 1] > i - 1;
+        flag[i] = (cov && (!prev || (mark && mark[i]))) ? 1u : 0u;
+    }
+}
+// P = the exclusive scan of the begin flags: a begin at i is span P[i]; a covered byte that ends a run ends span P[i + 1] - 1
+__global__ void __launch_bounds__(kBlock)
+k_rep_spans_emit(const uint32_t* __restrict__ M, const uint8_t* __restrict__ mark, const uint32_t* __restrict__ P, uint64_t n,
+                 uint32_t* __restrict__ begin, uint32_t* __restrict__ end, uint64_t capacity)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        if (!(M[i] > i)) continue;
+        const uint32_t k0 = P[i], k1 = P[i + 1];
+        if (k1 != k0 && k0 < capacity) begin[k0] = (uint32_t)i;
+        const bool last = i + 1 == n || !(M[i + 1] > i + 1) || (mark && mark[i + 1]);
+        if (last && (uint64_t)(k1 - 1) < capacity) end[k1 - 1] = (uint32_t)(i + 1);
+    }
+}
+
+// [bad flag | prefix maxima n | flags / their scan n + 1 | scan partials | document-start marks n + 1 bytes]
+struct RepSpansWs {
+    uint32_t *bad, *M, *P, *part;
+    uint8_t* mark;
+};
+template <class A> static void rep_spans_carve(A& a, uint64_t n, RepSpansWs* w)
+{
+    w->bad = a.template take<uint32_t>(64);
+    w->M = a.template take<uint32_t>(n);
+    w->P = a.template take<uint32_t>(n + 1);
+    w->part = a.template take<uint32_t>(kMaxGrid + 64);
+    w->mark = a.template take<uint8_t>(n + 1);
+}
+uint64_t repeat_spans_workspace_bytes(uint64_t n)
+{
+    GsaSizer z;
+    RepSpansWs w;
+    rep_spans_carve(z, n, &w);
+    return z.used;
+}
+int repeat_spans_dev(const uint32_t* d_rep, uint64_t n, uint32_t min_len, const uint64_t* d_starts, uint64_t ndocs, uint32_t* d_begin,
+                     uint32_t* d_end, uint64_t capacity, uint64_t* count_out, void* ws, uint64_t ws_bytes, hipStream_t st)
+{
+    if (!count_out || min_len == 0) return SFX_ERR_ARG;
+    *count_out = 0;
+    if (n > 0xFFFFFFFFull || ndocs > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!d_rep || (capacity && (!d_begin || !d_end)) || (d_starts && ndocs == 0)) return SFX_ERR_ARG;
+    if (!ws || ws_bytes < repeat_spans_workspace_bytes(n)) return SFX_ERR_WORKSPACE;
+    Arena a(ws, ws_bytes);
+    RepSpansWs w;
+    rep_spans_carve(a, n, &w);
+    if (a.overflow) return SFX_ERR_INTERNAL;
+    const uint8_t* mark = nullptr;
+    if (d_starts) {
+        bool bad = false;
+        SFX_TRY(gsa_check_docs(d_starts, ndocs, n, w.bad, st, &bad));
+        if (bad) return SFX_ERR_ARG;
+        SFX_HIP(hipMemsetAsync(w.mark, 0, n + 1, st));
+        const unsigned dgrid = (unsigned)dmin<uint64_t>((ndocs + kBlock - 1) / kBlock, kMaxGrid);
+        SFX_LAUNCH("rep_spans_mark", (double)ndocs * 9, k_rep_spans_mark, dgrid, kBlock, st, d_starts, ndocs, n, w.mark);
+        mark = w.mark;
+    }
+    const unsigned nb = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, dmin<unsigned>(kMaxGrid, grid_cap()));
+    const uint64_t chunk = (n + nb - 1) / nb;
+    SFX_LAUNCH("rep_spans_max", (double)n * 4, k_rep_spans_max_count, nb, kBlock, st, d_rep, n, min_len, chunk, w.part);
+    SFX_LAUNCH("rep_spans_max", (double)nb * 8, k_rep_spans_max_top, 1, kBlock, st, w.part, nb);
+    SFX_LAUNCH("rep_spans_max", (double)n * 8, k_rep_spans_max_apply, nb, kBlock, st, d_rep, n, min_len, chunk, (const uint32_t*)w.part, w.M);
+    const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
+    SFX_LAUNCH("rep_spans_flag", (double)n * (mark ? 9 : 8), k_rep_spans_flag, grid, kBlock, st, (const uint32_t*)w.M, mark, n, w.P);
+    SFX_TRY(gsa_scan<uint32_t>(w.P, n, w.P, w.part, st));
+    SFX_LAUNCH("rep_spans", (double)n * (mark ? 9 : 8), k_rep_spans_emit, grid, kBlock, st, (const uint32_t*)w.M, mark, (const uint32_t*)w.P,
+               n, d_begin, d_end, capacity);
+    uint32_t count = 0;
+    SFX_TRY(read_back(&count, w.P + n, sizeof(count), st));
+    *count_out = count;
     return SFX_OK;
 }
 

@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from ._lib import default_engine
+from ._lib import REP_SCOPES, default_engine
 
 
 def _on(t):
@@ -213,6 +213,82 @@ def build_gsa(text, doc_starts, out_sa=None, out_da=None, out_lcp=None, workspac
         eng.check(eng.lib.sfx_build_gsa_u32_dev(_p(text), n, _p(doc_starts), nd, _p(out_sa), _p(out_da), _p(out_lcp),
                                                 _p(workspace), workspace.numel(), _stream_ptr(text)), "sfx_build_gsa_u32_dev")
     return out_sa, out_da, out_lcp
+
+
+def _check_u32(t, name, n=None):
+    if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous 1-D int32 tensor (uint32 values in int32 storage)")
+    if n is not None and t.numel() != n:
+        raise ValueError(f"{name} must hold {n} entries")
+
+
+def repeat_lens_workspace(n, scope, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_repeat_lens_workspace_bytes(int(n), REP_SCOPES[scope])), dtype=torch.uint8, device=device)
+
+
+def repeat_lens(sa, lcp, scope="any", da=None, want_src=False, workspace=None, engine=None):
+    """Repeat lengths from a suffix array and its LCP array (uint32 in int32 storage, on one device): rep[p] = the
+    longest common prefix of the suffix at text position p with any other suffix (scope "any"), any suffix at an
+    earlier position ("earlier": the LPF array) or any suffix of another document ("other_doc": needs da, and the
+    arrays of build_gsa).  -> rep, or (rep, src) with want_src: src[p] = a position attaining rep[p], 0xFFFFFFFF
+    where rep[p] == 0.  See include/suffix_hip.h."""
+    eng = engine or default_engine()
+    if scope not in REP_SCOPES:
+        raise ValueError(f"scope must be one of {sorted(REP_SCOPES)}")
+    n = sa.numel()
+    _check_u32(sa, "sa")
+    _check_u32(lcp, "lcp", n)
+    if scope == "other_doc":
+        if da is None:
+            raise ValueError('scope "other_doc" needs the document array da')
+        _check_u32(da, "da", n)
+    else:
+        da = None
+    for t in (lcp, da):
+        if t is not None and t.device != sa.device:
+            raise ValueError(f"all arrays must be on one device ({sa.device})")
+    if sa.is_cuda:
+        eng.require_device()
+    rep = torch.empty(n, dtype=torch.int32, device=sa.device)
+    src = torch.empty(n, dtype=torch.int32, device=sa.device) if want_src else None
+    if workspace is None:
+        workspace = repeat_lens_workspace(n, scope, sa.device, eng)
+    with _on(sa):
+        eng.check(eng.lib.sfx_repeat_lens_dev(_p(sa), _p(lcp), _p(da), n, REP_SCOPES[scope], _p(rep), _p(src), _p(workspace),
+                                              workspace.numel(), _stream_ptr(sa)), "sfx_repeat_lens_dev")
+    return (rep, src) if want_src else rep
+
+
+def repeat_spans(rep, min_len, doc_starts=None, engine=None):
+    """The maximal runs of bytes covered by a repeat of at least min_len bytes (rep from repeat_lens), split at every
+    document start when doc_starts (int64, on rep's device) is given: -> an (k, 2) int32 tensor of [begin, end) rows in
+    ascending order."""
+    eng = engine or default_engine()
+    _check_u32(rep, "rep")
+    min_len = int(min_len)
+    if min_len < 1 or min_len > 0xFFFFFFFF:
+        raise ValueError("min_len must be in 1 .. 2^32 - 1")
+    nd = 0
+    if doc_starts is not None:
+        if doc_starts.dtype != torch.int64 or doc_starts.dim() != 1 or not doc_starts.is_contiguous():
+            raise TypeError("doc_starts must be a contiguous 1-D int64 tensor")
+        if doc_starts.device != rep.device:
+            raise ValueError(f"doc_starts must be on rep's device ({rep.device})")
+        nd = doc_starts.numel()
+    n = rep.numel()
+    if rep.is_cuda:
+        eng.require_device()
+    cap = n // min_len + 1                                   # every run is at least min_len long
+    begin = torch.empty(cap, dtype=torch.int32, device=rep.device)
+    end = torch.empty(cap, dtype=torch.int32, device=rep.device)
+    ws = torch.empty(int(eng.lib.sfx_repeat_spans_workspace_bytes(n)), dtype=torch.uint8, device=rep.device)
+    count = ctypes.c_uint64(0)
+    with _on(rep):
+        eng.check(eng.lib.sfx_repeat_spans_dev(_p(rep), n, min_len, _p(doc_starts), nd, _p(begin), _p(end), cap, ctypes.byref(count),
+                                               _p(ws), ws.numel(), _stream_ptr(rep)), "sfx_repeat_spans_dev")
+    k = int(count.value)
+    return torch.stack((begin[:k], end[:k]), dim=1)
 
 
 class GeneralizedDeviceIndex:

@@ -10,6 +10,8 @@ no match spans two documents.
     lcp_lens()       common prefix of neighbouring truncated suffixes (0 first)
     positions(q)     [(doc, offset)] of every occurrence of q, in table order
     documents(q)     sorted distinct documents containing q; document_frequency(q) = their number
+    repeat_lens(scope)            longest repeat starting at every position: anywhere, earlier, or in another document
+    repeated_spans(min_len, ...)  [(document, begin_offset, end_offset)] of the bytes inside such repeats
 
 Construction and queries run on the GPU through the C ABI (sfx_build_gsa_u32, sfx_gindex_*); there is no CPU
 path except `new_naive`, the definition itself.
@@ -19,7 +21,7 @@ import ctypes
 import numpy as np
 
 from ._lib import default_engine
-from .table import _as_bytes, _ptr
+from .table import _as_bytes, _ptr, _repeat_lens, _repeat_spans
 
 _NONE = 0xFFFFFFFF
 
@@ -205,3 +207,18 @@ class GeneralizedSuffixTable:
 
     def document_frequency(self, query):
         return int(self.document_frequency_batch([query])[0])
+
+    # -- repeats --------------------------------------------------------------------------------
+    def repeat_lens(self, scope="any", with_source=False):
+        """rep[p] (indexed by text position doc_starts[i] + offset) = the longest common prefix of the truncated suffix
+        at p with any other one (scope "any"), any at an earlier position ("earlier") or any of ANOTHER document
+        ("other_doc").  with_source: -> (rep, src), src[p] = a position attaining rep[p], 0xFFFFFFFF where rep[p] == 0."""
+        return _repeat_lens(self._eng, self._table, self._lcp, self._da, scope, with_source)
+
+    def repeated_spans(self, min_len, scope="any"):
+        """[(document, begin_offset, end_offset)] in ascending order: the maximal runs of bytes inside a repeat of at
+        least min_len bytes; no run spans two documents."""
+        b, e = _repeat_spans(self._eng, self.repeat_lens(scope), min_len, self._starts)
+        d = np.searchsorted(self._starts, b, side="right").astype(np.int64) - 1
+        s = self._starts[d].astype(np.int64) if b.size else np.zeros(0, dtype=np.int64)
+        return list(zip(d.tolist(), (b.astype(np.int64) - s).tolist(), (e.astype(np.int64) - s).tolist()))

@@ -16,6 +16,7 @@ Same method names, argument meaning and error behaviour as the Rust API:
     .positions(q)                     :223   .positions(q)
     .any_position(q)                  :279   .any_position(q)
     (none)                                   .positions_batch(qs) / .contains_batch(qs)
+    (none)                                   .repeat_lens(scope) / .repeated_spans(min_len, scope)
 
 Text is indexed by BYTES (every UTF-8 byte offset has a suffix, :29-31 of the
 crate docs and :379); `str` input is encoded as UTF-8.  Construction, LCP and
@@ -25,7 +26,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import default_engine
+from ._lib import REP_SCOPES, default_engine
 
 _NONE = 0xFFFFFFFF
 
@@ -42,6 +43,40 @@ def _as_bytes(x):
 
 def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data if a.size else 0)
+
+
+def _repeat_lens(eng, table, lcp, da, scope, with_source):
+    """sfx_repeat_lens_u32 on host arrays -> rep, or (rep, src)."""
+    if scope not in REP_SCOPES or (scope == "other_doc" and da is None):
+        raise ValueError(f"unknown scope {scope!r}")
+    n = int(table.size)
+    rep = np.zeros(n, dtype=np.uint32)
+    src = np.full(n, _NONE, dtype=np.uint32) if with_source else None
+    if n:
+        eng.require_device()
+        eng.check(eng.lib.sfx_repeat_lens_u32(_ptr(table), _ptr(lcp), _ptr(da) if scope == "other_doc" else None, n,
+                                              REP_SCOPES[scope], _ptr(rep), _ptr(src) if with_source else None),
+                  "sfx_repeat_lens_u32")
+    return (rep, src) if with_source else rep
+
+
+def _repeat_spans(eng, rep, min_len, starts):
+    """sfx_repeat_spans_u32 on host arrays -> (begin, end) uint32 arrays."""
+    min_len = int(min_len)
+    if min_len < 1 or min_len > 0xFFFFFFFF:
+        raise ValueError("min_len must be in 1 .. 2^32 - 1")
+    n = int(rep.size)
+    cap = n // min_len + 1
+    begin = np.zeros(cap, dtype=np.uint32)
+    end = np.zeros(cap, dtype=np.uint32)
+    count = ctypes.c_uint64(0)
+    if n:
+        eng.require_device()
+        eng.check(eng.lib.sfx_repeat_spans_u32(_ptr(rep), n, min_len, _ptr(starts) if starts is not None else None,
+                                               starts.size if starts is not None else 0, _ptr(begin), _ptr(end), cap,
+                                               ctypes.byref(count)), "sfx_repeat_spans_u32")
+    k = int(count.value)
+    return begin[:k], end[:k]
 
 
 class SuffixTable:
@@ -209,6 +244,22 @@ class SuffixTable:
 
     def contains(self, query):
         return self.any_position(query) is not None                  # :197-199
+
+    # -- repeats --------------------------------------------------------------------------------
+    def repeat_lens(self, scope="any", with_source=False):
+        """rep[p] = the longest common prefix of the suffix at byte p with any other suffix (scope "any") or with any
+        suffix that starts earlier ("earlier": the longest-previous-factor array) -- uint32, indexed by text position.
+        with_source: -> (rep, src), src[p] = a position that attains rep[p] (which one is arbitrary), 0xFFFFFFFF where
+        rep[p] == 0."""
+        if scope not in ("any", "earlier"):
+            raise ValueError('scope must be "any" or "earlier"')
+        return _repeat_lens(self._eng, self._table, self.lcp_lens(), None, scope, with_source)
+
+    def repeated_spans(self, min_len, scope="any"):
+        """[(begin, end)] in ascending order: the maximal runs of bytes that lie inside a repeat of at least min_len
+        bytes (scope as for repeat_lens; "earlier" keeps the first copy of everything out of the report)."""
+        b, e = _repeat_spans(self._eng, self.repeat_lens(scope), min_len, None)
+        return list(zip(b.tolist(), e.tolist()))
 
     def __repr__(self):                                              # Debug, :296-312
         lines = ["", "-----------------------------------------", "SUFFIX TABLE",

@@ -3,12 +3,15 @@
 // over the MI355X engine's C++ host mirror (include/suffix_table.hpp -> libsuffix_hip.so),
 // extended into the large-file driver SURVEY.md 8(f) asks for:
 //
-//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--time]
+//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--time]
 //
 //   --dump PREFIX   write PREFIX.sa (and PREFIX.lcp with --lcp) as raw little-endian u32
 //                   arrays -- the on-disk form SuffixTable::from_parts (:111-119) reloads
 //   --load PREFIX   skip construction: from_parts(text, PREFIX.sa)
 //   --query Q       positions(Q) (:223-259): prints count and the first few positions
+//   --repeats L     one "begin end" line per maximal run of bytes that lie inside a repeat of at least L bytes;
+//                   with --earlier only repeats of something EARLIER in the file count (the first copy of everything
+//                   stays out of the report: what a deduplication would keep)
 //   --time          wall-clock milliseconds of construction / LCP (host pointers, i.e.
 //                   including the PCIe copies: the device-resident rate is bench.py's)
 //
@@ -16,6 +19,7 @@
 // reference panics in those places, :380 / :117).
 #include <chrono>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -55,7 +59,8 @@ int main(int argc, char** argv)
 {
     std::string file, dump, load;
     std::vector<std::string> queries;
-    bool want_lcp = false, timing = false;
+    bool want_lcp = false, timing = false, earlier = false;
+    long long repeats = -1;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto need = [&](const char* opt) -> const char* {
@@ -67,11 +72,16 @@ int main(int argc, char** argv)
         else if (a == "--dump") dump = need("--dump");
         else if (a == "--load") load = need("--load");
         else if (a == "--query") queries.push_back(need("--query"));
+        else if (a == "--earlier") earlier = true;
+        else if (a == "--repeats") {
+            repeats = atoll(need("--repeats"));
+            if (repeats < 1 || repeats > 0xFFFFFFFFll) { fprintf(stderr, "--repeats needs a length of at least 1\n"); return 1; }
+        }
         else if (!a.empty() && a[0] == '-') { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
         else file = a;
     }
     if (file.empty()) {
-        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--time]\n");
+        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--time]\n");
         return 1;
     }
     std::string text;
@@ -113,6 +123,12 @@ int main(int argc, char** argv)
                 if (e > s) std::cout << (e - s > 8 ? ", ...]" : "]");
                 std::cout << "\n";
             }
+        }
+        if (repeats > 0) {
+            t0 = std::chrono::steady_clock::now();
+            const auto spans = st.repeated_spans((uint32_t)repeats, earlier ? SFX_REP_EARLIER : SFX_REP_ANY);
+            if (timing) std::cout << "repeats ms: " << ms_since(t0) << "\n";
+            for (const auto& be : spans) std::cout << be.first << " " << be.second << "\n";
         }
     } catch (const std::exception& ex) {
         fprintf(stderr, "suffix-array: %s\n", ex.what());
