@@ -16,7 +16,24 @@
  *    outputs left in HBM) plus a caller-provided device workspace; the others
  *    take HOST pointers and stage through HBM themselves;
  *  - re-entrant: no global mutable state except the optional profiler.
+ *
+ * Alignment of the DEVICE pointers of the "*_dev" entry points (checked on the host before anything is
+ * launched; a pointer that does not meet it is SFX_ERR_ARG and nothing is read or written):
+ *  - text and query bytes (const uint8_t*), d_found, the 256 scratch bytes of sfx_pack_text_dev: ANY address.
+ *    The kernels take their 16-byte loads only from a 16-byte boundary on and read the bytes in front one by one;
+ *  - uint32_t arrays (suffix array, LCP, DA, rep / src, lb / rb / node / parent / leaf_parent, begin / end, the
+ *    query outputs, the packed words, slices of any of them): 4 bytes, the element's own alignment, is enough.
+ *    An array that also sits on a 16-byte boundary is read and written 16 bytes at a time where that pays;
+ *  - uint64_t arrays (d_qoff, d_doc_starts, d_bins*, d_global_byte_bins256, the widened table): 8 bytes;
+ *  - workspaces: SFX_WORKSPACE_ALIGN bytes.  The engine carves a workspace at 256-byte steps FROM ITS BASE and
+ *    uses the pieces with loads and stores of up to 16 bytes and with 64-bit atomics, so the base's alignment
+ *    is every piece's.  hipMalloc, malloc and every tensor allocator meet it.  A workspace that is long
+ *    enough but misaligned is SFX_ERR_ARG; one that is too short (or NULL) is SFX_ERR_WORKSPACE wherever it
+ *    lies.  A workspace may hold anything on entry: the engine clears what it needs cleared.
+ * Everything a call queues goes to the caller's `stream` and to no other; outputs are complete when the work
+ * queued on it is (entry points that read a result back -- documented at each -- synchronise that stream).
  */
+#define SFX_WORKSPACE_ALIGN 16
 #ifndef SUFFIX_HIP_H
 #define SUFFIX_HIP_H
 #include <stdint.h>

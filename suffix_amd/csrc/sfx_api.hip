@@ -186,6 +186,28 @@ static int check_device()
     return SFX_OK;
 }
 
+// ---- the alignment contract of the *_dev entry points (include/suffix_hip.h) --------------------
+// Checked on the host before anything is launched.  NULL passes: what NULL means is each entry point's own business.
+// What the kernels do on caller pointers beyond element-wide accesses, and why the contract covers it:
+//  - text / query bytes: 16-byte loads only behind a test of the address (k_byte_hist's head / vector / tail split,
+//    k_byte_presence, k_bigram_hist, k_key_hist_raw's vec_ok, k_tiny_sa's LDS fill; prepare_text picks k_pack_text_pow2 only
+//    for a 16-byte aligned text) -- and the 8-byte loads at byte addresses of extend_match and the query comparisons, plain
+//    global loads that the hardware serves from any address and that every GPU run has always relied on;
+//  - uint32_t arrays: the fused LCP moves d_lcp 16 bytes at a time (k_groups_reduce writes it, k_lcp_pending reads it), so
+//    build_sa_lcp_u32_dev fuses only into an array on a 16-byte boundary and otherwise runs the separate LCP routine, which
+//    goes entry by entry; k_groups_apply reads the table 16 bytes at a time behind a test of its address;
+//  - uint64_t arrays and workspaces see 64-bit atomics: 8 / SFX_WORKSPACE_ALIGN bytes are required, never assumed.
+template <class... P> static bool aligned_to(uintptr_t a, P... p)
+{
+    return ((... | reinterpret_cast<uintptr_t>(static_cast<const void*>(p))) & (a - 1)) == 0;
+}
+#define SFX_NEED_U32(...) do { if (!::sfx::aligned_to(4, __VA_ARGS__)) return SFX_ERR_ARG; } while (0)
+#define SFX_NEED_U64(...) do { if (!::sfx::aligned_to(8, __VA_ARGS__)) return SFX_ERR_ARG; } while (0)
+// a workspace that is large enough but off the boundary is an argument error; a short or missing one stays
+// SFX_ERR_WORKSPACE wherever it lies (the entry point's own check)
+#define SFX_NEED_WS(p, have, need) \
+    do { if ((p) && (have) >= (need) && !::sfx::aligned_to(SFX_WORKSPACE_ALIGN, p)) return SFX_ERR_ARG; } while (0)
+
 }  // namespace sfx
 
 using namespace sfx;
@@ -294,6 +316,8 @@ uint64_t sfx_sa_workspace_bytes(uint64_t n) { return sa_workspace_bytes(n); }
 int sfx_build_sa_u32_dev(const uint8_t* d_text, uint64_t n, uint32_t* d_sa, void* d_workspace,
                          uint64_t workspace_bytes, void* stream)
 {
+    SFX_NEED_U32(d_sa);
+    SFX_NEED_WS(d_workspace, workspace_bytes, sa_workspace_bytes(n));
     return build_sa_u32_dev(d_text, n, d_sa, d_workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -349,6 +373,8 @@ uint64_t sfx_lcp_workspace_bytes(uint64_t n) { return lcp_workspace_bytes(n); }
 int sfx_build_lcp_u32_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t* d_lcp,
                           void* d_workspace, uint64_t workspace_bytes, void* stream)
 {
+    SFX_NEED_U32(d_sa, d_lcp);
+    SFX_NEED_WS(d_workspace, workspace_bytes, lcp_workspace_bytes(n));
     return build_lcp_u32_dev(d_text, n, d_sa, d_lcp, d_workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -381,6 +407,8 @@ uint64_t sfx_sa_lcp_workspace_bytes(uint64_t n) { return sa_lcp_workspace_bytes(
 int sfx_build_sa_lcp_u32_dev(const uint8_t* d_text, uint64_t n, uint32_t* d_sa, uint32_t* d_lcp, void* d_workspace,
                              uint64_t workspace_bytes, void* stream)
 {
+    SFX_NEED_U32(d_sa, d_lcp);
+    SFX_NEED_WS(d_workspace, workspace_bytes, sa_lcp_workspace_bytes(n));
     return build_sa_lcp_u32_dev(d_text, n, d_sa, d_lcp, d_workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -457,6 +485,7 @@ int sfx_index_create(const uint8_t* text, uint64_t n, const uint32_t* sa, sfx_in
 // unchanged for the life of the index); builds only the bucket directory.
 int sfx_index_create_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, void* stream, sfx_index** out)
 {
+    SFX_NEED_U32(d_sa);
     if (!out) return SFX_ERR_ARG;
     *out = nullptr;
     if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
@@ -476,6 +505,8 @@ int sfx_index_create_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa
 int sfx_index_query_dev(const sfx_index* ix, const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq,
                         uint32_t* d_start, uint32_t* d_end, uint8_t* d_found, uint32_t* d_any, void* stream)
 {
+    SFX_NEED_U64(d_qoff);
+    SFX_NEED_U32(d_start, d_end, d_any);
     if (!ix) return SFX_ERR_ARG;
     if (ix->n == 0 || !ix->d_dir)
         return query_batch_dev(ix->d_text, ix->n, ix->d_sa, ix->n, d_qbytes, d_qoff, nq, d_start, d_end, d_found, d_any,
@@ -546,6 +577,8 @@ int sfx_query_batch_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
                         uint32_t* d_start, uint32_t* d_end, uint8_t* d_found, uint32_t* d_any,
                         void* stream)
 {
+    SFX_NEED_U64(d_qoff);
+    SFX_NEED_U32(d_sa, d_start, d_end, d_any);
     return query_batch_dev(d_text, n, d_sa, n, d_qbytes, d_qoff, nq, d_start, d_end, d_found, d_any,
                            (hipStream_t)stream);
 }
@@ -554,16 +587,21 @@ int sfx_query_batch_range_dev(const uint8_t* d_text, uint64_t n, const uint32_t*
                               uint32_t* d_start, uint32_t* d_end, uint8_t* d_found, uint32_t* d_any,
                               void* stream)
 {
+    SFX_NEED_U64(d_qoff);
+    SFX_NEED_U32(d_sa_part, d_start, d_end, d_any);
     return query_batch_dev(d_text, n, d_sa_part, count, d_qbytes, d_qoff, nq, d_start, d_end, d_found, d_any,
                            (hipStream_t)stream);
 }
 int sfx_build_lcp_range_u32_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa_part, uint64_t count,
                                 uint32_t prev_suffix, uint32_t* d_lcp_part, void* stream)
 {
+    SFX_NEED_U32(d_sa_part, d_lcp_part);
     return build_lcp_range_u32_dev(d_text, n, d_sa_part, count, prev_suffix, d_lcp_part, (hipStream_t)stream);
 }
 int sfx_widen_u32_to_u64_dev(const uint32_t* d_in, uint64_t count, uint64_t* d_out, void* stream)
 {
+    SFX_NEED_U32(d_in);
+    SFX_NEED_U64(d_out);
     return widen_u32_to_u64_dev(d_in, count, d_out, (hipStream_t)stream);
 }
 
@@ -614,12 +652,16 @@ int sfx_lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uin
                           uint32_t* d_parent, uint32_t* d_leaf_parent, void* d_workspace, uint64_t workspace_bytes,
                           void* stream)
 {
+    SFX_NEED_U32(d_lcp, d_lb, d_rb, d_node, d_parent, d_leaf_parent);
+    SFX_NEED_WS(d_workspace, workspace_bytes, lcp_intervals_workspace_bytes(n));
     return lcp_intervals_dev(d_lcp, n, d_lb, d_rb, d_node, d_parent, d_leaf_parent, d_workspace, workspace_bytes,
                              (hipStream_t)stream);
 }
 int sfx_doc_lookup_dev(const uint32_t* d_positions, uint64_t count, const uint64_t* d_doc_starts, uint64_t ndocs,
                        uint32_t* d_doc, uint32_t* d_offset, void* stream)
 {
+    SFX_NEED_U64(d_doc_starts);
+    SFX_NEED_U32(d_positions, d_doc, d_offset);
     return doc_lookup_dev(d_positions, count, d_doc_starts, ndocs, d_doc, d_offset, (hipStream_t)stream);
 }
 
@@ -632,6 +674,9 @@ uint64_t sfx_gsa_workspace_bytes(uint64_t n, uint64_t ndocs)
 int sfx_build_gsa_u32_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_starts, uint64_t ndocs, uint32_t* d_sa,
                           uint32_t* d_da, uint32_t* d_lcp, void* d_workspace, uint64_t workspace_bytes, void* stream)
 {
+    SFX_NEED_U64(d_doc_starts);
+    SFX_NEED_U32(d_sa, d_da, d_lcp);
+    SFX_NEED_WS(d_workspace, workspace_bytes, gsa_workspace_bytes(n));
     return gsa_build_dev(d_text, n, d_doc_starts, ndocs, d_sa, d_da, d_lcp, d_workspace, workspace_bytes, (hipStream_t)stream);
 }
 int sfx_build_gsa_u32(const uint8_t* text, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs, uint32_t* sa_out,
@@ -667,6 +712,8 @@ uint64_t sfx_repeat_lens_workspace_bytes(uint64_t n, int scope) { return repeat_
 int sfx_repeat_lens_dev(const uint32_t* d_sa, const uint32_t* d_lcp, const uint32_t* d_da, uint64_t n, int scope, uint32_t* d_rep,
                         uint32_t* d_src, void* d_workspace, uint64_t workspace_bytes, void* stream)
 {
+    SFX_NEED_U32(d_sa, d_lcp, d_da, d_rep, d_src);
+    SFX_NEED_WS(d_workspace, workspace_bytes, repeat_lens_workspace_bytes(n, scope));
     return repeat_lens_dev(d_sa, d_lcp, d_da, n, scope, d_rep, d_src, d_workspace, workspace_bytes, (hipStream_t)stream);
 }
 uint64_t sfx_repeat_spans_workspace_bytes(uint64_t n) { return repeat_spans_workspace_bytes(n); }
@@ -674,6 +721,9 @@ int sfx_repeat_spans_dev(const uint32_t* d_rep, uint64_t n, uint32_t min_len, co
                          uint32_t* d_begin, uint32_t* d_end, uint64_t capacity, uint64_t* count_out, void* d_workspace,
                          uint64_t workspace_bytes, void* stream)
 {
+    SFX_NEED_U64(d_doc_starts);
+    SFX_NEED_U32(d_rep, d_begin, d_end);
+    SFX_NEED_WS(d_workspace, workspace_bytes, repeat_spans_workspace_bytes(n));
     return repeat_spans_dev(d_rep, n, min_len, d_doc_starts, ndocs, d_begin, d_end, capacity, count_out, d_workspace, workspace_bytes,
                             (hipStream_t)stream);
 }
@@ -742,6 +792,8 @@ int sfx_repeat_spans_u32(const uint32_t* rep, uint64_t n, uint32_t min_len, cons
 int sfx_gindex_create_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_starts, uint64_t ndocs, const uint32_t* d_sa,
                           const uint32_t* d_da, void* stream, sfx_gindex** out)
 {
+    SFX_NEED_U64(d_doc_starts);
+    SFX_NEED_U32(d_sa, d_da);
     if (!out) return SFX_ERR_ARG;
     *out = nullptr;
     if (n > 0xFFFFFFFFull || ndocs > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
@@ -813,6 +865,8 @@ int sfx_gindex_create(const uint8_t* text, uint64_t n, const uint64_t* doc_start
 int sfx_gindex_query_dev(const sfx_gindex* gx, const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq, uint32_t* d_start,
                          uint32_t* d_end, uint8_t* d_found, uint32_t* d_any, uint32_t* d_ndocs, void* stream)
 {
+    SFX_NEED_U64(d_qoff);
+    SFX_NEED_U32(d_start, d_end, d_any, d_ndocs);
     if (!gx) return SFX_ERR_ARG;
     if (nq == 0) return SFX_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -888,12 +942,14 @@ void sfx_gindex_destroy(sfx_gindex* gx)
 int sfx_byte_histogram_dev(const uint8_t* d_text, uint64_t shard_begin, uint64_t shard_end,
                            uint64_t* d_bins256, void* stream)
 {
+    SFX_NEED_U64(d_bins256);
     return byte_histogram_dev(d_text, shard_begin, shard_end, d_bins256, (hipStream_t)stream);
 }
 int sfx_key_histogram_dev(const uint8_t* d_text, uint64_t n, uint64_t shard_begin,
                           uint64_t shard_end, const uint64_t* d_global_byte_bins256, int top_bits,
                           uint64_t* d_bins, void* stream)
 {
+    SFX_NEED_U64(d_global_byte_bins256, d_bins);
     return key_histogram_dev(d_text, n, shard_begin, shard_end, d_global_byte_bins256, top_bits,
                              d_bins, (hipStream_t)stream);
 }
@@ -904,6 +960,9 @@ int sfx_build_sa_range_u32_dev(const uint8_t* d_text, uint64_t n,
                                uint64_t* count_out, void* d_workspace, uint64_t workspace_bytes,
                                void* stream)
 {
+    SFX_NEED_U64(d_global_byte_bins256);
+    SFX_NEED_U32(d_sa_part);
+    SFX_NEED_WS(d_workspace, workspace_bytes, sa_range_workspace_bytes(n, capacity));
     return build_sa_range_u32_dev(d_text, n, d_global_byte_bins256, top_bits, bin_lo, bin_hi, capacity,
                                   d_sa_part, count_out, d_workspace, workspace_bytes,
                                   (hipStream_t)stream);
@@ -912,6 +971,8 @@ int sfx_build_sa_range_u32_dev(const uint8_t* d_text, uint64_t n,
 int sfx_pack_text_dev(const uint8_t* d_text, uint64_t count, const uint64_t* d_global_byte_bins256,
                       uint8_t* d_scratch256, uint32_t* d_words, uint64_t n_words, void* stream)
 {
+    SFX_NEED_U64(d_global_byte_bins256);
+    SFX_NEED_U32(d_words);
     return pack_text_dev(d_text, count, d_global_byte_bins256, d_scratch256, d_words, n_words, (hipStream_t)stream);
 }
 int sfx_build_sa_range_packed_u32_dev(const uint32_t* d_packed, uint64_t n,
@@ -920,6 +981,9 @@ int sfx_build_sa_range_packed_u32_dev(const uint32_t* d_packed, uint64_t n,
                                       uint64_t* count_out, void* d_workspace, uint64_t workspace_bytes,
                                       void* stream)
 {
+    SFX_NEED_U64(d_global_byte_bins256);
+    SFX_NEED_U32(d_packed, d_sa_part);
+    SFX_NEED_WS(d_workspace, workspace_bytes, sa_range_workspace_bytes(n, capacity));
     if (!d_packed) return SFX_ERR_ARG;
     return build_sa_range_u32_dev(nullptr, n, d_global_byte_bins256, top_bits, bin_lo, bin_hi, capacity, d_sa_part,
                                   count_out, d_workspace, workspace_bytes, (hipStream_t)stream, d_packed);

@@ -2704,8 +2704,10 @@ int build_sa_lcp_u32_dev(const uint8_t* d_text, uint64_t n, uint32_t* d_sa, uint
         return SFX_OK;
     }
     int cpk = 0;
-    // the lower-bound encoding needs the top bit of an LCP value
-    const bool fuse = n < 0x80000000ull;
+    // the lower-bound encoding needs the top bit of an LCP value; the fused route moves d_lcp 16 bytes at a time
+    // (k_groups_reduce writes it so, k_lcp_pending reads it so, at multiples of 8 entries) -- a caller's array that only has
+    // the 4-byte alignment include/suffix_hip.h asks for takes the separate LCP routine, which goes entry by entry
+    const bool fuse = n < 0x80000000ull && (reinterpret_cast<uintptr_t>(d_lcp) & 15u) == 0;
     bool fused = fuse;
     SFX_TRY(build_sa_impl(d_text, n, d_sa, ws, ws_bytes, st, fuse ? d_lcp : nullptr, &cpk, &fused));
     const sfx_build_stats stats = tls_build_stats();

@@ -364,6 +364,45 @@ def fused_lcp_short_suffix_ties(eng, orc):
             assert bad.size == 0, (wlen, k, bad[:4], got[bad[:4]], want[bad[:4]])
 
 
+def directory_texts(scale=1):
+    """The texts of directory_queries."""
+    return [_gen.dna(30000 * scale, seed=5).tobytes() + b"AAAA", _gen.english_like(20000 * scale).tobytes(),
+            _gen.utf8_mixed(20000 * scale).tobytes(), bytes(range(256)) * (8 * scale) + b"\x00\x00",
+            b"a" * 300, b"ab" * 200 + b"a", _gen.uniform_bytes(5000 * scale, 3, 9, base=65).tobytes() + b"AA",
+            # the 24-byte keys of the B+tree: runs of the padding bytes 0x00 / 0xFF, long shared prefixes
+            b"\xff" * 40 + b"\x00" * 40 + b"\xff" * 17 + b"\x00" * 9 + b"\xff" * 16 + b"\x00" * 25 + b"\xff" * 24,
+            (b"abcdefgh" * 40 + b"abcdefgx") * 5 + b"abcdefghabcdefgh",
+            _gen.english_like(3000).tobytes() * 4 + b"\x00" * 20,
+            # 1-bit symbols and n > 2^18: the directory key (17 symbols) is longer than the tree's, descents start at the root
+            _gen.uniform_bytes(270_000, 2, 4, base=97).tobytes()]
+
+
+def directory_query_list(text, rng, random_count=400):
+    """The fixed adversarial queries of one text of directory_queries (ends of the text, the padding bytes 0x00 / 0xFF in runs
+    of 8 / 16 / 17 / 24 / 25, queries over the end of the text), followed by `random_count` drawn from `rng`: substrings of
+    1 .. 89 bytes, some with the last byte changed, a byte appended, or 0x00 / 0xFF behind them."""
+    n = len(text)
+    qs = [b"", text[-1:], text[-2:], text[-3:], text[:1], b"\xfe\xfd", text[:40], b"A", b"AA", b"AAA", b"AAAA", b"AAAAA",
+          text[-8:], text[-9:], text[-16:], text[-17:], text[-16:] + b"\x00", text[-8:] + b"\x00", text[-5:] + b"\x00\x00",
+          b"\xff" * 8, b"\xff" * 16, b"\xff" * 17, b"\x00" * 8, b"\x00" * 16, b"\x00" * 17,
+          text[-24:], text[-25:], text[-24:] + b"\x00", text[-20:] + b"\x00\x00", b"\xff" * 24, b"\xff" * 25, b"\x00" * 24,
+          b"\x00" * 25, text[:24], text[:25], text[:23] + b"\xff", text[:16] + b"\x00" * 8, text[:16] + b"\xff" * 8]
+    for it in range(random_count):
+        a = int(rng.integers(0, n))
+        q = text[a:a + int(rng.integers(1, 14 if it < 200 else (40 if it < 340 else 90)))]
+        r = rng.random()
+        if r < 0.25:
+            q = q[:-1] + bytes([q[-1] ^ 0x55])
+        elif r < 0.35:
+            q = q + bytes([int(rng.integers(0, 256))])
+        elif r < 0.42:
+            q = q + b"\x00" * int(rng.integers(1, 4))
+        elif r < 0.47:
+            q = q + b"\xff"
+        qs.append(q)
+    return qs
+
+
 def directory_queries(eng, orc, device="cpu", scale=1):
     """The resident index with its bucket directory (sfx_index_create_dev / sfx_index_query_dev) against the
     undirected search and the oracle: queries shorter than, equal to and longer than the directory key,
@@ -372,36 +411,9 @@ def directory_queries(eng, orc, device="cpu", scale=1):
 
     from suffix_amd import device as sdev
     rng = np.random.default_rng(11)
-    texts = [_gen.dna(30000 * scale, seed=5).tobytes() + b"AAAA", _gen.english_like(20000 * scale).tobytes(),
-             _gen.utf8_mixed(20000 * scale).tobytes(), bytes(range(256)) * (8 * scale) + b"\x00\x00",
-             b"a" * 300, b"ab" * 200 + b"a", _gen.uniform_bytes(5000 * scale, 3, 9, base=65).tobytes() + b"AA",
-             # the 24-byte keys of the B+tree: runs of the padding bytes 0x00 / 0xFF, long shared prefixes
-             b"\xff" * 40 + b"\x00" * 40 + b"\xff" * 17 + b"\x00" * 9 + b"\xff" * 16 + b"\x00" * 25 + b"\xff" * 24,
-             (b"abcdefgh" * 40 + b"abcdefgx") * 5 + b"abcdefghabcdefgh",
-             _gen.english_like(3000).tobytes() * 4 + b"\x00" * 20,
-             # 1-bit symbols and n > 2^18: the directory key (17 symbols) is longer than the tree's, descents start at the root
-             _gen.uniform_bytes(270_000, 2, 4, base=97).tobytes()]
-    for text in texts:
-        n = len(text)
+    for text in directory_texts(scale):
         exp = orc.sais(text)
-        qs = [b"", text[-1:], text[-2:], text[-3:], text[:1], b"\xfe\xfd", text[:40], b"A", b"AA", b"AAA", b"AAAA", b"AAAAA",
-              text[-8:], text[-9:], text[-16:], text[-17:], text[-16:] + b"\x00", text[-8:] + b"\x00", text[-5:] + b"\x00\x00",
-              b"\xff" * 8, b"\xff" * 16, b"\xff" * 17, b"\x00" * 8, b"\x00" * 16, b"\x00" * 17,
-              text[-24:], text[-25:], text[-24:] + b"\x00", text[-20:] + b"\x00\x00", b"\xff" * 24, b"\xff" * 25, b"\x00" * 24,
-              b"\x00" * 25, text[:24], text[:25], text[:23] + b"\xff", text[:16] + b"\x00" * 8, text[:16] + b"\xff" * 8]
-        for it in range(400):
-            a = int(rng.integers(0, n))
-            q = text[a:a + int(rng.integers(1, 14 if it < 200 else (40 if it < 340 else 90)))]
-            r = rng.random()
-            if r < 0.25:
-                q = q[:-1] + bytes([q[-1] ^ 0x55])
-            elif r < 0.35:
-                q = q + bytes([int(rng.integers(0, 256))])
-            elif r < 0.42:
-                q = q + b"\x00" * int(rng.integers(1, 4))
-            elif r < 0.47:
-                q = q + b"\xff"
-            qs.append(q)
+        qs = directory_query_list(text, rng)
         off = np.zeros(len(qs) + 1, dtype=np.int64)
         off[1:] = np.cumsum([len(q) for q in qs])
         t = torch.frombuffer(bytearray(text), dtype=torch.uint8).to(device)
@@ -548,11 +560,13 @@ def suffix_tree_at_scale(eng, orc, text, device="cuda"):
     return int((ref["node"] == np.arange(len(text), dtype=np.uint32)).sum())          # internal nodes (ids = their own boundary)
 
 
-def range_slices(eng, orc, text, nranges, device="cpu", packed=False, top_bits=14, exp=None):
+def range_slices(eng, orc, text, nranges, device="cpu", packed=False, top_bits=14, exp=None, text_offset=0):
     """The range-partitioned build driven for `nranges` virtual ranks in one process: every
     range [lo, hi) of the planned key bins is built on its own and the slices must
     concatenate to the oracle's suffix array (`exp`, if the caller has it).  Many ranges make
     sparse tiles in the filter (direct stores), few make dense ones (LDS-compacted).
+    text_offset > 0: the text lies that many bytes behind the start of its allocation, so that the histograms, the pack and
+    the filter see a text that is not 16-byte aligned.
     Returns how many slices fell back to a whole-array build (SFX_ERR_NEEDS_RANKS)."""
     import ctypes
 
@@ -563,7 +577,8 @@ def range_slices(eng, orc, text, nranges, device="cpu", packed=False, top_bits=1
     if exp is None:
         exp = orc.sais(text)
     n = len(text)
-    t = torch.frombuffer(bytearray(text), dtype=torch.uint8).to(device)
+    t = torch.frombuffer(bytearray(b"\xa5" * text_offset + text), dtype=torch.uint8).to(device)[text_offset:]
+    assert text_offset == 0 or t.data_ptr() % 16 == text_offset % 16
     bb = torch.zeros(256, dtype=torch.int64, device=device)
     eng.check(eng.lib.sfx_byte_histogram_dev(_p(t), 0, n, _p(bb), None), "byte_hist")
     assert np.array_equal(bb.cpu().numpy(), np.bincount(np.frombuffer(text, dtype=np.uint8), minlength=256))
