@@ -163,6 +163,58 @@ uint64_t sfx_lcp_intervals_workspace_bytes(uint64_t n);
 int sfx_lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_t* d_rb, uint32_t* d_node,
                           uint32_t* d_parent, uint32_t* d_leaf_parent, void* d_workspace, uint64_t workspace_bytes,
                           void* stream);
+/* ---- suffix-tree node table with ordered children (suffix_tree/src/lib.rs:107-160, the `Node` interface) ------
+ * The same tree looking DOWN, for a plain table (sa, lcp of a text of n bytes; lcp[0] is not looked at).
+ *   Internal nodes  the lcp-intervals, the root [0, n-1] at depth 0 among them: m of them, with dense ids 0 .. m-1 in
+ *                   ascending order of their sfx_lcp_intervals_dev id (the order the reference's sweep creates them in;
+ *                   not preorder).  The root is node 0.
+ *   Terminals       the leaf of rank r under node v has the edge label text[sa[r] + depth(v) ..].  Where that is empty
+ *                   (n - sa[r] == depth(v)) the reference makes no child: the suffix is a TERMINAL of v itself
+ *                   (lib.rs:127-131).  A node has at most one, the suffix at its first rank; the root has none.
+ *                   T = the number of nodes that have one.
+ *   Children        of v, in rank order: its child intervals and the ranks directly under it whose label is not empty.
+ *                   Rank order is the order of the first bytes of their edge labels (distinct inside a node: at most 256
+ *                   children), the reference's BTreeMap<u8, _> order.  C = n - 1 + m - T children in all, C <= 2n - 1.
+ * Arrays (device pointers; NONE = UINT32_MAX):
+ *   node_lb, node_rb   m u32        rank range of node k
+ *   node_depth         m u32        its string depth (the reference's path_len)
+ *   node_parent        m u32        dense id of its parent, NONE for the root
+ *   node_terminal      m u32        text position of its terminal suffix, NONE if it has none
+ *   child_off          m + 1 u64    the children of node k are entries child_off[k] .. child_off[k + 1]; child_off[m] == C
+ *   child_lb           C u32        first rank of the child, strictly ascending inside a node; the child ends where the
+ *                                   next one begins, or at node_rb
+ *   child_node         C u32        dense id of the child if it is an internal node, NONE if it is the leaf of rank child_lb
+ *   child_byte         C u8         first byte of the child's edge label (any address); d_text and d_child_byte are both
+ *                                   given or both NULL
+ *   leaf_parent        n u32        dense id of the node the leaf of rank r is a child or the terminal of; may be NULL
+ * Every array is determined by (text, sa, lcp) alone: two calls give the same bytes.
+ * *nodes_out = m and *children_out = C (HOST pointers) are written on every SFX_OK.  If m > node_capacity or
+ * C > child_capacity no array is written and the call still returns SFX_OK: the caller compares and calls again with
+ * more room (capacities of 0 with NULL arrays is the sizing call; node_capacity = n and child_capacity = 2n always
+ * suffice).  The call SYNCHRONISES the stream once, to read m, C and the table check back, as sfx_repeat_lens_dev does;
+ * everything is queued on the caller's stream, and the workspace may hold anything on entry.
+ * n == 0 succeeds with m = C = 0; n == 1 is the root with one leaf child.
+ * SFX_ERR_ARG: a table entry >= n (checked on the device), exactly one of d_text / d_child_byte NULL, a NULL among the
+ * other arrays (leaf_parent excepted) when the capacities suffice; SFX_ERR_TOO_LARGE: n > u32::MAX.
+ * For ANY lcp contents and any table with entries < n nothing is read or written out of bounds; what the arrays hold
+ * for an lcp array that is not the table's is unspecified.
+ * Not covered: generalized tables (truncated suffixes give a node several terminals), suffix links, preorder numbers. */
+uint64_t sfx_suffix_tree_workspace_bytes(uint64_t n);
+int sfx_suffix_tree_dev(const uint8_t* d_text /* may be NULL */, const uint32_t* d_sa, const uint32_t* d_lcp, uint64_t n,
+                        uint64_t node_capacity, uint64_t child_capacity,
+                        uint32_t* d_node_lb, uint32_t* d_node_rb, uint32_t* d_node_depth, uint32_t* d_node_parent,
+                        uint32_t* d_node_terminal, uint64_t* d_child_off /* node_capacity + 1 */,
+                        uint32_t* d_child_lb, uint32_t* d_child_node, uint8_t* d_child_byte /* may be NULL */,
+                        uint32_t* d_leaf_parent /* may be NULL */,
+                        uint64_t* nodes_out /* host */, uint64_t* children_out /* host */,
+                        void* d_workspace, uint64_t workspace_bytes, void* stream);
+/* the same with host buffers, staged through HBM */
+int sfx_suffix_tree_u32(const uint8_t* text /* may be NULL */, const uint32_t* sa, const uint32_t* lcp, uint64_t n,
+                        uint64_t node_capacity, uint64_t child_capacity,
+                        uint32_t* node_lb, uint32_t* node_rb, uint32_t* node_depth, uint32_t* node_parent,
+                        uint32_t* node_terminal, uint64_t* child_off, uint32_t* child_lb, uint32_t* child_node,
+                        uint8_t* child_byte /* may be NULL */, uint32_t* leaf_parent /* may be NULL */,
+                        uint64_t* nodes_out, uint64_t* children_out);
 /* ---- generalized suffix array (README.md:60-74): documents concatenated with a separator byte into one
  * text, one SuffixTable over it; a match position is mapped back to (document, offset) by a binary search
  * over the sorted document start offsets.  doc / offset may be NULL to skip. */

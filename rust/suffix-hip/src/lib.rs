@@ -50,6 +50,22 @@ extern "C" {
                            start_out: *mut u32, end_out: *mut u32) -> c_int;
     fn sfx_contains_batch(ix: *const SfxIndex, qbytes: *const u8, qoff: *const u64, nq: u64,
                           found_out: *mut u8, any_out: *mut u32) -> c_int;
+    // suffix_tree's node table with ordered children (children(), preorder(), leaves(), suffix_indices() read it)
+    #[allow(dead_code)]
+    fn sfx_suffix_tree_u32(text: *const u8, sa: *const u32, lcp: *const u32, n: u64, node_capacity: u64,
+                           child_capacity: u64, node_lb: *mut u32, node_rb: *mut u32, node_depth: *mut u32,
+                           node_parent: *mut u32, node_terminal: *mut u32, child_off: *mut u64, child_lb: *mut u32,
+                           child_node: *mut u32, child_byte: *mut u8, leaf_parent: *mut u32, nodes_out: *mut u64,
+                           children_out: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_suffix_tree_workspace_bytes(n: u64) -> u64;
+    #[allow(dead_code)]
+    fn sfx_suffix_tree_dev(d_text: *const u8, d_sa: *const u32, d_lcp: *const u32, n: u64, node_capacity: u64,
+                           child_capacity: u64, d_node_lb: *mut u32, d_node_rb: *mut u32, d_node_depth: *mut u32,
+                           d_node_parent: *mut u32, d_node_terminal: *mut u32, d_child_off: *mut u64,
+                           d_child_lb: *mut u32, d_child_node: *mut u32, d_child_byte: *mut u8,
+                           d_leaf_parent: *mut u32, nodes_out: *mut u64, children_out: *mut u64, ws: *mut c_void,
+                           ws_bytes: u64, stream: *mut c_void) -> c_int;
     // device-pointer variants (`*_dev`) take a hipStream_t as *mut c_void; omitted here.
     #[allow(dead_code)]
     fn sfx_build_sa_u32_dev(d_text: *const u8, n: u64, d_sa: *mut u32, ws: *mut c_void,

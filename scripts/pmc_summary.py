@@ -66,6 +66,8 @@ NAMES = [
     ("k_phi_scatter", "phi_scatter"), ("k_phi_pairs", "phi_pairs"), ("k_plcp", "plcp"),
     ("k_pyr_reduce", "tree_pyramid"), ("k_lcp_intervals_open", "tree_intervals_open"), ("k_lcp_intervals", "tree_intervals"),
     ("k_tree_parents", "tree_parents"), ("k_tree_leaves", "tree_leaves"), ("k_tree_level", "tree_level"),
+    ("k_tree_heads", "tree_heads"), ("k_tree_count", "tree_count"), ("k_tree_totals", "tree_totals"), ("k_tree_fill", "tree_fill"),
+    ("k_tree_order", "tree_order"),
     ("k_dir_mark", "dir_mark"), ("k_dir_block_min", "dir_block_min"), ("k_dir_scan_mins", "dir_scan_mins"), ("k_dir_fill", "dir_fill"),
     ("k_gsa_check_docs", "gsa_check_docs"), ("k_gsa_check_index", "gsa_check_index"), ("k_gsa_affected", "gsa_affected"),
     ("k_gsa_scan_count<", "gsa_scan"), ("k_gsa_scan_top<", "gsa_scan"), ("k_gsa_scan_apply<", "gsa_scan"), ("k_gsa_compact", "gsa_compact"),

@@ -69,6 +69,11 @@ ABI = [
     ("sfx_lcp_intervals_workspace_bytes", _u64, [_u64]),
     ("sfx_lcp_intervals_dev", _int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     ("sfx_doc_lookup_dev", _int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    ("sfx_suffix_tree_workspace_bytes", _u64, [_u64]),
+    ("sfx_suffix_tree_dev", _int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp, _u64, _vp]),
+    ("sfx_suffix_tree_u32", _int, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     ("sfx_gsa_workspace_bytes", _u64, [_u64, _u64]),
     ("sfx_build_gsa_u32_dev", _int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
     ("sfx_build_gsa_u32", _int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),

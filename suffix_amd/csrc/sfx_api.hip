@@ -665,6 +665,76 @@ int sfx_doc_lookup_dev(const uint32_t* d_positions, uint64_t count, const uint64
     return doc_lookup_dev(d_positions, count, d_doc_starts, ndocs, d_doc, d_offset, (hipStream_t)stream);
 }
 
+// ---- suffix-tree node table ---------------------------------------------------------------------------------
+uint64_t sfx_suffix_tree_workspace_bytes(uint64_t n) { return suffix_tree_workspace_bytes(n); }
+int sfx_suffix_tree_dev(const uint8_t* d_text, const uint32_t* d_sa, const uint32_t* d_lcp, uint64_t n, uint64_t node_capacity,
+                        uint64_t child_capacity, uint32_t* d_node_lb, uint32_t* d_node_rb, uint32_t* d_node_depth,
+                        uint32_t* d_node_parent, uint32_t* d_node_terminal, uint64_t* d_child_off, uint32_t* d_child_lb,
+                        uint32_t* d_child_node, uint8_t* d_child_byte, uint32_t* d_leaf_parent, uint64_t* nodes_out,
+                        uint64_t* children_out, void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    SFX_NEED_U64(d_child_off);
+    SFX_NEED_U32(d_sa, d_lcp, d_node_lb, d_node_rb, d_node_depth, d_node_parent, d_node_terminal, d_child_lb, d_child_node,
+                 d_leaf_parent);
+    SFX_NEED_WS(d_workspace, workspace_bytes, suffix_tree_workspace_bytes(n));
+    return suffix_tree_dev(d_text, d_sa, d_lcp, n, node_capacity, child_capacity, d_node_lb, d_node_rb, d_node_depth, d_node_parent,
+                           d_node_terminal, d_child_off, d_child_lb, d_child_node, d_child_byte, d_leaf_parent, nodes_out,
+                           children_out, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sfx_suffix_tree_u32(const uint8_t* text, const uint32_t* sa, const uint32_t* lcp, uint64_t n, uint64_t node_capacity,
+                        uint64_t child_capacity, uint32_t* node_lb, uint32_t* node_rb, uint32_t* node_depth, uint32_t* node_parent,
+                        uint32_t* node_terminal, uint64_t* child_off, uint32_t* child_lb, uint32_t* child_node, uint8_t* child_byte,
+                        uint32_t* leaf_parent, uint64_t* nodes_out, uint64_t* children_out)
+{
+    if (!nodes_out || !children_out) return SFX_ERR_ARG;
+    *nodes_out = 0;
+    *children_out = 0;
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if ((text == nullptr) != (child_byte == nullptr)) return SFX_ERR_ARG;
+    if (n == 0) return SFX_OK;
+    if (!sa || !lcp) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    if (node_capacity > n) node_capacity = n;                            // (no table is longer)
+    if (child_capacity > 2 * n) child_capacity = 2 * n;
+    const bool fill = node_lb && node_rb && node_depth && node_parent && node_terminal && child_off && child_lb && child_node;
+    DevBuf dt, ds, dl, dn[5], doff, dc[2], db, dp, dw;
+    const uint64_t wsb = suffix_tree_workspace_bytes(n), bytes = n * sizeof(uint32_t);
+    if (text) SFX_TRY(dt.alloc(n));
+    SFX_TRY(ds.alloc(bytes));
+    SFX_TRY(dl.alloc(bytes));
+    if (fill) {
+        for (DevBuf& b : dn) SFX_TRY(b.alloc(node_capacity * sizeof(uint32_t)));
+        SFX_TRY(doff.alloc((node_capacity + 1) * sizeof(uint64_t)));
+        for (DevBuf& b : dc) SFX_TRY(b.alloc(child_capacity * sizeof(uint32_t)));
+        if (child_byte) SFX_TRY(db.alloc(child_capacity));
+        if (leaf_parent) SFX_TRY(dp.alloc(bytes));
+    }
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    if (text) SFX_HIP(hipMemcpyAsync(dt.p, text, n, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(ds.p, sa, bytes, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dl.p, lcp, bytes, hipMemcpyHostToDevice, st));
+    SFX_TRY(suffix_tree_dev((const uint8_t*)dt.p, (const uint32_t*)ds.p, (const uint32_t*)dl.p, n, fill ? node_capacity : 0,
+                            fill ? child_capacity : 0, (uint32_t*)dn[0].p, (uint32_t*)dn[1].p, (uint32_t*)dn[2].p, (uint32_t*)dn[3].p,
+                            (uint32_t*)dn[4].p, (uint64_t*)doff.p, (uint32_t*)dc[0].p, (uint32_t*)dc[1].p, (uint8_t*)db.p,
+                            (uint32_t*)dp.p, nodes_out, children_out, dw.p, wsb, st));
+    const uint64_t m = *nodes_out, c = *children_out;
+    if (m > node_capacity || c > child_capacity) return SFX_OK;
+    if (!fill) return SFX_ERR_ARG;                                       // (room for everything, and nowhere to put it)
+    uint32_t* const node_out[5] = {node_lb, node_rb, node_depth, node_parent, node_terminal};
+    for (int i = 0; i < 5; i++) SFX_HIP(hipMemcpyAsync(node_out[i], dn[i].p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipMemcpyAsync(child_off, doff.p, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (c) {
+        SFX_HIP(hipMemcpyAsync(child_lb, dc[0].p, c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(child_node, dc[1].p, c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (child_byte) SFX_HIP(hipMemcpyAsync(child_byte, db.p, c, hipMemcpyDeviceToHost, st));
+    }
+    if (leaf_parent) SFX_HIP(hipMemcpyAsync(leaf_parent, dp.p, bytes, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+
 // ---- generalized suffix array over documents ------------------------------------------------------------
 uint64_t sfx_gsa_workspace_bytes(uint64_t n, uint64_t ndocs)
 {

@@ -430,6 +430,13 @@ int lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_
                       uint32_t* d_leaf_parent, void* ws, uint64_t ws_bytes, hipStream_t st);
 int doc_lookup_dev(const uint32_t* d_pos, uint64_t count, const uint64_t* d_starts, uint64_t ndocs, uint32_t* d_doc,
                    uint32_t* d_offset, hipStream_t st);
+// node table with ordered children (sfx_tree.hip); synchronises the stream once for the counts
+uint64_t suffix_tree_workspace_bytes(uint64_t n);
+int suffix_tree_dev(const uint8_t* d_text, const uint32_t* d_sa, const uint32_t* d_lcp, uint64_t n, uint64_t node_capacity,
+                    uint64_t child_capacity, uint32_t* d_node_lb, uint32_t* d_node_rb, uint32_t* d_node_depth,
+                    uint32_t* d_node_parent, uint32_t* d_node_terminal, uint64_t* d_child_off, uint32_t* d_child_lb,
+                    uint32_t* d_child_node, uint8_t* d_child_byte, uint32_t* d_leaf_parent, uint64_t* nodes_out,
+                    uint64_t* children_out, void* ws, uint64_t ws_bytes, hipStream_t st);
 // generalized suffix array over documents without separators, and its resident index (sfx_tree.hip)
 uint64_t gsa_workspace_bytes(uint64_t n);
 int gsa_build_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, uint32_t* d_gsa, uint32_t* d_da,

@@ -1295,4 +1295,276 @@ int repeat_spans_dev(const uint32_t* d_rep, uint64_t n, uint32_t min_len, const 
     return SFX_OK;
 }
 
+// ---- suffix-tree node table with ordered children (include/suffix_hip.h: sfx_suffix_tree_dev) ------------------
+// The topology above looks upwards and names nodes by boundary numbers.  The table looks down: the heads (boundary 0
+// and every p with node[p] == p) get dense ids by a scan of their flags, which is the order the reference's sweep
+// creates them in; every child item -- a non-root head under its parent, a rank under its leaf parent unless its
+// suffix ends exactly at that node (the node's TERMINAL, lib.rs:127-131) -- counts itself at its parent, a 64-bit
+// scan of the counts gives the segments, a second pass over the same items hands out the slots of a segment in
+// arrival order (the counter counted down again), and every segment is then ordered by its first ranks: the result
+// does not depend on the order the atomics ran in.  A node of a text has at most 256 children (distinct first
+// bytes), so no counter receives more than 256 adds however large n is.
+constexpr int kTreeLaneSeg = 8;                  // segments of up to 8 children are ordered by one lane, in registers
+constexpr int kTreeWaveSeg = 256;                // longer ones by a wave in LDS (a longer one is no text's: left as it is)
+
+// head flags for the scan, and the table check
+__global__ void __launch_bounds__(kBlock)
+k_tree_heads(const uint32_t* __restrict__ sa, const uint32_t* __restrict__ node, uint64_t n, uint32_t* __restrict__ flag,
+             uint32_t* __restrict__ bad)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += stride) {
+        if (sa[p] >= n) *bad = 1u;
+        flag[p] = (p == 0 || node[p] == p) ? 1u : 0u;
+    }
+}
+// is the leaf of rank r, hanging under the node of boundary v, a child of it (true) or its terminal (false)?
+__device__ __forceinline__ bool tree_leaf_is_child(const uint32_t* __restrict__ sa, const uint32_t* __restrict__ lcp, uint64_t n,
+                                                   uint64_t r, uint32_t v)
+{
+    const uint64_t s = sa[r];
+    const uint32_t depth = v ? lcp[v] : 0u;
+    return !(s < n && n - s == depth);
+}
+// P = the exclusive scan of the head flags (P[boundary of a head] = its dense id, P[n] = the number of nodes).
+// Every child item adds one to its parent's counter (cnt: n + 1 zeroed words; an id is <= n whatever lcp holds).
+__global__ void __launch_bounds__(kBlock)
+k_tree_count(const uint32_t* __restrict__ sa, const uint32_t* __restrict__ lcp, uint64_t n, const uint32_t* __restrict__ node,
+             const uint32_t* __restrict__ parent, const uint32_t* __restrict__ leaf_parent, const uint32_t* __restrict__ P,
+             uint32_t* __restrict__ cnt)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += stride) {
+        if (p && node[p] == p) {
+            const uint32_t up = parent[p];
+            if (up < n) atomicAdd(&cnt[P[up]], 1u);
+        }
+        const uint32_t v = leaf_parent[p];
+        if (v < n && tree_leaf_is_child(sa, lcp, n, p, v)) atomicAdd(&cnt[P[v]], 1u);
+    }
+}
+// the three words the host waits for: nodes, children, the table check
+__global__ void __launch_bounds__(64)
+k_tree_totals(const uint32_t* __restrict__ P, const uint64_t* __restrict__ off, const uint32_t* __restrict__ bad, uint64_t n,
+              uint64_t* __restrict__ res)
+{
+    if (threadIdx.x == 0) {
+        res[0] = P[n];
+        res[1] = off[n];
+        res[2] = *bad;
+    }
+}
+__device__ __forceinline__ void tree_place(uint32_t* __restrict__ cnt, const uint64_t* __restrict__ off, uint64_t total, uint32_t k,
+                                           uint32_t first, uint32_t id, uint32_t* __restrict__ child_lb, uint32_t* __restrict__ child_node)
+{
+    const uint32_t slot = atomicSub(&cnt[k], 1u) - 1u;               // (the count of k_tree_count, handed back one by one)
+    const uint64_t at = off[k] + slot;
+    if (at < total) {                                                // (always, for the items that were counted)
+        child_lb[at] = first;
+        child_node[at] = id;
+    }
+}
+// one lane per boundary / rank p: the five per-node arrays of a head, its slot under its parent, the slot of leaf p
+__global__ void __launch_bounds__(kBlock)
+k_tree_fill(const uint32_t* __restrict__ sa, const uint32_t* __restrict__ lcp, uint64_t n, const uint32_t* __restrict__ lb,
+            const uint32_t* __restrict__ rb, const uint32_t* __restrict__ node, const uint32_t* __restrict__ parent,
+            const uint32_t* __restrict__ leaf_parent, const uint32_t* __restrict__ P, uint32_t* __restrict__ cnt,
+            const uint64_t* __restrict__ off, uint64_t nodes, uint64_t total, uint32_t* __restrict__ node_lb,
+            uint32_t* __restrict__ node_rb, uint32_t* __restrict__ node_depth, uint32_t* __restrict__ node_parent,
+            uint32_t* __restrict__ node_terminal, uint32_t* __restrict__ child_lb, uint32_t* __restrict__ child_node,
+            uint32_t* __restrict__ leaf_parent_out)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t p = (uint64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += stride) {
+        if (p == 0 || node[p] == p) {
+            const uint32_t k = P[p];
+            const uint32_t l = p ? lb[p] : 0u, depth = p ? lcp[p] : 0u;
+            const uint32_t up = p ? parent[p] : kNoNode;
+            const uint32_t upk = up < n ? P[up] : kNoNode;
+            if (k < nodes) {
+                const uint64_t s = l < n ? sa[l] : n;
+                node_lb[k] = l;
+                node_rb[k] = p ? rb[p] : (uint32_t)(n - 1);
+                node_depth[k] = depth;
+                node_parent[k] = upk;
+                node_terminal[k] = (s < n && n - s == depth) ? (uint32_t)s : kNoNode;
+            }
+            if (upk != kNoNode) tree_place(cnt, off, total, upk, l, k, child_lb, child_node);
+        }
+        const uint32_t v = leaf_parent[p];
+        if (v < n) {
+            const uint32_t k = P[v];
+            if (leaf_parent_out) leaf_parent_out[p] = k;
+            if (tree_leaf_is_child(sa, lcp, n, p, v)) tree_place(cnt, off, total, k, (uint32_t)p, kNoNode, child_lb, child_node);
+        }
+    }
+}
+// first byte of the edge to the child that starts at rank `first`, under a node of string depth `depth`
+__device__ __forceinline__ uint8_t tree_edge_byte(const uint8_t* __restrict__ text, const uint32_t* __restrict__ sa, uint64_t n,
+                                                  uint32_t first, uint32_t depth)
+{
+    if (first >= n) return 0;
+    const uint64_t at = (uint64_t)sa[first] + depth;
+    return at < n ? text[at] : (uint8_t)0;
+}
+#define SFX_TREE_CSWAP(a, b) do { const uint64_t lo_ = dmin(a, b), hi_ = dmax(a, b); a = lo_; b = hi_; } while (0)
+// Orders every segment by (first rank << 32 | child id) -- first ranks are distinct inside a node -- and writes the edge bytes.
+// A wave takes 64 nodes at a time: each lane orders its node's segment if that is short (an 8-input network on
+// registers), then the wave goes through the longer ones among the 64 together, ranking every entry against the others in LDS.
+__global__ void __launch_bounds__(kBlock)
+k_tree_order(const uint8_t* __restrict__ text, const uint32_t* __restrict__ sa, uint64_t n, uint64_t nodes,
+             const uint64_t* __restrict__ off, const uint32_t* __restrict__ node_depth, uint32_t* __restrict__ child_lb,
+             uint32_t* __restrict__ child_node, uint8_t* __restrict__ child_byte)
+{
+    __shared__ uint64_t seg[kWavesPerBlock][kTreeWaveSeg];
+    const unsigned lane = lane_id(), wave = wave_id();
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t base = (uint64_t)blockIdx.x * kBlock + wave * kWave; base < nodes; base += stride) {
+        const uint64_t k = base + lane;
+        const bool valid = k < nodes;
+        const uint64_t b = valid ? off[k] : 0, e = valid ? off[k + 1] : 0;
+        const uint64_t len = e >= b ? e - b : 0;
+        if (valid && len >= 1 && len <= (uint64_t)kTreeLaneSeg) {
+            const uint32_t depth = node_depth[k];
+            const uint64_t none = ~0ull;
+            uint64_t a0 = ((uint64_t)child_lb[b] << 32) | child_node[b], a1 = none, a2 = none, a3 = none, a4 = none, a5 = none,
+                     a6 = none, a7 = none;
+            if (len > 1) a1 = ((uint64_t)child_lb[b + 1] << 32) | child_node[b + 1];
+            if (len > 2) a2 = ((uint64_t)child_lb[b + 2] << 32) | child_node[b + 2];
+            if (len > 3) a3 = ((uint64_t)child_lb[b + 3] << 32) | child_node[b + 3];
+            if (len > 4) a4 = ((uint64_t)child_lb[b + 4] << 32) | child_node[b + 4];
+            if (len > 5) a5 = ((uint64_t)child_lb[b + 5] << 32) | child_node[b + 5];
+            if (len > 6) a6 = ((uint64_t)child_lb[b + 6] << 32) | child_node[b + 6];
+            if (len > 7) a7 = ((uint64_t)child_lb[b + 7] << 32) | child_node[b + 7];
+            if (len > 1) {
+                SFX_TREE_CSWAP(a0, a1); SFX_TREE_CSWAP(a2, a3);
+                SFX_TREE_CSWAP(a0, a2); SFX_TREE_CSWAP(a1, a3);
+                SFX_TREE_CSWAP(a1, a2);
+            }
+            if (len > 4) {                                           // (19 exchanges in all: the 8-input network)
+                SFX_TREE_CSWAP(a4, a5); SFX_TREE_CSWAP(a6, a7);
+                SFX_TREE_CSWAP(a4, a6); SFX_TREE_CSWAP(a5, a7);
+                SFX_TREE_CSWAP(a5, a6);
+                SFX_TREE_CSWAP(a0, a4); SFX_TREE_CSWAP(a1, a5); SFX_TREE_CSWAP(a2, a6); SFX_TREE_CSWAP(a3, a7);
+                SFX_TREE_CSWAP(a2, a4); SFX_TREE_CSWAP(a3, a5);
+                SFX_TREE_CSWAP(a1, a2); SFX_TREE_CSWAP(a3, a4); SFX_TREE_CSWAP(a5, a6);
+            }
+#define SFX_TREE_PUT(i, a)                                                                              \
+    if (len > i) {                                                                                      \
+        child_lb[b + i] = (uint32_t)(a >> 32);                                                          \
+        child_node[b + i] = (uint32_t)a;                                                                \
+        if (child_byte) child_byte[b + i] = tree_edge_byte(text, sa, n, (uint32_t)(a >> 32), depth);    \
+    }
+            SFX_TREE_PUT(0, a0) SFX_TREE_PUT(1, a1) SFX_TREE_PUT(2, a2) SFX_TREE_PUT(3, a3)
+            SFX_TREE_PUT(4, a4) SFX_TREE_PUT(5, a5) SFX_TREE_PUT(6, a6) SFX_TREE_PUT(7, a7)
+#undef SFX_TREE_PUT
+        }
+        unsigned long long todo = __ballot(valid && len > (uint64_t)kTreeLaneSeg);
+        while (todo) {
+            const unsigned src = (unsigned)__ffsll(todo) - 1u;
+            todo &= todo - 1ull;
+            const uint64_t kk = base + src;
+            const uint64_t sb = off[kk], sl = off[kk + 1] - sb;
+            const uint32_t depth = node_depth[kk];
+            uint64_t* sh = seg[wave];
+            if (sl <= (uint64_t)kTreeWaveSeg) {
+                for (uint64_t i = lane; i < sl; i += kWave) sh[i] = ((uint64_t)child_lb[sb + i] << 32) | child_node[sb + i];
+                wave_sync();
+                for (uint64_t i = lane; i < sl; i += kWave) {
+                    const uint64_t mine = sh[i];
+                    uint32_t r = 0;
+                    for (uint32_t j = 0; j < (uint32_t)sl; j++) r += sh[j] < mine ? 1u : 0u;
+                    child_lb[sb + r] = (uint32_t)(mine >> 32);
+                    child_node[sb + r] = (uint32_t)mine;
+                    if (child_byte) child_byte[sb + r] = tree_edge_byte(text, sa, n, (uint32_t)(mine >> 32), depth);
+                }
+                wave_sync();
+            } else if (child_byte) {                                 // (no text has such a node: the bytes only, in place)
+                for (uint64_t i = lane; i < sl; i += kWave) child_byte[sb + i] = tree_edge_byte(text, sa, n, child_lb[sb + i], depth);
+            }
+        }
+    }
+}
+#undef SFX_TREE_CSWAP
+
+// [results | bad flag | lb, rb, node, parent, leaf_parent: n each | P: n + 1 | counters: n + 1 | offsets: n + 1 u64 |
+//  scan partials | the topology's own workspace]
+struct TreeWs {
+    uint64_t *res, *off, *part;
+    uint32_t *bad, *lb, *rb, *node, *parent, *leaf_parent, *P, *cnt;
+    uint8_t* topo;
+};
+template <class A> static void tree_carve(A& a, uint64_t n, TreeWs* w)
+{
+    w->res = a.template take<uint64_t>(32);
+    w->bad = a.template take<uint32_t>(64);
+    w->lb = a.template take<uint32_t>(n);
+    w->rb = a.template take<uint32_t>(n);
+    w->node = a.template take<uint32_t>(n);
+    w->parent = a.template take<uint32_t>(n);
+    w->leaf_parent = a.template take<uint32_t>(n);
+    w->P = a.template take<uint32_t>(n + 1);
+    w->cnt = a.template take<uint32_t>(n + 1);
+    w->off = a.template take<uint64_t>(n + 1);
+    w->part = a.template take<uint64_t>(kMaxGrid + 64);
+    w->topo = a.template take<uint8_t>(lcp_intervals_workspace_bytes(n));
+}
+uint64_t suffix_tree_workspace_bytes(uint64_t n)
+{
+    if (n == 0 || n > 0xFFFFFFFFull) return 0;
+    GsaSizer z;
+    TreeWs w;
+    tree_carve(z, n, &w);
+    return z.used;
+}
+int suffix_tree_dev(const uint8_t* d_text, const uint32_t* d_sa, const uint32_t* d_lcp, uint64_t n, uint64_t node_capacity,
+                    uint64_t child_capacity, uint32_t* d_node_lb, uint32_t* d_node_rb, uint32_t* d_node_depth,
+                    uint32_t* d_node_parent, uint32_t* d_node_terminal, uint64_t* d_child_off, uint32_t* d_child_lb,
+                    uint32_t* d_child_node, uint8_t* d_child_byte, uint32_t* d_leaf_parent, uint64_t* nodes_out,
+                    uint64_t* children_out, void* ws, uint64_t ws_bytes, hipStream_t st)
+{
+    if (!nodes_out || !children_out) return SFX_ERR_ARG;
+    *nodes_out = 0;
+    *children_out = 0;
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if ((d_text == nullptr) != (d_child_byte == nullptr)) return SFX_ERR_ARG;
+    if (n == 0) return SFX_OK;
+    if (!d_sa || !d_lcp) return SFX_ERR_ARG;
+    if (!ws || ws_bytes < suffix_tree_workspace_bytes(n)) return SFX_ERR_WORKSPACE;
+    Arena a(ws, ws_bytes);
+    TreeWs w;
+    tree_carve(a, n, &w);
+    if (a.overflow) return SFX_ERR_INTERNAL;
+    SFX_TRY(lcp_intervals_dev(d_lcp, n, w.lb, w.rb, w.node, w.parent, w.leaf_parent, w.topo, lcp_intervals_workspace_bytes(n), st));
+    SFX_HIP(hipMemsetAsync(w.bad, 0, sizeof(uint32_t), st));
+    SFX_HIP(hipMemsetAsync(w.cnt, 0, (n + 1) * sizeof(uint32_t), st));
+    const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
+    SFX_LAUNCH("tree_heads", (double)n * 12, k_tree_heads, grid, kBlock, st, d_sa, (const uint32_t*)w.node, n, w.P, w.bad);
+    SFX_TRY(gsa_scan<uint32_t>(w.P, n, w.P, reinterpret_cast<uint32_t*>(w.part), st));
+    SFX_LAUNCH("tree_count", (double)n * 28, k_tree_count, grid, kBlock, st, d_sa, d_lcp, n, (const uint32_t*)w.node,
+               (const uint32_t*)w.parent, (const uint32_t*)w.leaf_parent, (const uint32_t*)w.P, w.cnt);
+    SFX_TRY(gsa_scan<uint64_t>(w.cnt, n, w.off, w.part, st));
+    SFX_LAUNCH("tree_totals", 0.0, k_tree_totals, 1, 64, st, (const uint32_t*)w.P, (const uint64_t*)w.off, (const uint32_t*)w.bad, n,
+               w.res);
+    uint64_t res[3] = {0, 0, 0};
+    SFX_TRY(read_back(res, w.res, sizeof(res), st));
+    if (res[2]) return SFX_ERR_ARG;
+    const uint64_t nodes = res[0], total = res[1];
+    *nodes_out = nodes;
+    *children_out = total;
+    if (nodes > node_capacity || total > child_capacity) return SFX_OK;
+    if (!d_node_lb || !d_node_rb || !d_node_depth || !d_node_parent || !d_node_terminal || !d_child_off ||
+        (total && (!d_child_lb || !d_child_node)))
+        return SFX_ERR_ARG;
+    SFX_HIP(hipMemcpyAsync(d_child_off, w.off, (nodes + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    SFX_LAUNCH("tree_fill", (double)n * 44 + (double)nodes * 20, k_tree_fill, grid, kBlock, st, d_sa, d_lcp, n, (const uint32_t*)w.lb,
+               (const uint32_t*)w.rb, (const uint32_t*)w.node, (const uint32_t*)w.parent, (const uint32_t*)w.leaf_parent,
+               (const uint32_t*)w.P, w.cnt, (const uint64_t*)w.off, nodes, total, d_node_lb, d_node_rb, d_node_depth, d_node_parent,
+               d_node_terminal, d_child_lb, d_child_node, d_leaf_parent);
+    const unsigned ogrid = (unsigned)dmin<uint64_t>((nodes + kBlock - 1) / kBlock, kMaxGrid);
+    SFX_LAUNCH("tree_order", (double)nodes * 12 + (double)total * (d_child_byte ? 22 : 16), k_tree_order, ogrid, kBlock, st, d_text, d_sa,
+               n, nodes, (const uint64_t*)w.off, (const uint32_t*)d_node_depth, d_child_lb, d_child_node, d_child_byte);
+    return SFX_OK;
+}
+
 }  // namespace sfx

@@ -171,6 +171,59 @@ def lcp_intervals(lcp, engine=None):
     return out
 
 
+def suffix_tree_workspace(n, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_suffix_tree_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def suffix_tree(sa, lcp, text=None, want_leaf_parent=True, workspace=None, engine=None):
+    """Suffix-tree node table with ordered children from a suffix array and its LCP array (uint32 in int32 storage, on one
+    device): -> dict(node_lb, node_rb, node_depth, node_parent, node_terminal, child_off (int64, m + 1), child_lb,
+    child_node, child_byte (uint8; only with text), leaf_parent (only if wanted)), cut to the m nodes and C children of
+    the tree.  One sizing call, then one filling call; each synchronises the stream once.  See include/suffix_hip.h."""
+    eng = engine or default_engine()
+    n = sa.numel()
+    _check_u32(sa, "sa")
+    _check_u32(lcp, "lcp", n)
+    if text is not None:
+        _check_u8(text)
+        if text.numel() != n:
+            raise ValueError(f"text must hold {n} bytes")
+    for t in (lcp, text):
+        if t is not None and t.device != sa.device:
+            raise ValueError(f"all arrays must be on one device ({sa.device})")
+    if sa.is_cuda:
+        eng.require_device()
+    dev = sa.device
+    if workspace is None:
+        workspace = suffix_tree_workspace(n, dev, eng)
+    m, c = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    with _on(sa):
+        eng.check(eng.lib.sfx_suffix_tree_dev(None, _p(sa), _p(lcp), n, 0, 0, None, None, None, None, None, None, None, None, None,
+                                              None, ctypes.byref(m), ctypes.byref(c), _p(workspace), workspace.numel(),
+                                              _stream_ptr(sa)), "sfx_suffix_tree_dev")
+    nm, nc = int(m.value), int(c.value)
+    out = {k: torch.empty(nm, dtype=torch.int32, device=dev) for k in ("node_lb", "node_rb", "node_depth", "node_parent", "node_terminal")}
+    out["child_off"] = torch.zeros(nm + 1, dtype=torch.int64, device=dev)
+    out["child_lb"] = torch.empty(nc, dtype=torch.int32, device=dev)
+    out["child_node"] = torch.empty(nc, dtype=torch.int32, device=dev)
+    # (a byte array of no entries still has to be a pointer when there is a text: both or neither)
+    cbyte = torch.empty(max(nc, 1), dtype=torch.uint8, device=dev) if text is not None else None
+    leaf = torch.empty(n, dtype=torch.int32, device=dev) if want_leaf_parent else None
+    if n:
+        with _on(sa):
+            eng.check(eng.lib.sfx_suffix_tree_dev(_p(text), _p(sa), _p(lcp), n, nm, nc, _p(out["node_lb"]), _p(out["node_rb"]),
+                                                  _p(out["node_depth"]), _p(out["node_parent"]), _p(out["node_terminal"]),
+                                                  _p(out["child_off"]), _p(out["child_lb"]), _p(out["child_node"]), _p(cbyte),
+                                                  _p(leaf), ctypes.byref(m), ctypes.byref(c), _p(workspace), workspace.numel(),
+                                                  _stream_ptr(sa)), "sfx_suffix_tree_dev")
+    if cbyte is not None:
+        out["child_byte"] = cbyte[:nc]
+    if leaf is not None:
+        out["leaf_parent"] = leaf
+    return out
+
+
 def doc_lookup(positions, doc_starts, engine=None):
     """Generalized suffix array: text positions (uint32 in int32 storage) -> (document index, offset inside it);
     doc_starts = sorted int64 start offsets of the documents inside the concatenated text."""
