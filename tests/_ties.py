@@ -189,8 +189,12 @@ def _runs(flag):
     return starts, np.flatnonzero(d == -1) - starts
 
 
-def witness(text, sa, lcp, text_fed=True):
+def witness(text, sa, lcp, text_fed=True, key_symbols=None):
     """What the tie route does with `text`, modelled from the oracle's SA and LCP (lcp[r] = LCP of slots r - 1 and r).
+
+    key_symbols: the symbols the initial sort keys on, where the caller knows them (tests/_routes.py: symbols_per_key of the
+    ordinary route -- 2 * (32 // bits) on fixed-width 64-bit keys -- and of a hybrid sort whose symbols are wider than 4 bits, one
+    more on the hybrid route's tie mode with 1-, 2- or 4-bit symbols); None: from `text_fed`, as below.
 
     Keys (sfx_radix.hip:1925-1932, SrcText36): a text-fed build sorts on symbols_per_key + 1 symbols (one more symbol in the four
     bits a suffix index of <= 2^28 leaves free); a slice of a multi-range build on symbols_per_key.  Slot r is tied when its key
@@ -201,7 +205,8 @@ def witness(text, sa, lcp, text_fed=True):
     first when small_groups_pay(kept, groups) (sfx_sa.hip:2137, groups * 4 >= kept)."""
     codes, bits, spk = codes_of(text)
     m = len(codes)
-    nsym = spk + 1 if text_fed else spk
+    nsym = int(key_symbols) if key_symbols is not None else (spk + 1 if text_fed else spk)
+    assert nsym >= spk, (nsym, spk)
     depth = DEPTH_WORDS // 2 * 2 * spk
     sa = np.asarray(sa)
     key = prefix_keys(codes, bits, nsym)[sa]            # (in SA order)
