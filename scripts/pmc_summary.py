@@ -39,8 +39,8 @@ NAMES = [
     ("k_radix_hist_all<sfx::SrcE64", "radix_hist_all_u32"), ("k_radix_hist_all<sfx::SrcKV", "radix_hist_all_u64"),
     ("k_radix_hist_chunk", "radix_hist"), ("k_radix_scan", "radix_scan"),
     ("k_window_hist", "radix_hist_all_text_u32"), ("k_window_fix", "radix_window_fix"), ("k_window_from_hist16", "radix_window_from_hist16"),
-    ("k_hist16_text", "radix_hist16_text"), ("k_hist16_e64", "radix_hist16_elems"), ("k_hist16_reduce", "radix_hist16_reduce"),
-    ("k_hist16_scan", "radix_hist16_scan"), ("k_hist16_oversize", "radix_hist16_oversize"), ("k_partition_cursors", "partition_cursors"),
+    ("k_hist16_text", "radix_hist16_text"), ("k_hist16_e64", "radix_hist16_elems"), ("k_hist16_finish", "radix_hist16_finish"),
+    ("k_hist16_oversize", "radix_hist16_oversize"),
     ("k_bucket_sort<4, 8, true, true", "bucket_sort_ties_keys"), ("k_bucket_sort<4, 16, true, true", "bucket_sort_ties_keys"),
     ("k_bucket_sort<16, 16, true, true", "bucket_sort_ties_keys"),
     ("k_bucket_sort<4, 8, true", "bucket_sort_ties"), ("k_bucket_sort<4, 16, true", "bucket_sort_ties"),

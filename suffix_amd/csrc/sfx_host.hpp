@@ -128,9 +128,11 @@ void profile_end(hipStream_t st);
 // read-back) against 15.2 for an asynchronous copy into pinned memory + hipStreamSynchronize and 39.5 for a copy into
 // pageable memory (lab/sync_probe.hip, MI355X).  The stream is queried every few thousand polls: a stream that has drained
 // (or failed) without the word arriving ends the wait with its error.
-#ifndef SFX_EMULATED
 namespace detail {
 constexpr unsigned kPostWords = 64;                                  // 256 bytes per read-back
+}
+#ifndef SFX_EMULATED
+namespace detail {
 static __global__ void __launch_bounds__(64) k_post_words(const uint32_t* __restrict__ src, unsigned words, volatile uint32_t* host,
                                                    uint32_t seq)
 {
@@ -142,15 +144,23 @@ static __global__ void __launch_bounds__(64) k_post_words(const uint32_t* __rest
 }
 }  // namespace detail
 #endif
-inline int read_back(void* dst, const void* d_src, size_t bytes, hipStream_t st)
+// A kernel that has the words anyway posts them itself (post_words_from_kernel at its end) and saves the one-wave launch: the
+// host takes a PostTicket before the launch, hands it to the kernel and waits on it afterwards.  host == nullptr (no pinned page,
+// or the CPU emulator): nobody polls, the kernel posts nothing and read_posted copies from d_src.
+struct PostTicket {
+    volatile uint32_t* host;
+    uint32_t seq;
+};
+namespace detail {
+constexpr size_t kStage = 4096, kPostArea = 512;
+// One pinned allocation per thread, two disjoint areas: [0, kStage) stages the copies of the fallback below (and of every
+// read above 256 bytes: the 2 KiB of byte bins), [kStage, kStage + 512) is the posted area -- payload + sequence word.  They
+// must not overlap: a staged copy that left a stale value where the sequence word lives would end a later poll before its
+// kernel has run (the bins of a text with spaces wrote 1 over the word, the first post polled for 1).
+// Portable + coherent + mapped: kernels of whichever device is current later write the page, and the host sees the words
+// without a flush.
+inline void* post_stage()
 {
-    // One pinned allocation per thread, two disjoint areas: [0, kStage) stages the copies of the fallback below (and of every
-    // read above 256 bytes: the 2 KiB of byte bins), [kStage, kStage + 512) is the posted area -- payload + sequence word.  They
-    // must not overlap: a staged copy that left a stale value where the sequence word lives would end a later poll before its
-    // kernel has run (the bins of a text with spaces wrote 1 over the word, the first post polled for 1).
-    // Portable + coherent + mapped: kernels of whichever device is current later write the page, and the host sees the words
-    // without a flush.
-    constexpr size_t kStage = 4096, kPostArea = 512;
     thread_local void* stage = nullptr;
     thread_local bool tried = false;
     if (!tried) {
@@ -161,14 +171,51 @@ inline int read_back(void* dst, const void* d_src, size_t bytes, hipStream_t st)
         }
         if (stage) std::memset(stage, 0, kStage + kPostArea);
     }
+    return stage;
+}
+}  // namespace detail
+inline PostTicket post_ticket()
+{
 #ifndef SFX_EMULATED
     thread_local uint32_t seq = 0;
-    if (stage && bytes > 0 && bytes <= detail::kPostWords * 4 && (bytes & 3u) == 0 && (reinterpret_cast<uintptr_t>(d_src) & 3u) == 0) {
-        static_assert((detail::kPostWords + 16) * 4 <= kPostArea, "payload + the sequence word's own 64-byte block");
-        volatile uint32_t* const host = reinterpret_cast<volatile uint32_t*>(static_cast<char*>(stage) + kStage);
+    void* const stage = detail::post_stage();
+    if (stage) {
+        static_assert((detail::kPostWords + 16) * 4 <= detail::kPostArea, "payload + the sequence word's own 64-byte block");
         if (++seq == 0) seq = 1;
-        hipLaunchKernelGGL(detail::k_post_words, dim3(1), dim3(64), 0, st, static_cast<const uint32_t*>(d_src), (unsigned)(bytes / 4), host, seq);
-        SFX_HIP(hipGetLastError());
+        return PostTicket{reinterpret_cast<volatile uint32_t*>(static_cast<char*>(stage) + detail::kStage), seq};
+    }
+#endif
+    return PostTicket{nullptr, 0};
+}
+// (device) the last thread standing of a kernel posts `words` <= kPostWords words it has in `src` (its own registers or memory it
+// wrote itself); call from ONE thread, after everything the host may act on has been written
+template <class Words>
+__device__ __forceinline__ void post_words_from_kernel(const PostTicket& t, const Words& src, unsigned words)
+{
+#ifndef SFX_EMULATED
+    if (!t.host) return;
+    for (unsigned i = 0; i < words; i++) t.host[i] = src[i];
+    __threadfence_system();
+    __builtin_amdgcn_s_waitcnt(0);
+    t.host[detail::kPostWords] = t.seq;                              // (its own 64-byte block, after the payload)
+#endif
+}
+inline int read_by_copy(void* dst, const void* d_src, size_t bytes, hipStream_t st)
+{
+    void* const stage = detail::post_stage();
+    void* via = (stage && bytes <= detail::kStage) ? stage : dst;
+    SFX_HIP(hipMemcpyAsync(via, d_src, bytes, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    if (via != dst) std::memcpy(dst, via, bytes);
+    return SFX_OK;
+}
+// the words a kernel launched on `st` posts under ticket `t`; d_src: where the same words lie in device memory
+inline int read_posted(void* dst, const void* d_src, size_t bytes, const PostTicket& t, hipStream_t st)
+{
+#ifndef SFX_EMULATED
+    if (t.host && bytes > 0 && bytes <= detail::kPostWords * 4 && (bytes & 3u) == 0) {
+        volatile uint32_t* const host = t.host;
+        const uint32_t seq = t.seq;
         for (unsigned spins = 1;; spins++) {
             if (host[detail::kPostWords] == seq) break;
 #if defined(__x86_64__) || defined(__i386__)
@@ -179,20 +226,30 @@ inline int read_back(void* dst, const void* d_src, size_t bytes, hipStream_t st)
                 if (q == hipErrorNotReady) continue;
                 SFX_HIP(q);                                          // (a failed stream)
                 if (host[detail::kPostWords] == seq) break;
-                SFX_HIP(hipStreamSynchronize(st));                   // drained without the word (cannot happen): take the copy below
-                goto by_copy;
+                SFX_HIP(hipStreamSynchronize(st));                   // drained without the word (cannot happen): take the copy
+                return read_by_copy(dst, d_src, bytes, st);
             }
         }
         for (size_t i = 0; i < bytes / 4; i++) static_cast<uint32_t*>(dst)[i] = host[i];
         return SFX_OK;
     }
-by_copy:
 #endif
-    void* via = (stage && bytes <= kStage) ? stage : dst;
-    SFX_HIP(hipMemcpyAsync(via, d_src, bytes, hipMemcpyDeviceToHost, st));
-    SFX_HIP(hipStreamSynchronize(st));
-    if (via != dst) std::memcpy(dst, via, bytes);
-    return SFX_OK;
+    return read_by_copy(dst, d_src, bytes, st);
+}
+inline int read_back(void* dst, const void* d_src, size_t bytes, hipStream_t st)
+{
+#ifndef SFX_EMULATED
+    if (bytes > 0 && bytes <= detail::kPostWords * 4 && (bytes & 3u) == 0 && (reinterpret_cast<uintptr_t>(d_src) & 3u) == 0) {
+        const PostTicket t = post_ticket();
+        if (t.host) {
+            hipLaunchKernelGGL(detail::k_post_words, dim3(1), dim3(64), 0, st, static_cast<const uint32_t*>(d_src), (unsigned)(bytes / 4), t.host,
+                               t.seq);
+            SFX_HIP(hipGetLastError());
+            return read_posted(dst, d_src, bytes, t, st);
+        }
+    }
+#endif
+    return read_by_copy(dst, d_src, bytes, st);
 }
 
 // ---- cross-TU entry points ----------------------------------------------------------

@@ -72,6 +72,11 @@ struct SrcText32 {
         return ((uint64_t)packed_key32(t, i) << 32) | (uint64_t)(uint32_t)i;
     }
     __device__ __forceinline__ uint32_t val(uint64_t) const { return 0u; }
+    // the element of suffix i from the 64 bits of symbols that start at it (kbits == 32: the key is their top half)
+    __device__ __forceinline__ uint64_t from_window(uint64_t k64, uint64_t i) const
+    {
+        return (k64 & 0xFFFFFFFF00000000ull) | (uint64_t)(uint32_t)i;
+    }
 };
 // The same with `extra` more key bits in the element where the suffix index leaves room (round 6; the hybrid route, m <= 2^28:
 // a suffix index needs 28 bits): element = key of 32 + extra bits << (32 - extra) | suffix.  The order of whole elements is
@@ -97,9 +102,45 @@ struct SrcText36 {
             const uint64_t both = ((pair & 0xFFFFFFFFull) << 32) | (pair >> 32);
             k64 = both << (off * (unsigned)t.bits);
         }
-        return ((k64 >> (32 - extra)) << (32 - extra)) | (uint64_t)(uint32_t)i;
+        return from_window(k64, i);
     }
     __device__ __forceinline__ uint32_t val(uint64_t) const { return 0u; }
+    __device__ __forceinline__ uint64_t from_window(uint64_t k64, uint64_t i) const
+    {
+        return ((k64 >> (32 - extra)) << (32 - extra)) | (uint64_t)(uint32_t)i;
+    }
+};
+// A full tile of a text-fed partition pass without a load per element (round 7).  With SPW = 32 / bits symbols in a packed word
+// (1, 2, 4, 8 bits: kbits == 32) and tiles that begin on word boundaries, thread t takes the tile's positions [KPT t, KPT t + KPT):
+// they start in max(KPT / SPW, 1) consecutive words, and with the word behind those every one of the KPT windows is a shift of two
+// neighbouring registers.  One load of TextTileWords::kCount words per thread and tile -- DNA at KPT = 16: two -- where key()
+// issues KPT eight-byte loads, each a word-index division, and a wave's 64 lanes ask for the same 16 - 24 bytes 64 times.  Which
+// lane ranks which element is free in an unstable pass.
+template <int SPW, int KPT>
+struct TextTileWords {
+    static_assert(SPW >= KPT ? SPW % KPT == 0 : KPT % SPW == 0, "a thread's positions begin on a word boundary or stay inside one word");
+    static constexpr int kOwn = SPW >= KPT ? 1 : KPT / SPW;
+    static constexpr int kCount = kOwn + 1;
+    uint32_t w[kCount];
+    // the words of thread `tid` of the tile whose first position is `begin` (a multiple of SPW; all of the tile's KPT * threads
+    // positions are < t.n, so the last word read is at most the one behind the text's last: inside the array's 3 spare words)
+    __device__ __forceinline__ void load(const PackedText& t, uint64_t begin, unsigned tid)
+    {
+        __builtin_memcpy(w, t.words + (begin / (unsigned)SPW + ((uint64_t)tid * KPT) / (unsigned)SPW), sizeof(w));
+    }
+    template <class Src>
+    __device__ __forceinline__ void keys(const Src& src, uint64_t begin, unsigned tid, uint64_t (&key)[KPT]) const
+    {
+        constexpr unsigned kBits = 32u / SPW;
+        const unsigned off0 = SPW > KPT ? (tid * KPT) % (unsigned)SPW : 0u;
+#pragma unroll
+        for (int r = 0; r < KPT; r++) {
+            const int j = SPW > KPT ? 0 : r / SPW;
+            const unsigned off = SPW > KPT ? off0 + (unsigned)r : (unsigned)(r % SPW);
+            const uint64_t both = ((uint64_t)w[j] << 32) | (uint64_t)w[j + 1];
+            key[r] = src.from_window(both << (off * kBits), begin + (uint64_t)tid * KPT + (unsigned)r);
+        }
+    }
 };
 struct SrcKV {
     static constexpr bool kHasVal = true;
@@ -955,13 +996,17 @@ struct PartSmem {
 //              bucket = bits [shift, shift + 8) inside top-8 bucket b, cursor[(b << 8) | d].
 // (Ranking: the match masks of the one-sweep pass.  One returning LDS atomic per element was the first version -- the LDS
 // retires about one of them per clock and CU: 8.4 us per 16384-element tile against 4.6 for the masks, lab/partition_lab.hip.)
-template <class Src, int KPT, int NW, bool SUB>
+// SPW > 0:     (text-fed, SUB = false, 32 / SPW bits per symbol, class_len a multiple of SPW) the full tiles take their elements
+//              through TextTileWords, the words of the workgroup's next tile requested before this one is ranked; a short tile
+//              (the last of a stretch) keeps src.key().
+template <class Src, int KPT, int NW, bool SUB, int SPW = 0>
 __global__ void __launch_bounds__(NW * kWave) SFX_WAVES_PER_EU(4, 4)      // (16 waves per CU: one workgroup of 16, two of 8 or four of 4)
 k_partition(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t* __restrict__ cursor,
             const uint32_t* __restrict__ bstart16, uint64_t class_len)
 {
     constexpr int kThreads = NW * kWave;
     constexpr uint32_t kTile = kThreads * KPT;
+    static_assert(SPW == 0 || (Src::kFromText && !SUB), "the tile loader reads packed text");
     static_assert(kThreads >= kRadix, "thread d owns bucket d");
     static_assert(kWave * KPT >= kRadix, "the match masks must fit the staging buffer");
     static_assert(kTile < 65536, "16-bit tile positions");
@@ -1034,20 +1079,45 @@ k_partition(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t
     };
     // (wave-striped loads, 64 consecutive elements per round; the padding of a short tile carries the largest digit and is
     // ranked behind the real elements of its wave's last rounds: it stays out of the counts and is never stored.  Requesting
-    // the next tile's elements before this one leaves was measured: the 32 registers it takes spill into the ranking loop.)
+    // the next tile's elements before this one leaves was measured: the 32 registers it takes spill into the ranking loop.
+    // The tile loader's words are another matter: two registers for DNA.  A short tile does not use it: its padding is ranked
+    // behind the real elements only in the wave-striped order.)
+    TextTileWords<SPW ? SPW : KPT, KPT> words = {};
+    auto request = [&](uint64_t v) {                                 // the words of tile v, when it is a full one
+        if constexpr (SPW > 0) {
+            uint64_t begin;
+            unsigned nvalid, top;
+            locate(v, begin, nvalid, top);
+            if (nvalid == kTile) words.load(src.t, begin, tid);
+        }
+    };
+    request(blockIdx.x);
     for (uint64_t v = blockIdx.x; v < ntiles; v += gridDim.x) {
         uint64_t begin;
         unsigned nvalid, top;
         locate(v, begin, nvalid, top);
-        if (nvalid == 0u) continue;                                  // (SUB: this class has fewer tiles than the largest)
+        if (nvalid == 0u) {                                          // (a stretch or a class with fewer tiles than the largest)
+            request(v + gridDim.x);
+            continue;
+        }
         uint64_t key[KPT];
         uint32_t pos[KPT];
-        unsigned first = w * (kWave * KPT) + lane;                   // (opaque, like t below)
-        SFX_OPAQUE_VGPR(first);
+        bool striped = true;
+        if constexpr (SPW > 0) {
+            if (nvalid == kTile) {
+                words.keys(src, begin, tid, key);
+                striped = false;
+            }
+            request(v + gridDim.x);                                  // (in flight while this tile is ranked, staged and stored)
+        }
+        if (striped) {
+            unsigned first = w * (kWave * KPT) + lane;               // (opaque, like t below)
+            SFX_OPAQUE_VGPR(first);
 #pragma unroll
-        for (int r = 0; r < KPT; r++) {
-            const unsigned idx = first + r * kWave;
-            key[r] = idx < nvalid ? src.key(begin + idx) : ~0ull;
+            for (int r = 0; r < KPT; r++) {
+                const unsigned idx = first + r * kWave;
+                key[r] = idx < nvalid ? src.key(begin + idx) : ~0ull;
+            }
         }
 #pragma unroll
         for (int k = 0; k < kRadix / kWave; k++) my_flags[k * kWave + lane] = 0ull;
@@ -1104,26 +1174,6 @@ k_partition(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t
         __syncthreads();
     }
 }
-// the cursors of both passes from the sub-bucket starts: second pass = the sub-bucket starts themselves; first pass = one per
-// (stretch of the input x, top-8 bucket b): the bucket's start + what the stretches before x put into it
-__global__ void __launch_bounds__(kBlock)
-k_partition_cursors(const uint32_t* __restrict__ bstart16, const uint32_t* __restrict__ class_top8, uint32_t* __restrict__ cursor16,
-                    uint32_t* __restrict__ cursor8)
-{
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < (unsigned)(1 << 16)) {
-        const uint32_t b = bstart16[i];
-        cursor16[i] = b;
-        if ((i & 255u) == 0u) {
-            uint32_t run = b;
-            for (unsigned x = 0; x < kPartClasses; x++) {
-                cursor8[(x * kRadix + (i >> 8)) * kCursorPad] = run;
-                run += class_top8[x * kRadix + (i >> 8)];
-            }
-        }
-    }
-}
-
 // ---- hybrid initial sort: two device-wide passes on the top 16 key bits, the rest in LDS ----------
 // An LSD sort moves every element once per 8 key bits through the CU write path (0.41 of HBM peak, §9 of
 // DESIGN.md).  When the text is large enough that the 65536 sub-buckets of the top 16 key bits hold a few
@@ -1136,13 +1186,28 @@ k_partition_cursors(const uint32_t* __restrict__ bstart16, const uint32_t* __res
 constexpr int kH16Bins = 1 << 16;
 constexpr int kH16Words = kH16Bins / 2;                              // two 16-bit counters per LDS word
 constexpr int kH16Threads = 1024;
+// What the kernels behind the sweep want zeroed (the sub-bucket counts with the statistics and k_hist16_finish's ticket behind
+// them; the tickets of the one-sweep passes): the sweep's workgroups clear it on their way in -- they are bound by their LDS
+// atomics, and a fill is a launch of its own in the stream (~4 us each, two of them before round 7).
+struct H16Zero {
+    uint32_t* a;
+    uint32_t na;
+    uint32_t* b;
+    uint32_t nb;
+    __device__ __forceinline__ void clear(unsigned threads) const
+    {
+        for (uint32_t i = blockIdx.x * threads + threadIdx.x; i < na; i += gridDim.x * threads) a[i] = 0;
+        for (uint32_t i = blockIdx.x * threads + threadIdx.x; i < nb; i += gridDim.x * threads) b[i] = 0;
+    }
+};
 // One sweep over the workgroup's stretch of the text with 16-bit counters (128 KiB of LDS).  A counter can only
 // wrap when a sub-bucket holds >= 65536 suffixes of this stretch alone -- far beyond what the LDS sort accepts;
 // a wrap changes the sum of all counters by -65535 (low half: its carry lands in the high half) or -65536 (high
 // half), never by 0 in any combination, so the host detects it from the total (!= m) and takes the other route.
 __global__ void __launch_bounds__(kH16Threads)
-k_hist16_text(PackedText t, int drop, uint64_t words_per_block, uint32_t* __restrict__ partial)
+k_hist16_text(PackedText t, int drop, uint64_t words_per_block, uint32_t* __restrict__ partial, H16Zero z)
 {
+    z.clear(kH16Threads);
     __shared__ uint32_t h[kH16Words];                                 // 128 KiB
     const unsigned tid = threadIdx.x;
     const uint64_t nwords = (t.n + (uint64_t)t.spw - 1) / (uint64_t)t.spw;
@@ -1151,9 +1216,13 @@ k_hist16_text(PackedText t, int drop, uint64_t words_per_block, uint32_t* __rest
     const uint64_t mask = (1ull << t.kbits) - 1ull;
     for (unsigned i = tid; i < (unsigned)kH16Words; i += kH16Threads) h[i] = 0;
     __syncthreads();
+    // (the word pair of the next step is requested before this step's atomics: the LDS works while the load is on its way)
+    uint32_t w0 = 0, w1 = 0;
+    if (qb + tid < qe) { w0 = t.words[qb + tid]; w1 = t.words[qb + tid + 1]; }
     for (uint64_t q = qb + tid; q < qe; q += kH16Threads) {
         // the spw keys that start in word q, from the two words they span (as packed_key32)
-        const uint64_t both = ((uint64_t)t.words[q] << t.kbits) | (uint64_t)t.words[q + 1];
+        const uint64_t both = ((uint64_t)w0 << t.kbits) | (uint64_t)w1;
+        if (q + kH16Threads < qe) { w0 = t.words[q + kH16Threads]; w1 = t.words[q + kH16Threads + 1]; }
         const uint64_t j0 = q * (uint64_t)t.spw;
         for (int o = 0; o < t.spw; o++) {
             if (j0 + (uint64_t)o >= t.n) break;
@@ -1169,8 +1238,9 @@ k_hist16_text(PackedText t, int drop, uint64_t words_per_block, uint32_t* __rest
 // The same counts from (key << 32 | suffix) elements that already exist (a slice of the partitioned build): bits
 // [shift, shift + 16) of the element.
 __global__ void __launch_bounds__(kH16Threads)
-k_hist16_e64(const uint64_t* __restrict__ E, uint64_t m, int shift, uint64_t per_block, uint32_t* __restrict__ partial)
+k_hist16_e64(const uint64_t* __restrict__ E, uint64_t m, int shift, uint64_t per_block, uint32_t* __restrict__ partial, H16Zero z)
 {
+    z.clear(kH16Threads);
     __shared__ uint32_t h[kH16Words];                                 // 128 KiB
     const unsigned tid = threadIdx.x;
     const uint64_t qb = (uint64_t)blockIdx.x * per_block;
@@ -1198,92 +1268,150 @@ k_hist16_e64(const uint64_t* __restrict__ E, uint64_t m, int shift, uint64_t per
     uint32_t* out = partial + (uint64_t)blockIdx.x * kH16Words;
     for (unsigned i = tid; i < (unsigned)kH16Words; i += kH16Threads) out[i] = h[i];
 }
-// bins[b] += the counts of a slice of the workgroups' partial histograms: workgroup x + 64 y takes the 1024 bins
-// from 1024 x (2 KB of every partial, one 8-byte load per thread) and the partials y, y + split, ...
-constexpr int kH16ReduceBins = 1024;
-constexpr unsigned kH16ReduceSplit = 8;
-// (The rows are split among the kH16ReduceSplit = 8 block groups in contiguous stretches of `rows_per_class`: group x sums the
-// workgroups that counted the x-th stretch of the text, and a wave's 256 bins are one top-8 bucket -- so the sum over a wave is
-// the number of suffixes of that stretch in that bucket: class_top8[x * 256 + bucket], which the first partition pass turns
-// into one cursor per (stretch, bucket), k_partition.)
-__global__ void __launch_bounds__(kBlock)
-k_hist16_reduce(const uint32_t* __restrict__ partial, unsigned nblocks, uint32_t* __restrict__ bins, unsigned rows_per_class,
-                uint32_t* __restrict__ class_top8)
-{
-    const unsigned bx = blockIdx.x % (kH16Bins / kH16ReduceBins), by = blockIdx.x / (kH16Bins / kH16ReduceBins);
-    const unsigned w0 = bx * (kH16ReduceBins / 2) + threadIdx.x * 2;              // this thread's two counter words = 4 bins
-    uint32_t c[4] = {0, 0, 0, 0};
-    const unsigned g1 = dmin(nblocks, (by + 1u) * rows_per_class);
-    for (unsigned g = by * rows_per_class; g < g1; g++) {
-        const uint2 v = *reinterpret_cast<const uint2*>(partial + (uint64_t)g * kH16Words + w0);
-        c[0] += v.x & 0xFFFFu;
-        c[1] += v.x >> 16;
-        c[2] += v.y & 0xFFFFu;
-        c[3] += v.y >> 16;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        if (c[k]) atomicAdd(&bins[2 * w0 + k], c[k]);
-    uint32_t all = c[0] + c[1] + c[2] + c[3];
-    for (int d = 32; d >= 1; d >>= 1) all += __shfl_xor(all, d);
-    static_assert(kWave * 4 == kRadix, "a wave's bins are one top-8 bucket");
-    if (lane_id() == 0) class_top8[by * kRadix + (2u * w0) / (unsigned)kRadix] = all;
-}
-// totals_lo[d] = sum over the high digits of bin (j, d), totals_hi[j] = sum over the low digits; bins[b] -> first
-// position of sub-bucket b (in place), bins[65536] = m.  stat_out (zeroed by the caller) = {largest bin, sum of all
-// bins, sub-buckets of more than `cap` suffixes, their suffixes, suffixes in sub-buckets of more than `fast`}.
+// Everything between the histogram sweep and the first partition pass in ONE launch (round 7; rounds 3-6: a reduction, a
+// one-workgroup scan, a cursor kernel and a one-wave kernel that posted the statistics to the host).
+//   every workgroup  bins[b] += the counts of a slice of the workgroups' partial histograms: workgroup x + 32 y takes the 2048
+//                    bins from 2048 x (4 KB of every partial, one 8-byte load per thread, four rows in flight) and the partials
+//                    of the y-th of kPartClasses contiguous stretches of `rows_per_class` rows -- the workgroups that counted the
+//                    y-th stretch of the text; a wave's 256 bins are one top-8 bucket, so the sum over a wave is the number of
+//                    suffixes of that stretch in that bucket, class_top8[y * 256 + bucket];
+//   the last one     (to finish: a device-scope ticket) reads the 65536 counts in two halves through the LDS -- 16-byte loads,
+//                    coalesced, where round 3's scan had every lane on a line of its own -- and leaves
+//                      bins[b] = first position of sub-bucket b (in place), bins[65536] = m; cursor16 = the same (the second
+//                      partition pass advances it); cursor8[(x * 256 + j) * kCursorPad] = start of top-8 bucket j + what the
+//                      stretches before x put into it (the first pass's);
+//                      totals_lo[d] = sum over the high digits of bin (j, d), totals_hi[j] = sum over the low digits;
+//                      stat_out = {largest bin, sum of all bins, sub-buckets of more than `cap` suffixes, their suffixes,
+//                      suffixes in sub-buckets of more than `fast`}, posted to the host as well (PostTicket).
+// bins[0 .. 65536) and *ticket are zero on entry.
 struct OversizeEntry { uint32_t bin, start, size, off; };
 constexpr uint32_t kOversizeMax = 16384;
-__global__ void __launch_bounds__(kH16Threads)
-k_hist16_scan(uint32_t* __restrict__ bins, uint32_t* __restrict__ totals_lo, uint32_t* __restrict__ totals_hi,
-              uint32_t* __restrict__ stat_out, uint32_t cap, uint32_t fast)
+constexpr int kH16FinThreads = 512;
+constexpr int kH16FinBins = 4 * kH16FinThreads;                      // bins of one workgroup of the reduction
+constexpr int kH16FinHalf = kH16Bins / 2;                            // bins the LDS holds at a time in the scan
+constexpr int kH16FinPer = kH16FinHalf / kH16FinThreads;             // consecutive bins per thread and half: 64
+__global__ void __launch_bounds__(kH16FinThreads)
+k_hist16_finish(const uint32_t* __restrict__ partial, unsigned nblocks, unsigned rows_per_class, uint32_t* bins,
+                uint32_t* class_top8, uint32_t* ticket, uint32_t* __restrict__ totals_lo, uint32_t* __restrict__ totals_hi,
+                uint32_t* __restrict__ stat_out, uint32_t cap, uint32_t fast, uint32_t* __restrict__ cursor16,
+                uint32_t* __restrict__ cursor8, PostTicket post)
 {
-    __shared__ uint32_t part[kH16Threads / kWave];
-    __shared__ uint32_t pmax[kH16Threads / kWave];
-    __shared__ uint32_t lo[4][kRadix];
-    __shared__ uint32_t tsum[kH16Threads];
-    constexpr int kPer = kH16Bins / kH16Threads;                       // 64 consecutive bins per thread: a quarter of a high digit
+    constexpr int kWaves = kH16FinThreads / kWave;
+    __shared__ uint32_t tile[kH16FinHalf + kH16FinHalf / kH16FinPer];   // (one word of padding per thread's stretch: 130 KiB)
+    __shared__ uint32_t lo[kRadix];
+    __shared__ uint32_t part[kWaves];
+    __shared__ uint32_t sstat[5];
+    __shared__ uint32_t last;
     const unsigned tid = threadIdx.x;
     {
-        // thread (q, d): the bins (j, d) with j = q mod 4
-        const unsigned d = tid & 255u, q = tid >> 8;
-        uint32_t t = 0;
-        for (unsigned j = q; j < (unsigned)kRadix; j += 4) t += bins[j * kRadix + d];
-        lo[q][d] = t;
-    }
-    uint32_t v[kPer], sum = 0, most = 0;
-    {
-        uint32_t slow = 0, nover = 0, sover = 0;
-        for (int j = 0; j < kPer; j++) {
-            v[j] = bins[tid * kPer + j];
-            sum += v[j];
-            most = dmax(most, v[j]);
-            if (v[j] > fast) slow += v[j];
-            if (v[j] > cap) { nover++; sover += v[j]; }
+        constexpr unsigned kGroups = kH16Bins / kH16FinBins;
+        const unsigned bx = blockIdx.x % kGroups, by = blockIdx.x / kGroups;
+        const unsigned w0 = bx * (kH16FinBins / 2) + tid * 2;                        // this thread's two counter words = 4 bins
+        uint32_t c[4] = {0, 0, 0, 0};
+        const unsigned g1 = dmin(nblocks, (by + 1u) * rows_per_class);
+        constexpr int kFly = 4;
+        for (unsigned g = by * rows_per_class; g < g1; g += kFly) {
+            uint2 v[kFly];
+#pragma unroll
+            for (int k = 0; k < kFly; k++) {
+                v[k] = uint2{0u, 0u};
+                if (g + (unsigned)k < g1) v[k] = *reinterpret_cast<const uint2*>(partial + (uint64_t)(g + (unsigned)k) * kH16Words + w0);
+            }
+#pragma unroll
+            for (int k = 0; k < kFly; k++) {
+                c[0] += v[k].x & 0xFFFFu;
+                c[1] += v[k].x >> 16;
+                c[2] += v[k].y & 0xFFFFu;
+                c[3] += v[k].y >> 16;
+            }
         }
-        if (slow) atomicAdd(&stat_out[4], slow);
-        if (nover) { atomicAdd(&stat_out[2], nover); atomicAdd(&stat_out[3], sover); }
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (c[k]) atomicAdd(&bins[2 * w0 + k], c[k]);
+        uint32_t all = c[0] + c[1] + c[2] + c[3];
+        for (int d = 32; d >= 1; d >>= 1) all += __shfl_xor(all, d);
+        static_assert(kWave * 4 == kRadix, "a wave's bins are one top-8 bucket");
+        if (lane_id() == 0) class_top8[by * kRadix + (2u * w0) / (unsigned)kRadix] = all;
     }
-    tsum[tid] = sum;
-    for (int d = 32; d >= 1; d >>= 1) most = dmax(most, __shfl_xor(most, d));
-    // exclusive scan of one value per thread over 16 waves
-    const uint32_t incl = wave_scan_add(sum);
-    if (lane_id() == 63) part[wave_id()] = incl;
-    if (lane_id() == 0) pmax[wave_id()] = most;
+    // (release: this workgroup's counts before its ticket; acquire: every workgroup's counts after the last ticket)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __syncthreads();
-    if (tid < (unsigned)kRadix) {
-        totals_lo[tid] = lo[0][tid] + lo[1][tid] + lo[2][tid] + lo[3][tid];
-        totals_hi[tid] = tsum[4 * tid] + tsum[4 * tid + 1] + tsum[4 * tid + 2] + tsum[4 * tid + 3];
+    if (tid == 0) last = (atomicAdd(ticket, 1u) == gridDim.x - 1u) ? 1u : 0u;
+    __syncthreads();
+    if (!last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (tid < (unsigned)kRadix) lo[tid] = 0;
+    if (tid < 5u) sstat[tid] = 0;
+    uint32_t lo4[4] = {0, 0, 0, 0}, carry = 0;
+    uint32_t most = 0, slow = 0, nover = 0, sover = 0;
+    auto padded = [](unsigned i) { return i + i / (unsigned)kH16FinPer; };
+    for (int h = 0; h < 2; h++) {
+        uint32_t* const src = bins + h * kH16FinHalf;
+        __syncthreads();                                                             // (the tile's readers of the first half are done)
+#pragma unroll 4
+        for (int k = 0; k < kH16FinPer / 4; k++) {
+            // (four bins whose low digits are 4 tid .. 4 tid + 3 mod 256, whatever k: their column sums stay in registers)
+            const unsigned i = (unsigned)k * kH16FinBins + 4u * tid;
+            const uint4 v = *reinterpret_cast<const uint4*>(src + i);
+            lo4[0] += v.x; lo4[1] += v.y; lo4[2] += v.z; lo4[3] += v.w;
+            const unsigned at = padded(i);
+            tile[at] = v.x; tile[at + 1] = v.y; tile[at + 2] = v.z; tile[at + 3] = v.w;
+        }
+        __syncthreads();
+        uint32_t* const mine = tile + padded(tid * kH16FinPer);                      // (thread t's 64 bins: banks t + j)
+        uint32_t sum = 0;
+        for (int j = 0; j < kH16FinPer; j++) {
+            const uint32_t x = mine[j];
+            sum += x;
+            most = dmax(most, x);
+            if (x > fast) slow += x;
+            if (x > cap) { nover++; sover += x; }
+        }
+        const uint32_t incl = wave_scan_add(sum);
+        if (lane_id() == 63) part[wave_id()] = incl;
+        __syncthreads();
+        uint32_t run = carry + incl - sum, total = 0;
+        for (unsigned k = 0; k < (unsigned)kWaves; k++) {
+            if (k < wave_id()) run += part[k];
+            total += part[k];
+        }
+        carry += total;
+        static_assert(kRadix % kH16FinPer == 0, "a top-8 bucket begins with a thread's first bin");
+        if ((tid * kH16FinPer) % (unsigned)kRadix == 0u) {
+            const unsigned j = ((unsigned)h * kH16FinHalf + tid * kH16FinPer) / (unsigned)kRadix;
+            uint32_t at = run;
+            for (unsigned x = 0; x < kPartClasses; x++) {
+                cursor8[(x * kRadix + j) * kCursorPad] = at;
+                at += class_top8[x * kRadix + j];
+            }
+            totals_hi[j] = at - run;
+        }
+        for (int j = 0; j < kH16FinPer; j++) {
+            const uint32_t x = mine[j];
+            mine[j] = run;
+            run += x;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int k = 0; k < kH16FinPer / 4; k++) {
+            const unsigned i = (unsigned)k * kH16FinBins + 4u * tid, at = padded(i);
+            const uint4 v = uint4{tile[at], tile[at + 1], tile[at + 2], tile[at + 3]};
+            *reinterpret_cast<uint4*>(src + i) = v;
+            *reinterpret_cast<uint4*>(cursor16 + h * kH16FinHalf + i) = v;
+        }
     }
-    uint32_t base = 0;
-    for (unsigned k = 0; k < wave_id(); k++) base += part[k];
-    uint32_t run = base + incl - sum;
-    for (int j = 0; j < kPer; j++) { bins[tid * kPer + j] = run; run += v[j]; }
-    if (tid == kH16Threads - 1) { bins[kH16Bins] = run; stat_out[1] = run; }
+#pragma unroll
+    for (int k = 0; k < 4; k++) atomicAdd(&lo[(4u * tid + (unsigned)k) % (unsigned)kRadix], lo4[k]);
+    atomicMax(&sstat[0], most);
+    if (slow) atomicAdd(&sstat[4], slow);
+    if (nover) { atomicAdd(&sstat[2], nover); atomicAdd(&sstat[3], sover); }
+    __syncthreads();
+    if (tid < (unsigned)kRadix) totals_lo[tid] = lo[tid];
     if (tid == 0) {
-        uint32_t mx = 0;
-        for (unsigned k = 0; k < (unsigned)(kH16Threads / kWave); k++) mx = dmax(mx, pmax[k]);
-        stat_out[0] = mx;
+        bins[kH16Bins] = carry;
+        const uint32_t words[5] = {sstat[0], carry, sstat[2], sstat[3], sstat[4]};
+        for (int k = 0; k < 5; k++) stat_out[k] = words[k];
+        post_words_from_kernel(post, words, 5u);
     }
 }
 // (only when there are any:) the list of the sub-buckets of more than `cap` suffixes, in bin order, from the starts
@@ -1805,28 +1933,28 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
     const uint64_t room = m * sizeof(uint64_t) / (kH16Words * sizeof(uint32_t));     // partial histograms that fit e1
     if (room == 0) return SFX_OK;
     Chunking ch = make_chunking(nwords, kH16Threads, (unsigned)dmin<uint64_t>(room, 256));
-    SFX_HIP(hipMemsetAsync(scr.tickets, 0, 64 * sizeof(uint32_t), st));
-    SFX_HIP(hipMemsetAsync(bins, 0, (kH16Bins + 128) * sizeof(uint32_t), st));             // (the counts and the statistics)
+    const H16Zero zero = {bins, (uint32_t)(kH16Bins + 128), scr.tickets, 64u};             // (the counts and the statistics; the tickets)
     if (from_elems)
         SFX_LAUNCH("radix_hist16_elems", (double)m * 8.0, k_hist16_e64, ch.blocks, kH16Threads, st, (const uint64_t*)e0, m, top_hi - 16,
-                   ch.tiles_per_block * kH16Threads, partial);
+                   ch.tiles_per_block * kH16Threads, partial, zero);
     else
         SFX_LAUNCH("radix_hist16_text", (double)m * text.bits / 8.0, k_hist16_text, ch.blocks, kH16Threads, st, text, low_bits,
-                   ch.tiles_per_block * kH16Threads, partial);
+                   ch.tiles_per_block * kH16Threads, partial, zero);
     // (the rows of the partial counts in kPartClasses contiguous stretches: k_partition's first pass wants the top-8 counts of each)
-    static_assert(kH16ReduceSplit == kPartClasses, "one block group of the reduction per stretch");
     const unsigned rows_per_class = (ch.blocks + kPartClasses - 1) / kPartClasses;
     const uint64_t class_len = (uint64_t)rows_per_class * ch.tiles_per_block * kH16Threads * (from_elems ? 1u : (uint64_t)text.spw);
     uint32_t* cursor16 = bins + kH16Bins + 128 + 4 * kOversizeMax;     // (behind the oversize list)
     uint32_t* class_top8 = cursor16 + kH16Bins;
     uint32_t* cursor8 = class_top8 + kPartClasses * kRadix;
     static_assert(kH16Bins + 128 + 4 * kOversizeMax + kH16Bins + kPartClasses * kRadix * (1 + kCursorPad) <= kReserve, "the reserve holds the cursors too");
-    SFX_LAUNCH("radix_hist16_reduce", (double)ch.blocks * kH16Words * 4, k_hist16_reduce, (kH16Bins / kH16ReduceBins) * kH16ReduceSplit, kBlock, st,
-               (const uint32_t*)partial, ch.blocks, bins, rows_per_class, class_top8);
-    SFX_LAUNCH("radix_hist16_scan", (double)kH16Bins * 8, k_hist16_scan, 1, kH16Threads, st, bins, scr.totals, scr.totals + kRadix,
-               stat, cap, dmin(cap, 4096u));
+    // sub-bucket starts, digit totals, the cursors of both partition passes and the statistics, posted to the host by the kernel
+    // itself: one launch (k_hist16_finish); its ticket is a zeroed word behind the statistics
     uint32_t host_stat[5] = {0, 0, 0, 0, 0};
-    SFX_TRY(read_back(host_stat, stat, sizeof(host_stat), st));
+    const PostTicket post = post_ticket();
+    SFX_LAUNCH("radix_hist16_finish", (double)ch.blocks * kH16Words * 4 + (double)kH16Bins * 12, k_hist16_finish,
+               (kH16Bins / kH16FinBins) * kPartClasses, kH16FinThreads, st, (const uint32_t*)partial, ch.blocks, rows_per_class, bins, class_top8,
+               stat + 16, scr.totals, scr.totals + kRadix, stat, cap, dmin(cap, 4096u), cursor16, cursor8, post);
+    SFX_TRY(read_posted(host_stat, stat, sizeof(host_stat), post, st));
     const uint32_t host_max = host_stat[0], nover = host_stat[2];
     const uint64_t nlarge = host_stat[3], nslow = host_stat[4];
     // A 16-bit counter wrapped, or more than 1/64 of the text sits in sub-buckets of more than 4096 suffixes: four
@@ -1870,8 +1998,6 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
         // two partition passes (k_partition: no order inside a sub-bucket, none needed): top 8 bits, then the next 8 inside
         // every top-8 bucket; cursors behind the oversize list
         constexpr int kPKpt = 16;
-        SFX_LAUNCH("partition_cursors", (double)kH16Bins * 8, k_partition_cursors, kH16Bins / kBlock, kBlock, st, (const uint32_t*)bins,
-                   (const uint32_t*)class_top8, cursor16, cursor8);
         static const unsigned cus = [] {
             int dev = 0, n = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
@@ -1898,12 +2024,27 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
                            SrcE64{e1}, e0, m, top_hi - 16, cursor16, (const uint32_t*)bins, class_len);
                 uint64_t* t = e0; e0 = e1; e1 = t;             // (from here on: e1 = the array grouped by its top 16 bits, e0 = free)
             } else {
-                if (extra)
-                    SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0), (k_partition<SrcText36, kPKpt, kPNw, false>),
-                               g1, kPNw * kWave, st, SrcText36{text, extra, wide_key}, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
-                else
-                    SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0), (k_partition<SrcText32, kPKpt, kPNw, false>),
-                               g1, kPNw * kWave, st, SrcText32{text}, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
+                // (whole words of 1, 2, 4 or 8-bit symbols and stretches that begin on word boundaries -- class_len is a multiple of
+                // 1024 spw by construction: the tile loader; anything else, and the 16- and 4-wave geometries of the tests: src.key())
+                const int loader_spw = (kPNw == 8 && text.bits * text.spw == 32 && text.kbits == 32 && !wide_key &&
+                                        class_len % (uint64_t)text.spw == 0) ? text.spw : 0;
+                auto text_pass = [&](auto tsrc, auto spw) -> int {
+                    SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0),
+                               (k_partition<decltype(tsrc), kPKpt, kPNw, false, (kPNw == 8 ? decltype(spw)::value : 0)>), g1, kPNw * kWave, st,
+                               tsrc, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
+                    return SFX_OK;
+                };
+                auto text_pass_of = [&](auto tsrc) -> int {
+                    switch (loader_spw) {
+                    case 32: return text_pass(tsrc, std::integral_constant<int, 32>{});
+                    case 16: return text_pass(tsrc, std::integral_constant<int, 16>{});
+                    case 8: return text_pass(tsrc, std::integral_constant<int, 8>{});
+                    case 4: return text_pass(tsrc, std::integral_constant<int, 4>{});
+                    default: return text_pass(tsrc, std::integral_constant<int, 0>{});
+                    }
+                };
+                if (extra) SFX_TRY(text_pass_of(SrcText36{text, extra, wide_key}));
+                else SFX_TRY(text_pass_of(SrcText32{text}));
                 SFX_LAUNCH("radix_scatter_u32", (double)m * 16.0, (k_partition<SrcE64, kPKpt, kPNw, true>), g2, kPNw * kWave, st,
                            SrcE64{e0}, e1, m, top_hi - 16, cursor16, (const uint32_t*)bins, class_len);
             }
