@@ -295,6 +295,47 @@ int sfx_repeat_lens_u32(const uint32_t* sa, const uint32_t* lcp, const uint32_t*
 int sfx_repeat_spans_u32(const uint32_t* rep, uint64_t n, uint32_t min_len, const uint64_t* doc_starts, uint64_t ndocs,
                          uint32_t* begin_out, uint32_t* end_out, uint64_t capacity, uint64_t* count_out);
 
+/* ---- matching statistics: which parts of a NEW text Q already stand in the indexed text T ----------------
+ * T = the indexed text of n bytes with suffix array sa; Q = a query text of m bytes; max_len = the caller's cap on a
+ * match, 0 = none.  For every i in [0, m), with lim = m - i (max_len == 0) or min(max_len, m - i):
+ *   len[i]            the largest l <= lim such that Q[i .. i + l) occurs in T;
+ *   start[i], end[i]  the rank range of the suffixes that begin with Q[i .. i + len[i]) -- what positions() of that
+ *                     pattern returns; 0 / 0 where len[i] == 0 (the empty query is empty);
+ *   src[i]            one text position where those len[i] bytes stand, UINT32_MAX where len[i] == 0.  WHICH
+ *                     occurrence is arbitrary by contract, as for any_position.
+ * For a collection (sfx_gindex) an occurrence lies inside ONE document (the truncated suffixes of sfx_build_gsa_u32);
+ * ranks are GSA ranks.  len, start and end are determined by (T, sa, Q, max_len) alone: two calls, two entry points or
+ * two streams give the same bytes; a capped len is min(uncapped len, max_len).  The arrays are rep-shaped:
+ * sfx_repeat_spans_dev(len, m, L, ...) lists the spans of Q that occur in T with at least L bytes, and for that report
+ * max_len = L is enough (the covered bytes are the same for every cap >= L).
+ * Arguments: d_len is required; d_src may be NULL; d_start and d_end are both given or both NULL (exactly one NULL is
+ * SFX_ERR_ARG).  m == 0 is SFX_OK and writes nothing.  n == 0 gives len = 0, src = UINT32_MAX and 0 / 0 everywhere.
+ * m > u32::MAX (or n > u32::MAX) is SFX_ERR_TOO_LARGE, whatever the pointers are.  d_query may have any alignment;
+ * the u32 arrays need 4 bytes.
+ * The _dev calls queue everything on the caller's stream, allocate nothing, keep no state in the index, read nothing
+ * back and DO NOT SYNCHRONISE: any number of threads may call on one index at once.  Nothing is read outside
+ * [d_query, d_query + m), [d_text, d_text + n) and d_sa[0 .. n) (for a collection also its doc_starts and DA); nothing
+ * is written outside the m entries of each output.
+ * sfx_match_stats_dev takes text and table as they are, like sfx_query_batch_dev: a table entry >= n reaches the
+ * kernel unchecked and is read out of bounds (the reference's from_parts "fails in weird ways", :105-107) -- hand it
+ * a table the engine built, or go through an index: the two index entries rely on the check made at index creation.
+ * Cost: one bisection per position, O(log n + len[i]) compared bytes (each probe starts at the bytes its two bounds
+ * already share), plus O(len[i] log(end - start)) for the interval.  An UNCAPPED call with Q = T is therefore quadratic
+ * on a repetitive text: max_len is the caller's bound. */
+int sfx_match_stats_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
+                        const uint8_t* d_query, uint64_t m, uint32_t max_len,
+                        uint32_t* d_len, uint32_t* d_src /* may be NULL */, uint32_t* d_start, uint32_t* d_end /* both or neither */,
+                        void* stream);
+int sfx_index_match_stats_dev(const sfx_index* ix, const uint8_t* d_query, uint64_t m, uint32_t max_len,
+                              uint32_t* d_len, uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, void* stream);
+int sfx_gindex_match_stats_dev(const sfx_gindex* gx, const uint8_t* d_query, uint64_t m, uint32_t max_len,
+                               uint32_t* d_len, uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, void* stream);
+/* the same with host buffers, staged through HBM (these synchronise their own stream) */
+int sfx_index_match_stats(const sfx_index* ix, const uint8_t* query, uint64_t m, uint32_t max_len,
+                          uint32_t* len_out, uint32_t* src_out, uint32_t* start_out, uint32_t* end_out);
+int sfx_gindex_match_stats(const sfx_gindex* gx, const uint8_t* query, uint64_t m, uint32_t max_len,
+                           uint32_t* len_out, uint32_t* src_out, uint32_t* start_out, uint32_t* end_out);
+
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the
  * text shard [shard_begin, shard_end).

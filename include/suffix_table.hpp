@@ -151,6 +151,38 @@ public:
         return out;
     }
 
+    // additive: matching statistics of a second text against this one (suffix_hip.h): len[i] = the longest prefix of
+    // query[i..] (at most max_len bytes, 0 = no cap) that occurs in the text, src[i] = one position where it stands
+    // (UINT32_MAX where len[i] == 0; which occurrence is arbitrary).  The cost grows with the lengths found.
+    struct MatchStats { std::vector<uint32_t> len, src; };
+    MatchStats match_stats(std::string_view query, uint32_t max_len = 0) const
+    {
+        MatchStats ms{std::vector<uint32_t>(query.size(), 0u), std::vector<uint32_t>(query.size(), 0xFFFFFFFFu)};
+        if (!query.empty() && !text_.empty())
+            check(sfx_index_match_stats(index(), reinterpret_cast<const uint8_t*>(query.data()), query.size(), max_len, ms.len.data(),
+                                        ms.src.data(), nullptr, nullptr), "match_stats");
+        return ms;
+    }
+    // additive: [begin, end) in query coordinates, ascending: the maximal runs of query bytes inside a stretch of at least
+    // min_len bytes that also occurs in the text -- the search capped at min_len, then the span report of the repeats
+    std::vector<std::pair<uint32_t, uint32_t>> shared_spans(std::string_view query, uint32_t min_len) const
+    {
+        if (min_len == 0) throw std::invalid_argument("shared_spans: min_len must be at least 1");
+        return spans_of(match_stats(query, min_len).len, min_len);
+    }
+    // the spans of a rep-shaped array (repeat_lens, match_stats().len) at min_len >= 1
+    static std::vector<std::pair<uint32_t, uint32_t>> spans_of(const std::vector<uint32_t>& rep, uint32_t min_len)
+    {
+        if (min_len == 0) throw std::invalid_argument("spans_of: min_len must be at least 1");
+        const uint64_t cap = rep.size() / min_len + 1;                               // every run is at least min_len long
+        std::vector<uint32_t> b(cap), e(cap);
+        uint64_t count = 0;
+        check(sfx_repeat_spans_u32(rep.data(), rep.size(), min_len, nullptr, 0, b.data(), e.data(), cap, &count), "spans_of");
+        std::vector<std::pair<uint32_t, uint32_t>> out((size_t)count);
+        for (size_t k = 0; k < out.size(); k++) out[k] = {b[k], e[k]};
+        return out;
+    }
+
 private:
     SuffixTable() = default;
     static const uint8_t* bytes(const std::string& s) { return reinterpret_cast<const uint8_t*>(s.data()); }

@@ -50,6 +50,16 @@ extern "C" {
                            start_out: *mut u32, end_out: *mut u32) -> c_int;
     fn sfx_contains_batch(ix: *const SfxIndex, qbytes: *const u8, qoff: *const u64, nq: u64,
                           found_out: *mut u8, any_out: *mut u32) -> c_int;
+    // matching statistics of a second text against the resident index (host buffers; src / start+end may be null)
+    fn sfx_index_match_stats(ix: *const SfxIndex, query: *const u8, m: u64, max_len: u32, len_out: *mut u32,
+                             src_out: *mut u32, start_out: *mut u32, end_out: *mut u32) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_index_match_stats_dev(ix: *const SfxIndex, d_query: *const u8, m: u64, max_len: u32, d_len: *mut u32,
+                                 d_src: *mut u32, d_start: *mut u32, d_end: *mut u32, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_match_stats_dev(d_text: *const u8, n: u64, d_sa: *const u32, d_query: *const u8, m: u64, max_len: u32,
+                           d_len: *mut u32, d_src: *mut u32, d_start: *mut u32, d_end: *mut u32,
+                           stream: *mut c_void) -> c_int;
     // suffix_tree's node table with ordered children (children(), preorder(), leaves(), suffix_indices() read it)
     #[allow(dead_code)]
     fn sfx_suffix_tree_u32(text: *const u8, sa: *const u32, lcp: *const u32, n: u64, node_capacity: u64,
@@ -182,6 +192,18 @@ impl DeviceIndex {
                                f.as_mut_ptr(), std::ptr::null_mut())
         }, "sfx_contains_batch");
         f.into_iter().map(|b| b != 0).collect()
+    }
+    /// Additive API: the matching statistics of `query` against the indexed text.  `len[i]` = the longest prefix of
+    /// `query[i..]` (at most `max_len` bytes, 0 = no cap) that occurs in the text; `src[i]` = one position where it
+    /// stands, `u32::MAX` where `len[i] == 0`.  The cost grows with the lengths found: cap a query that may repeat the text.
+    pub fn match_stats(&self, query: &[u8], max_len: u32) -> (Vec<u32>, Vec<u32>) {
+        assert!(query.len() <= u32::MAX as usize);
+        let (mut len, mut src) = (vec![0u32; query.len()], vec![u32::MAX; query.len()]);
+        check(unsafe {
+            sfx_index_match_stats(self.0, query.as_ptr(), query.len() as u64, max_len, len.as_mut_ptr(),
+                                  src.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut())
+        }, "sfx_index_match_stats");
+        (len, src)
     }
 }
 impl DeviceIndex {

@@ -88,6 +88,11 @@ ABI = [
     ("sfx_repeat_spans_dev", _int, [_vp, _u64, _u32, _vp, _u64, _vp, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64, _vp]),
     ("sfx_repeat_lens_u32", _int, [_vp, _vp, _vp, _u64, _int, _vp, _vp]),
     ("sfx_repeat_spans_u32", _int, [_vp, _u64, _u32, _vp, _u64, _vp, _vp, _u64, ctypes.POINTER(_u64)]),
+    ("sfx_match_stats_dev", _int, [_vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("sfx_index_match_stats_dev", _int, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("sfx_gindex_match_stats_dev", _int, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("sfx_index_match_stats", _int, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp]),
+    ("sfx_gindex_match_stats", _int, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),

@@ -646,6 +646,73 @@ int sfx_contains_batch(const sfx_index* ix, const uint8_t* qbytes, const uint64_
     return query_host(ix, qbytes, qoff, nq, nullptr, nullptr, found_out, any_out);
 }
 
+// ---- matching statistics of a query text (include/suffix_hip.h) -------------------------------
+// Pure launches on the caller's stream: nothing is allocated, read back or kept in the index.  The index entry starts
+// every bisection inside the bucket directory's stretch (DESIGN.md section 16 says why the key tree stays out of it) and
+// relies on the table check made when the index was created.
+int sfx_match_stats_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint8_t* d_query, uint64_t m,
+                        uint32_t max_len, uint32_t* d_len, uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, void* stream)
+{
+    SFX_NEED_U32(d_sa, d_len, d_src, d_start, d_end);
+    return match_stats_dev(d_text, n, d_sa, d_query, m, max_len, d_len, d_src, d_start, d_end, (hipStream_t)stream);
+}
+int sfx_index_match_stats_dev(const sfx_index* ix, const uint8_t* d_query, uint64_t m, uint32_t max_len, uint32_t* d_len,
+                              uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, void* stream)
+{
+    SFX_NEED_U32(d_len, d_src, d_start, d_end);
+    if (!ix) return SFX_ERR_ARG;
+    return match_stats_dir_dev(ix->d_text, ix->n, ix->d_sa, ix->d_dir, ix->d_lut, ix->bits, ix->k, ix->dbits, d_query, m, max_len,
+                               d_len, d_src, d_start, d_end, (hipStream_t)stream);
+}
+int sfx_gindex_match_stats_dev(const sfx_gindex* gx, const uint8_t* d_query, uint64_t m, uint32_t max_len, uint32_t* d_len,
+                               uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, void* stream)
+{
+    SFX_NEED_U32(d_len, d_src, d_start, d_end);
+    if (!gx) return SFX_ERR_ARG;
+    return gindex_match_stats_dev(gx->d_text, gx->n, gx->d_starts, gx->ndocs, gx->d_sa, gx->d_da, d_query, m, max_len, d_len,
+                                  d_src, d_start, d_end, (hipStream_t)stream);
+}
+// host buffers staged through HBM on the calling thread's stream; exactly one of ix / gx is given
+static int match_stats_host(const sfx_index* ix, const sfx_gindex* gx, const uint8_t* query, uint64_t m, uint32_t max_len,
+                            uint32_t* len_out, uint32_t* src_out, uint32_t* start_out, uint32_t* end_out)
+{
+    if (!ix && !gx) return SFX_ERR_ARG;
+    if (m > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if ((start_out == nullptr) != (end_out == nullptr)) return SFX_ERR_ARG;
+    if (m == 0) return SFX_OK;
+    if (!query || !len_out) return SFX_ERR_ARG;
+    DevBuf dq, dl, ds, da, de;
+    SFX_TRY(dq.alloc(m));
+    SFX_TRY(dl.alloc(m * 4));
+    if (src_out) SFX_TRY(ds.alloc(m * 4));
+    if (start_out) { SFX_TRY(da.alloc(m * 4)); SFX_TRY(de.alloc(m * 4)); }
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(dq.p, query, m, hipMemcpyHostToDevice, st));
+    if (ix)
+        SFX_TRY(sfx_index_match_stats_dev(ix, (const uint8_t*)dq.p, m, max_len, (uint32_t*)dl.p, (uint32_t*)ds.p, (uint32_t*)da.p,
+                                          (uint32_t*)de.p, st));
+    else
+        SFX_TRY(sfx_gindex_match_stats_dev(gx, (const uint8_t*)dq.p, m, max_len, (uint32_t*)dl.p, (uint32_t*)ds.p, (uint32_t*)da.p,
+                                           (uint32_t*)de.p, st));
+    SFX_HIP(hipMemcpyAsync(len_out, dl.p, m * 4, hipMemcpyDeviceToHost, st));
+    if (src_out) SFX_HIP(hipMemcpyAsync(src_out, ds.p, m * 4, hipMemcpyDeviceToHost, st));
+    if (start_out) SFX_HIP(hipMemcpyAsync(start_out, da.p, m * 4, hipMemcpyDeviceToHost, st));
+    if (end_out) SFX_HIP(hipMemcpyAsync(end_out, de.p, m * 4, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+int sfx_index_match_stats(const sfx_index* ix, const uint8_t* query, uint64_t m, uint32_t max_len, uint32_t* len_out,
+                          uint32_t* src_out, uint32_t* start_out, uint32_t* end_out)
+{
+    return match_stats_host(ix, nullptr, query, m, max_len, len_out, src_out, start_out, end_out);
+}
+int sfx_gindex_match_stats(const sfx_gindex* gx, const uint8_t* query, uint64_t m, uint32_t max_len, uint32_t* len_out,
+                           uint32_t* src_out, uint32_t* start_out, uint32_t* end_out)
+{
+    return match_stats_host(nullptr, gx, query, m, max_len, len_out, src_out, start_out, end_out);
+}
+
 // ---- suffix-tree topology, generalized suffix array -------------------------------------------
 uint64_t sfx_lcp_intervals_workspace_bytes(uint64_t n) { return lcp_intervals_workspace_bytes(n); }
 int sfx_lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_t* d_rb, uint32_t* d_node,

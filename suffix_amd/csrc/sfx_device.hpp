@@ -400,4 +400,121 @@ __host__ __device__ inline int bits_for(uint64_t v)
     return b ? b : 1;
 }
 
+// ---- matching statistics: one pattern against a sorted table (k_ms_search in sfx_query.hip, k_ms_gsa_search in
+// sfx_tree.hip) --------------------------------------------------------------------------------
+// length of the common prefix of a[0..lim) and b[0..lim), which agree on their first k <= lim bytes: 8 bytes per step
+// (unaligned loads; little-endian, so the first differing byte is the lowest non-zero byte of the XOR), then a tail
+// loop.  Nothing is read past a + lim or b + lim.
+__device__ __forceinline__ uint64_t ms_extend(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t k, uint64_t lim)
+{
+    while (k + 8 <= lim) {
+        uint64_t x, y;
+        __builtin_memcpy(&x, a + k, 8);
+        __builtin_memcpy(&y, b + k, 8);
+        const uint64_t d = x ^ y;
+        if (d) return k + ((uint64_t)(__ffsll((long long)d) - 1) >> 3);
+        k += 8;
+    }
+    while (k < lim && a[k] == b[k]) k++;
+    return k;
+}
+struct MsAnswer { uint32_t len, src, start, end; };
+// The longest prefix of p[0..lim) that stands in the table's text, where, and the rank range of the suffixes that begin
+// with it.  `suf.len(r, s)` = the length of the suffix at rank r (position s): to the end of the text for a plain table,
+// to the end of its document for a collection -- the order of the table is the order of those truncated suffixes.
+//   1. Bisection for the insertion rank of p (ranks below hold suffixes < p, a proper prefix of p among them; ranks from
+//      it on suffixes >= p).  l / r = the common prefix of p with the suffix just below lo / at hi: every suffix between
+//      the two shares min(l, r) bytes with p, so a probe starts comparing there.
+//   2. The longest match is the longer of the two neighbours of the insertion rank.
+//   3. (want_iv) "begins with p[0..len)" is true on one run of ranks that touches the insertion rank from either side:
+//      gallop outwards from it, then bisect the last step.
+// [lo0, hi0] = ranks known to hold the insertion rank (the whole table, or the stretch of a bucket directory: every
+// suffix below lo0 is smaller than p, every one from hi0 on larger).  Nothing is known about the suffixes just outside
+// a stretch, so a bound that never moves is compared once at the end -- an empty stretch is answered by those two
+// compares alone -- and the interval of step 3 is searched over the whole table, never inside the stretch: the match
+// may be shorter than the directory's key and its interval wider than any one bucket.
+template <class Suf>
+__device__ __forceinline__ MsAnswer ms_search(const uint8_t* __restrict__ text, const uint32_t* __restrict__ sa, uint64_t n,
+                                              const uint8_t* __restrict__ p, uint64_t lim, const Suf& suf, bool want_iv,
+                                              uint64_t lo0, uint64_t hi0)
+{
+    uint64_t lo = lo0, hi = hi0, l = 0, r = 0;
+    uint32_t sl = 0xFFFFFFFFu, sr = 0xFFFFFFFFu;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        const uint32_t s = sa[mid];
+        const uint64_t slen = suf.len(mid, s);
+        const uint64_t k = ms_extend(p, text + s, dmin(l, r), dmin(lim, slen));
+        // the suffix is >= p: p is its prefix, or its next byte is the larger one (a suffix that ends here sorts first)
+        const bool ge = k == lim || (k < slen && text[s + k] > p[k]);
+        if (ge) { hi = mid; r = k; sr = s; } else { lo = mid + 1; l = k; sl = s; }
+    }
+    if (lo == lo0 && lo > 0) {                                         // the lower bound never moved: rank lo - 1 was not seen
+        sl = sa[lo - 1];
+        l = ms_extend(p, text + sl, 0, dmin(lim, suf.len(lo - 1, sl)));
+    }
+    if (lo == hi0 && lo < n) {                                         // nor was rank hi
+        sr = sa[lo];
+        r = ms_extend(p, text + sr, 0, dmin(lim, suf.len(lo, sr)));
+    }
+    MsAnswer ans;
+    const uint64_t len = dmax(l, r);
+    ans.len = (uint32_t)len;
+    ans.src = len == 0 ? 0xFFFFFFFFu : (l >= r ? sl : sr);
+    ans.start = ans.end = 0;
+    if (len == 0 || !want_iv) return ans;
+    auto match = [&](uint64_t rank) {
+        const uint32_t s = sa[rank];
+        return suf.len(rank, s) >= len && ms_extend(p, text + s, 0, len) == len;
+    };
+    uint64_t start = lo, end = lo;
+    if (l == len) {                                                   // rank lo - 1 matches: the ranks [lo - cnt, lo) do
+        uint64_t cnt = 1, step = 1;
+        bool room;
+        while ((room = lo - cnt >= step) && match(lo - cnt - step)) { cnt += step; step <<= 1; }
+        uint64_t a = room ? lo - cnt - step + 1 : 0, b = lo - cnt;    // the first match lies in [a, b]; b is one
+        while (a < b) {
+            const uint64_t mid = (a + b) >> 1;
+            if (match(mid)) b = mid; else a = mid + 1;
+        }
+        start = a;
+    }
+    if (r == len) {                                                   // rank lo matches: the ranks [lo, lo + cnt) do
+        uint64_t cnt = 1, step = 1;
+        while (lo + cnt - 1 + step < n && match(lo + cnt - 1 + step)) { cnt += step; step <<= 1; }
+        uint64_t a = lo + cnt, b = dmin(n, lo + cnt - 1 + step);      // the end lies in [a, b]
+        while (a < b) {
+            const uint64_t mid = (a + b) >> 1;
+            if (!match(mid)) b = mid; else a = mid + 1;
+        }
+        end = a;
+    }
+    ans.start = (uint32_t)start;
+    ans.end = (uint32_t)end;
+    return ans;
+}
+// no narrowing: the whole table
+struct MsWholeTable {
+    __device__ __forceinline__ void stretch(const uint8_t*, uint64_t, uint64_t n, uint64_t& lo, uint64_t& hi) const { lo = 0; hi = n; }
+};
+// one lane per query position i, grid-stride: the pattern is q[i .. i + lim), lim = min(max_len, m - i) (max_len 0: no cap);
+// `where.stretch(p, lim, n, lo, hi)` gives the ranks the bisection starts from
+template <class Suf, class Where>
+__device__ __forceinline__ void ms_positions(const uint8_t* __restrict__ text, const uint32_t* __restrict__ sa, uint64_t n,
+                                             const uint8_t* __restrict__ q, uint64_t m, uint32_t max_len, const Suf& suf,
+                                             const Where& where, uint32_t* __restrict__ len_out, uint32_t* __restrict__ src_out,
+                                             uint32_t* __restrict__ start_out, uint32_t* __restrict__ end_out)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += stride) {
+        const uint64_t lim = max_len ? dmin<uint64_t>(max_len, m - i) : m - i;
+        uint64_t lo0, hi0;
+        where.stretch(q + i, lim, n, lo0, hi0);
+        const MsAnswer a = ms_search(text, sa, n, q + i, lim, suf, start_out != nullptr, lo0, hi0);
+        len_out[i] = a.len;
+        if (src_out) src_out[i] = a.src;
+        if (start_out) { start_out[i] = a.start; end_out[i] = a.end; }
+    }
+}
+
 }  // namespace sfx

@@ -446,6 +446,17 @@ int build_lcp_u32_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, u
 int query_batch_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint64_t sa_len,
                     const uint8_t* d_q, const uint64_t* d_qoff, uint64_t nq, uint32_t* d_start,
                     uint32_t* d_end, uint8_t* d_found, uint32_t* d_any, hipStream_t st);
+// matching statistics of a query text (sfx_query.hip; the collection's in sfx_tree.hip): no workspace, no read-back
+int ms_check_args(uint64_t n, const void* d_text, const void* d_sa, const void* d_q, uint64_t m, const void* d_len,
+                  const void* d_start, const void* d_end, bool* run);
+int match_stats_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint8_t* d_q, uint64_t m, uint32_t max_len,
+                    uint32_t* d_len, uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, hipStream_t st);
+int match_stats_dir_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint32_t* d_dir, const uint16_t* d_lut256,
+                        int bits, int k, int dbits, const uint8_t* d_q, uint64_t m, uint32_t max_len, uint32_t* d_len,
+                        uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, hipStream_t st);
+int gindex_match_stats_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, const uint32_t* d_sa,
+                           const uint32_t* d_da, const uint8_t* d_q, uint64_t m, uint32_t max_len, uint32_t* d_len,
+                           uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, hipStream_t st);
 // bucket directory of the resident index (sfx_query.hip)
 int dir_shape(uint64_t n, int bits, int* k_out, int* dbits_out, uint64_t* entries_out);
 uint64_t dir_scratch_words(uint64_t entries);

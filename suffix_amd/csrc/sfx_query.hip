@@ -836,6 +836,95 @@ int query_batch_tree_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa
     return SFX_OK;
 }
 
+// ---- matching statistics of a query text against the table (include/suffix_hip.h) -----------
+// One lane per query position; the search itself is ms_search (sfx_device.hpp), shared with the collection's kernel
+// in sfx_tree.hip.  A plain table's suffix runs to the end of the text.
+struct MsPlainSuffix {
+    uint64_t n;
+    __device__ __forceinline__ uint64_t len(uint64_t, uint32_t s) const { return n - s; }
+};
+__global__ void __launch_bounds__(kBlock)
+k_ms_search(const uint8_t* __restrict__ text, uint64_t n, const uint32_t* __restrict__ sa, const uint8_t* __restrict__ q,
+            uint64_t m, uint32_t max_len, uint32_t* __restrict__ len_out, uint32_t* __restrict__ src_out,
+            uint32_t* __restrict__ start_out, uint32_t* __restrict__ end_out)
+{
+    ms_positions(text, sa, n, q, m, max_len, MsPlainSuffix{n}, MsWholeTable{}, len_out, src_out, start_out, end_out);
+}
+// Through the resident index the bisection starts inside the bucket directory's stretch of the pattern's first k symbols:
+// buckets are in suffix order (a suffix shorter than the key is padded with the smallest code and sorts first among the
+// suffixes it imitates), so every suffix of a lower bucket is smaller than the pattern and every one of a higher bucket
+// larger.  A pattern with a byte the text does not hold among those symbols, or with fewer than k symbols left, has no
+// bucket: it searches the whole table, as sfx_match_stats_dev does.
+struct MsDirStretch {
+    DirParams dp;
+    __device__ __forceinline__ void stretch(const uint8_t* __restrict__ p, uint64_t lim, uint64_t n, uint64_t& lo, uint64_t& hi) const
+    {
+        lo = 0;
+        hi = n;
+        if (lim < (uint64_t)dp.k) return;
+        uint64_t c = 0;
+        for (int j = 0; j < dp.k; j++) {
+            const uint32_t sym = dp.lut[p[j]];
+            if (sym == 0u) return;
+            c = (c << dp.bits) | (uint64_t)(sym - 1u);
+        }
+        c >>= dp.k * dp.bits - dp.dbits;
+        lo = dp.dir[c];
+        hi = dp.dir[c + 1];
+    }
+};
+__global__ void __launch_bounds__(kBlock)
+k_ms_search_dir(const uint8_t* __restrict__ text, uint64_t n, const uint32_t* __restrict__ sa, DirParams dp,
+                const uint8_t* __restrict__ q, uint64_t m, uint32_t max_len, uint32_t* __restrict__ len_out,
+                uint32_t* __restrict__ src_out, uint32_t* __restrict__ start_out, uint32_t* __restrict__ end_out)
+{
+    ms_positions(text, sa, n, q, m, max_len, MsPlainSuffix{n}, MsDirStretch{dp}, len_out, src_out, start_out, end_out);
+}
+// the argument rules every matching-statistics entry point shares; *run = false: nothing to launch
+int ms_check_args(uint64_t n, const void* d_text, const void* d_sa, const void* d_q, uint64_t m, const void* d_len,
+                  const void* d_start, const void* d_end, bool* run)
+{
+    *run = false;
+    if (m > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if ((d_start == nullptr) != (d_end == nullptr)) return SFX_ERR_ARG;
+    if (m == 0) return SFX_OK;
+    if (!d_len || !d_q || (n && (!d_text || !d_sa))) return SFX_ERR_ARG;
+    *run = true;
+    return SFX_OK;
+}
+int match_stats_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint8_t* d_q, uint64_t m, uint32_t max_len,
+                    uint32_t* d_len, uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, hipStream_t st)
+{
+    bool run = false;
+    SFX_TRY(ms_check_args(n, d_text, d_sa, d_q, m, d_len, d_start, d_end, &run));
+    if (!run) return SFX_OK;
+    const unsigned grid = (unsigned)dmin<uint64_t>((m + kBlock - 1) / kBlock, kMaxGrid);
+    // log2 n probes of an SA entry and a text line, then the interval's
+    const double probes = (double)bits_for(n ? n : 1) * (d_start ? 2.0 : 1.0);
+    SFX_LAUNCH("ms_search", (double)m * probes * 12.0, k_ms_search, grid, kBlock, st, d_text, n, d_sa, d_q, m, max_len, d_len,
+               d_src, d_start, d_end);
+    return SFX_OK;
+}
+// the same through the index's directory; a cap below the directory's k symbols leaves no position a bucket, and the
+// undirected kernel runs
+int match_stats_dir_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint32_t* d_dir, const uint16_t* d_lut256,
+                        int bits, int k, int dbits, const uint8_t* d_q, uint64_t m, uint32_t max_len, uint32_t* d_len,
+                        uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, hipStream_t st)
+{
+    if (n == 0 || !d_dir || !d_lut256 || (max_len && max_len < (uint32_t)k))
+        return match_stats_dev(d_text, n, d_sa, d_q, m, max_len, d_len, d_src, d_start, d_end, st);
+    bool run = false;
+    SFX_TRY(ms_check_args(n, d_text, d_sa, d_q, m, d_len, d_start, d_end, &run));
+    if (!run) return SFX_OK;
+    const unsigned grid = (unsigned)dmin<uint64_t>((m + kBlock - 1) / kBlock, kMaxGrid);
+    // one directory read, the probes inside a bucket (about a quarter of the table's ranks have one of their own), two edges
+    const double probes = 1.0 + (double)dmax(2, bits_for(n) - dbits) + 2.0 + (d_start ? 4.0 : 0.0);
+    DirParams dp = {d_dir, d_lut256, bits, k, dbits};
+    SFX_LAUNCH("ms_search_dir", (double)m * probes * 12.0, k_ms_search_dir, grid, kBlock, st, d_text, n, d_sa, dp, d_q, m, max_len,
+               d_len, d_src, d_start, d_end);
+    return SFX_OK;
+}
+
 // sa_len == n: the whole suffix array.  sa_len < n: a contiguous SLICE of it (one rank of
 // the range-partitioned index); start/end are then positions inside the slice.
 int query_batch_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint64_t sa_len, const uint8_t* d_q,

@@ -717,6 +717,37 @@ k_gsa_query(const uint8_t* __restrict__ text, uint64_t n, const uint64_t* __rest
         if (d_len) d_len[k] = (uint32_t)(hi - lo);
     }
 }
+// matching statistics of a query text against the collection: ms_search (sfx_device.hpp) over the TRUNCATED suffixes, so
+// a match stops at the end of its document as gsa_cmp's does; ranks are GSA ranks
+struct MsDocSuffix {
+    const uint64_t* starts;
+    const uint32_t* da;
+    uint64_t ndocs, n;
+    __device__ __forceinline__ uint64_t len(uint64_t r, uint32_t s) const { return gsa_doc_end(starts, ndocs, n, da[r]) - s; }
+};
+__global__ void __launch_bounds__(kBlock)
+k_ms_gsa_search(const uint8_t* __restrict__ text, uint64_t n, const uint64_t* __restrict__ starts, uint64_t ndocs,
+                const uint32_t* __restrict__ sa, const uint32_t* __restrict__ da, const uint8_t* __restrict__ q, uint64_t m,
+                uint32_t max_len, uint32_t* __restrict__ len_out, uint32_t* __restrict__ src_out,
+                uint32_t* __restrict__ start_out, uint32_t* __restrict__ end_out)
+{
+    ms_positions(text, sa, n, q, m, max_len, MsDocSuffix{starts, da, ndocs, n}, MsWholeTable{}, len_out, src_out, start_out, end_out);
+}
+int gindex_match_stats_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, const uint32_t* d_sa,
+                           const uint32_t* d_da, const uint8_t* d_q, uint64_t m, uint32_t max_len, uint32_t* d_len,
+                           uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, hipStream_t st)
+{
+    bool run = false;
+    SFX_TRY(ms_check_args(n, d_text, d_sa, d_q, m, d_len, d_start, d_end, &run));
+    if (!run) return SFX_OK;
+    if (n && (!d_starts || !d_da || ndocs == 0)) return SFX_ERR_ARG;
+    const unsigned grid = (unsigned)dmin<uint64_t>((m + kBlock - 1) / kBlock, kMaxGrid);
+    const double probes = (double)bits_for(n ? n : 1) * (d_start ? 2.0 : 1.0);
+    SFX_LAUNCH("ms_gsa_search", (double)m * probes * 24.0, k_ms_gsa_search, grid, kBlock, st, d_text, n, d_starts, ndocs, d_sa, d_da,
+               d_q, m, max_len, d_len, d_src, d_start, d_end);
+    return SFX_OK;
+}
+
 // document frequency: the ranks r of [start, end) whose previous rank of the same document lies before start.  The work is
 // the TOTAL interval length (prefix offs over the queries), 1024 consecutive ranks per wave, so one huge interval spreads
 // over the whole device; a wave whose ranks all belong to one query adds its count once.

@@ -121,9 +121,53 @@ def query_batch(text, sa, qbytes, qoff, engine=None):
     return start, end, found, anyp
 
 
+def _ms_outputs(query, dev, max_len, want_src, want_interval):
+    """Checks of a matching-statistics call and its freshly allocated outputs: (m, max_len, len, src, start, end)."""
+    if query.dtype != torch.uint8 or query.dim() != 1 or not query.is_contiguous():
+        raise TypeError("query must be a contiguous 1-D uint8 tensor")
+    if query.device != dev:
+        raise ValueError(f"query must be on the text's device ({dev})")
+    max_len = int(max_len or 0)
+    if max_len < 0 or max_len > 0xFFFFFFFF:
+        raise ValueError("max_len must be in 0 .. 2^32 - 1 (0 = no cap)")
+    m = query.numel()
+    ln = torch.empty(m, dtype=torch.int32, device=dev)
+    src = torch.empty(m, dtype=torch.int32, device=dev) if want_src else None
+    start = torch.empty(m, dtype=torch.int32, device=dev) if want_interval else None
+    end = torch.empty(m, dtype=torch.int32, device=dev) if want_interval else None
+    return m, max_len, ln, src, start, end
+
+
+def _ms_result(ln, src, start, end, want_src, want_interval):
+    if not want_src and not want_interval:
+        return ln
+    return (ln,) + ((src,) if want_src else ()) + ((start, end) if want_interval else ())
+
+
+def match_stats(text, sa, query, max_len=0, want_src=False, want_interval=False, engine=None):
+    """Matching statistics of the uint8 tensor `query` against (text, sa) on the same device: len[i] = the longest
+    prefix of query[i:] (at most max_len bytes; 0 = no cap) that occurs in text -- uint32 in int32 storage.
+    -> len, or the tuple (len[, src][, start, end]): src[i] = a text position of that match (0xFFFFFFFF where len is
+    0), [start[i], end[i]) = the ranks of the suffixes that begin with it.  Runs on the current stream without a
+    synchronisation (sfx_match_stats_dev); the table is not checked."""
+    eng = engine or default_engine()
+    _check_u8(text)
+    _check_u32(sa, "sa", text.numel())
+    if sa.device != text.device:
+        raise ValueError(f"sa must be on the text's device ({text.device})")
+    m, max_len, ln, src, start, end = _ms_outputs(query, text.device, max_len, want_src, want_interval)
+    if text.is_cuda:
+        eng.require_device()
+    with _on(text):
+        eng.check(eng.lib.sfx_match_stats_dev(_p(text), text.numel(), _p(sa), _p(query), m, max_len, _p(ln), _p(src), _p(start),
+                                              _p(end), _stream_ptr(text)), "sfx_match_stats_dev")
+    return _ms_result(ln, src, start, end, want_src, want_interval)
+
+
 class DeviceIndex:
     """Resident index over device tensors (text, suffix array): the engine adds its bucket directory
-    (sfx_index_create_dev); `query` = batched positions() / contains() / any_position()."""
+    (sfx_index_create_dev); `query` = batched positions() / contains() / any_position(); `match_stats` = the
+    matching statistics of a query text."""
 
     def __init__(self, text, sa, engine=None):
         self._eng = engine or default_engine()
@@ -147,6 +191,14 @@ class DeviceIndex:
                                                               _p(found), _p(anyp), _stream_ptr(self._text)),
                             "sfx_index_query_dev")
         return start, end, found, anyp
+
+    def match_stats(self, query, max_len=0, want_src=False, want_interval=False):
+        """As the module's match_stats, against the index's text and (checked) table: sfx_index_match_stats_dev."""
+        m, max_len, ln, src, start, end = _ms_outputs(query, self._text.device, max_len, want_src, want_interval)
+        with _on(self._text):
+            self._eng.check(self._eng.lib.sfx_index_match_stats_dev(self._h, _p(query), m, max_len, _p(ln), _p(src), _p(start),
+                                                                    _p(end), _stream_ptr(self._text)), "sfx_index_match_stats_dev")
+        return _ms_result(ln, src, start, end, want_src, want_interval)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -379,6 +431,15 @@ class GeneralizedDeviceIndex:
             self._eng.check(self._eng.lib.sfx_gindex_query_dev(self._h, _p(qbytes), _p(qoff), nq, _p(start), _p(end), _p(found),
                                                                _p(anyp), _p(ndocs), _stream_ptr(self._text)), "sfx_gindex_query_dev")
         return start, end, found, anyp, ndocs
+
+    def match_stats(self, query, max_len=0, want_src=False, want_interval=False):
+        """As the module's match_stats, against the collection: a match lies inside one document, ranks are GSA ranks
+        (sfx_gindex_match_stats_dev)."""
+        m, max_len, ln, src, start, end = _ms_outputs(query, self._text.device, max_len, want_src, want_interval)
+        with _on(self._text):
+            self._eng.check(self._eng.lib.sfx_gindex_match_stats_dev(self._h, _p(query), m, max_len, _p(ln), _p(src), _p(start),
+                                                                     _p(end), _stream_ptr(self._text)), "sfx_gindex_match_stats_dev")
+        return _ms_result(ln, src, start, end, want_src, want_interval)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

@@ -12,6 +12,8 @@ no match spans two documents.
     documents(q)     sorted distinct documents containing q; document_frequency(q) = their number
     repeat_lens(scope)            longest repeat starting at every position: anywhere, earlier, or in another document
     repeated_spans(min_len, ...)  [(document, begin_offset, end_offset)] of the bytes inside such repeats
+    match_stats(query, max_len)   longest match of every suffix of a NEW text inside one document of the collection
+    shared_spans(query, min_len)  [(begin, end)] of the query bytes inside such matches of at least min_len bytes
 
 Construction and queries run on the GPU through the C ABI (sfx_build_gsa_u32, sfx_gindex_*); there is no CPU
 path except `new_naive`, the definition itself.
@@ -21,7 +23,7 @@ import ctypes
 import numpy as np
 
 from ._lib import default_engine
-from .table import _as_bytes, _ptr, _repeat_lens, _repeat_spans
+from .table import _as_bytes, _match_stats, _ptr, _repeat_lens, _repeat_spans, _shared_spans
 
 _NONE = 0xFFFFFFFF
 
@@ -222,3 +224,15 @@ class GeneralizedSuffixTable:
         d = np.searchsorted(self._starts, b, side="right").astype(np.int64) - 1
         s = self._starts[d].astype(np.int64) if b.size else np.zeros(0, dtype=np.int64)
         return list(zip(d.tolist(), (b.astype(np.int64) - s).tolist(), (e.astype(np.int64) - s).tolist()))
+
+    # -- matching statistics of a second text ---------------------------------------------------
+    def match_stats(self, query, max_len=None, with_source=False, with_intervals=False):
+        """As SuffixTable.match_stats, against the collection: a match lies inside ONE document; src is a text position
+        doc_starts[i] + offset, and table()[start:end] are GSA ranks."""
+        return _match_stats(self._eng, self._eng.lib.sfx_gindex_match_stats, "sfx_gindex_match_stats", self._ensure_index,
+                            self.len(), query, max_len, with_source, with_intervals)
+
+    def shared_spans(self, query, min_len):
+        """[(begin, end)] in query coordinates, ascending: the query bytes inside a stretch of at least min_len bytes
+        that occurs within one document."""
+        return _shared_spans(self._eng, self.match_stats, query, min_len)

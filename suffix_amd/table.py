@@ -17,6 +17,7 @@ Same method names, argument meaning and error behaviour as the Rust API:
     .any_position(q)                  :279   .any_position(q)
     (none)                                   .positions_batch(qs) / .contains_batch(qs)
     (none)                                   .repeat_lens(scope) / .repeated_spans(min_len, scope)
+    (none)                                   .match_stats(query, max_len) / .shared_spans(query, min_len)
 
 Text is indexed by BYTES (every UTF-8 byte offset has a suffix, :29-31 of the
 crate docs and :379); `str` input is encoded as UTF-8.  Construction, LCP and
@@ -77,6 +78,37 @@ def _repeat_spans(eng, rep, min_len, starts):
                                                ctypes.byref(count)), "sfx_repeat_spans_u32")
     k = int(count.value)
     return begin[:k], end[:k]
+
+
+def _match_stats(eng, fn, name, index, n, query, max_len, with_source, with_intervals):
+    """sfx_index_match_stats / sfx_gindex_match_stats on host arrays -> len, or (len[, src][, start, end]).
+    `index` is called for the handle only when there is something to search."""
+    q = np.frombuffer(_as_bytes(query), dtype=np.uint8)
+    max_len = int(max_len or 0)
+    if max_len < 0 or max_len > 0xFFFFFFFF:
+        raise ValueError("max_len must be in 0 .. 2^32 - 1 (None or 0 = no cap)")
+    m = int(q.size)
+    ln = np.zeros(m, dtype=np.uint32)
+    src = np.full(m, _NONE, dtype=np.uint32) if with_source else None
+    start = np.zeros(m, dtype=np.uint32) if with_intervals else None
+    end = np.zeros(m, dtype=np.uint32) if with_intervals else None
+    if m and n:
+        eng.require_device()
+        eng.check(fn(index(), _ptr(q), m, max_len, _ptr(ln), _ptr(src) if with_source else None,
+                     _ptr(start) if with_intervals else None, _ptr(end) if with_intervals else None), name)
+    if not with_source and not with_intervals:
+        return ln
+    return (ln,) + ((src,) if with_source else ()) + ((start, end) if with_intervals else ())
+
+
+def _shared_spans(eng, match_stats, query, min_len):
+    """The spans of `query` that occur in the indexed text with at least min_len bytes: the search capped at min_len
+    (the covered bytes are the same for every cap >= min_len), then the span report of the repeats."""
+    min_len = int(min_len)
+    if min_len < 1 or min_len > 0xFFFFFFFF:
+        raise ValueError("min_len must be in 1 .. 2^32 - 1")
+    b, e = _repeat_spans(eng, match_stats(query, max_len=min_len), min_len, None)
+    return list(zip(b.tolist(), e.tolist()))
 
 
 class SuffixTable:
@@ -260,6 +292,21 @@ class SuffixTable:
         bytes (scope as for repeat_lens; "earlier" keeps the first copy of everything out of the report)."""
         b, e = _repeat_spans(self._eng, self.repeat_lens(scope), min_len, None)
         return list(zip(b.tolist(), e.tolist()))
+
+    # -- matching statistics of a second text ---------------------------------------------------
+    def match_stats(self, query, max_len=None, with_source=False, with_intervals=False):
+        """len[i] = the longest prefix of query[i:] (at most max_len bytes; None = no cap) that occurs in the text --
+        uint32, one entry per query byte.  -> len, or the tuple (len[, src][, start, end]): src[i] = a text position
+        where those bytes stand (which one is arbitrary), 0xFFFFFFFF where len[i] == 0; table()[start[i]:end[i]] =
+        every such position (0 / 0 where len[i] == 0).  The cost grows with the lengths found: cap a query that may
+        repeat the text itself."""
+        return _match_stats(self._eng, self._eng.lib.sfx_index_match_stats, "sfx_index_match_stats", self._ensure_index,
+                            self.len(), query, max_len, with_source, with_intervals)
+
+    def shared_spans(self, query, min_len):
+        """[(begin, end)] in query coordinates, ascending: the maximal runs of query bytes that lie inside a stretch of
+        at least min_len bytes which also occurs in the text."""
+        return _shared_spans(self._eng, self.match_stats, query, min_len)
 
     def __repr__(self):                                              # Debug, :296-312
         lines = ["", "-----------------------------------------", "SUFFIX TABLE",

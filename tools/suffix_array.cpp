@@ -3,7 +3,7 @@
 // over the MI355X engine's C++ host mirror (include/suffix_table.hpp -> libsuffix_hip.so),
 // extended into the large-file driver SURVEY.md 8(f) asks for:
 //
-//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--time]
+//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--time]
 //
 //   --dump PREFIX   write PREFIX.sa (and PREFIX.lcp with --lcp) as raw little-endian u32
 //                   arrays -- the on-disk form SuffixTable::from_parts (:111-119) reloads
@@ -12,6 +12,10 @@
 //   --repeats L     one "begin end" line per maximal run of bytes that lie inside a repeat of at least L bytes;
 //                   with --earlier only repeats of something EARLIER in the file count (the first copy of everything
 //                   stays out of the report: what a deduplication would keep)
+//   --match FILE2   which parts of FILE2 already stand in FILE: "Shared with FILE2 (>= L bytes): K spans, B bytes", then
+//                   one "begin end src" line per maximal run of FILE2's bytes inside a stretch of at least L bytes
+//                   (--min-len L, default 32) that also occurs in FILE; src = a position in FILE of the match that
+//                   starts at `begin`
 //   --time          wall-clock milliseconds of construction / LCP (host pointers, i.e.
 //                   including the PCIe copies: the device-resident rate is bench.py's)
 //
@@ -57,7 +61,8 @@ static double ms_since(std::chrono::steady_clock::time_point t0)
 
 int main(int argc, char** argv)
 {
-    std::string file, dump, load;
+    std::string file, dump, load, match;
+    long long min_len = 32;
     std::vector<std::string> queries;
     bool want_lcp = false, timing = false, earlier = false;
     long long repeats = -1;
@@ -73,6 +78,11 @@ int main(int argc, char** argv)
         else if (a == "--load") load = need("--load");
         else if (a == "--query") queries.push_back(need("--query"));
         else if (a == "--earlier") earlier = true;
+        else if (a == "--match") match = need("--match");
+        else if (a == "--min-len") {
+            min_len = atoll(need("--min-len"));
+            if (min_len < 1 || min_len > 0xFFFFFFFFll) { fprintf(stderr, "--min-len needs a length of at least 1\n"); return 1; }
+        }
         else if (a == "--repeats") {
             repeats = atoll(need("--repeats"));
             if (repeats < 1 || repeats > 0xFFFFFFFFll) { fprintf(stderr, "--repeats needs a length of at least 1\n"); return 1; }
@@ -81,11 +91,13 @@ int main(int argc, char** argv)
         else file = a;
     }
     if (file.empty()) {
-        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--time]\n");
+        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--time]\n");
         return 1;
     }
     std::string text;
     if (!read_file(file, &text)) { fprintf(stderr, "cannot read %s\n", file.c_str()); return 1; }
+    std::string other;
+    if (!match.empty() && !read_file(match, &other)) { fprintf(stderr, "cannot read %s\n", match.c_str()); return 1; }
     try {
         auto t0 = std::chrono::steady_clock::now();
         suffix::SuffixTable st = [&] {
@@ -129,6 +141,16 @@ int main(int argc, char** argv)
             const auto spans = st.repeated_spans((uint32_t)repeats, earlier ? SFX_REP_EARLIER : SFX_REP_ANY);
             if (timing) std::cout << "repeats ms: " << ms_since(t0) << "\n";
             for (const auto& be : spans) std::cout << be.first << " " << be.second << "\n";
+        }
+        if (!match.empty()) {
+            t0 = std::chrono::steady_clock::now();
+            const auto ms = st.match_stats(other, (uint32_t)min_len);           // a span report at L needs no more than max_len = L
+            const auto spans = suffix::SuffixTable::spans_of(ms.len, (uint32_t)min_len);
+            if (timing) std::cout << "match ms: " << ms_since(t0) << "\n";
+            uint64_t covered = 0;
+            for (const auto& be : spans) covered += be.second - be.first;
+            std::cout << "Shared with " << match << " (>= " << min_len << " bytes): " << spans.size() << " spans, " << covered << " bytes\n";
+            for (const auto& be : spans) std::cout << be.first << " " << be.second << " " << ms.src[be.first] << "\n";
         }
     } catch (const std::exception& ex) {
         fprintf(stderr, "suffix-array: %s\n", ex.what());
