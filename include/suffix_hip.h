@@ -336,6 +336,57 @@ int sfx_index_match_stats(const sfx_index* ix, const uint8_t* query, uint64_t m,
 int sfx_gindex_match_stats(const sfx_gindex* gx, const uint8_t* query, uint64_t m, uint32_t max_len,
                            uint32_t* len_out, uint32_t* src_out, uint32_t* start_out, uint32_t* end_out);
 
+/* ---- Burrows-Wheeler transform with sampled ranks, and its inverse ------------------
+ * T = a text of n bytes with suffix array sa.  The n + 1 sorted rotations of T$ ($ smaller than every byte) are the
+ * ROWS: row 0 begins with $, row j (1 <= j <= n) with suffix sa[j-1].  Last column: L[0] = T[n-1];
+ * L[j] = T[sa[j-1]-1] if sa[j-1] > 0, else $.
+ *   primary       the row whose L is $ = 1 + the rank of suffix 0; 1 <= primary <= n
+ *   bwt           n bytes: L without its $ entry; row R != primary sits at bwt[R < primary ? R : R - 1]
+ *   sample_step   s = 0 or a power of two
+ *   samples[k]    the row of the suffix that starts at text position k*s, k in [0, cnt), cnt = ceil(n / s);
+ *                 samples[0] == primary always.  s == 0: the primary only (cnt = 1 for n > 0); n == 0: cnt = 0.
+ * Inverse: lf[i] = 1 + C[bwt[i]] + #{j < i : bwt[j] == bwt[i]} with C[c] = the number of bytes of bwt below c.
+ * Segment k = the text positions [k*s, min(n, (k+1)*s)) (s == 0: one segment, the whole text).  Its walk starts at row
+ * samples[k+1] (row 0 for the last segment); each step writes bwt[i(R)] at the current position, going down, and sets
+ * R = lf[i(R)]; it must end at row samples[k].  One lane walks one segment, so the samples are what makes the inverse
+ * parallel: n / s chains of s dependent steps.
+ *
+ * sfx_bwt_sample_count: cnt above; 0 for a step that is neither 0 nor a power of two.
+ * sfx_bwt_dev: no workspace, no read-back, no synchronisation: three launches on the caller's stream (the primary is
+ *   found on the device).  d_text and d_bwt may have any alignment, d_sa and d_samples need 4 bytes; d_samples holds
+ *   sfx_bwt_sample_count(n, sample_step) entries.  The table is taken as it is, like sfx_match_stats_dev's: for any
+ *   table whose entries are all < n nothing is read or written out of bounds -- without a zero entry or with several
+ *   too; what the outputs hold for a table that is no permutation is unspecified.  A step that is neither 0 nor a power
+ *   of two is SFX_ERR_ARG, n > u32::MAX is SFX_ERR_TOO_LARGE, n == 0 is SFX_OK and writes nothing.
+ * sfx_bwt_u32: the same with host buffers; sa == NULL builds the table first.
+ * sfx_unbwt_dev: queues everything on the caller's stream and synchronises it ONCE, at the end, to read two device-side
+ *   checks back: (a) every sample lies in [1, n]; (b) every segment's walk ended at row samples[k] (and met the primary
+ *   row nowhere before).  (b) is a complete integrity check: lf is injective, the walks chain into n steps from row 0
+ *   that end at the primary, so they visit every row once -- SFX_OK means that (d_bwt, d_samples) IS the transform of
+ *   the text returned; anything else is SFX_ERR_ARG, and d_text_out then holds unspecified bytes.  Whatever the input
+ *   bytes are, nothing is read or written out of bounds: rows stay in [0, n], indices in [0, n-1].
+ *   SFX_ERR_ARG also, before anything is launched: a bad step; nsamples != sfx_bwt_sample_count(n, sample_step);
+ *   d_text_out overlapping d_bwt; a chain -- min(n, s), n for s == 0 -- longer than SFX_UNBWT_MAX_CHAIN; a workspace off
+ *   SFX_WORKSPACE_ALIGN.  A workspace below sfx_unbwt_workspace_bytes(n) is SFX_ERR_WORKSPACE, n > u32::MAX
+ *   SFX_ERR_TOO_LARGE.  d_bwt and d_text_out may have any alignment.
+ *   SFX_UNBWT_MAX_CHAIN is a contract, not a tuning knob: one lane walking 10^9 dependent misses would hold a shared
+ *   GPU for minutes; 2^20 steps of one idle-latency HBM miss each (about 900 cycles) stay well under a few seconds.
+ * sfx_unbwt: the same with host buffers.
+ * Not covered: the transform of a collection (per-document terminators); inversion without samples at scale (list
+ * ranking); occurrence tables and backward search (an FM-index -- its locate would reuse this sample layout); the
+ * transform without a table. */
+#define SFX_UNBWT_MAX_CHAIN (1u << 20)
+uint64_t sfx_bwt_sample_count(uint64_t n, uint32_t sample_step);
+int sfx_bwt_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t sample_step,
+                uint8_t* d_bwt, uint32_t* d_samples, void* stream);
+int sfx_bwt_u32(const uint8_t* text, uint64_t n, const uint32_t* sa /* NULL: build it */, uint32_t sample_step,
+                uint8_t* bwt_out, uint32_t* samples_out);
+uint64_t sfx_unbwt_workspace_bytes(uint64_t n);
+int sfx_unbwt_dev(const uint8_t* d_bwt, uint64_t n, const uint32_t* d_samples, uint64_t nsamples, uint32_t sample_step,
+                  uint8_t* d_text_out, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_unbwt(const uint8_t* bwt, uint64_t n, const uint32_t* samples, uint64_t nsamples, uint32_t sample_step,
+              uint8_t* text_out);
+
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the
  * text shard [shard_begin, shard_end).

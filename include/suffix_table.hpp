@@ -8,7 +8,7 @@
 //   new_ / new_naive (doc-hidden upstream, :93-100: the definition, sorted on the host -- the reference's own test oracle,
 //   tests/tests.rs:18-20; never a fallback of new_) / from_parts / into_parts / lcp_lens / table / text / len / is_empty /
 //   suffix / suffix_bytes / contains / positions / any_position,
-// plus the additive positions_batch / contains_batch and repeat_lens / repeated_spans.  Errors that are panics
+// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans and bwt / unbwt.  Errors that are panics
 // in the reference (assert! :380, assert_eq! :117) are std::runtime_error /
 // std::length_error here.  Text is indexed by BYTES (:379).
 #pragma once
@@ -180,6 +180,29 @@ public:
         check(sfx_repeat_spans_u32(rep.data(), rep.size(), min_len, nullptr, 0, b.data(), e.data(), cap, &count), "spans_of");
         std::vector<std::pair<uint32_t, uint32_t>> out((size_t)count);
         for (size_t k = 0; k < out.size(); k++) out[k] = {b[k], e[k]};
+        return out;
+    }
+
+    // additive: the Burrows-Wheeler transform with sampled ranks (suffix_hip.h): bwt = the last column of the sorted rotations
+    // of text$ without its $ entry; samples[k] = the row of the suffix at k * sample_step (samples[0] = the primary row;
+    // sample_step 0: the primary only).  sample_step is 0 or a power of two.
+    struct Bwt { std::string bwt; std::vector<uint32_t> samples; };
+    Bwt bwt(uint32_t sample_step = 256) const
+    {
+        if (sample_step & (sample_step - 1u)) throw std::invalid_argument("bwt: sample_step must be 0 or a power of two");
+        Bwt out{std::string(text_.size(), '\0'), std::vector<uint32_t>((size_t)sfx_bwt_sample_count(text_.size(), sample_step), 0u)};
+        if (!text_.empty())
+            check(sfx_bwt_u32(bytes(text_), text_.size(), table_.data(), sample_step, reinterpret_cast<uint8_t*>(&out.bwt[0]),
+                              out.samples.data()), "bwt");
+        return out;
+    }
+    // ... and its inverse: the text whose transform (bwt, samples) is.  A pair that is the transform of no text throws
+    // std::runtime_error -- the walks check themselves, so what is returned is the text.
+    static std::string unbwt(std::string_view bwt, const std::vector<uint32_t>& samples, uint32_t sample_step)
+    {
+        std::string out(bwt.size(), '\0');
+        check(sfx_unbwt(reinterpret_cast<const uint8_t*>(bwt.data()), bwt.size(), samples.data(), samples.size(), sample_step,
+                        reinterpret_cast<uint8_t*>(&out[0])), "unbwt");
         return out;
     }
 

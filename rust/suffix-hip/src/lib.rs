@@ -60,6 +60,21 @@ extern "C" {
     fn sfx_match_stats_dev(d_text: *const u8, n: u64, d_sa: *const u32, d_query: *const u8, m: u64, max_len: u32,
                            d_len: *mut u32, d_src: *mut u32, d_start: *mut u32, d_end: *mut u32,
                            stream: *mut c_void) -> c_int;
+    // Burrows-Wheeler transform with sampled ranks and its inverse (host buffers; sa may be null: the table is built)
+    fn sfx_bwt_sample_count(n: u64, sample_step: u32) -> u64;
+    fn sfx_bwt_u32(text: *const u8, n: u64, sa: *const u32, sample_step: u32, bwt_out: *mut u8,
+                   samples_out: *mut u32) -> c_int;
+    fn sfx_unbwt(bwt: *const u8, n: u64, samples: *const u32, nsamples: u64, sample_step: u32,
+                 text_out: *mut u8) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_bwt_dev(d_text: *const u8, n: u64, d_sa: *const u32, sample_step: u32, d_bwt: *mut u8,
+                   d_samples: *mut u32, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_unbwt_workspace_bytes(n: u64) -> u64;
+    #[allow(dead_code)]
+    fn sfx_unbwt_dev(d_bwt: *const u8, n: u64, d_samples: *const u32, nsamples: u64, sample_step: u32,
+                     d_text_out: *mut u8, d_workspace: *mut c_void, workspace_bytes: u64,
+                     stream: *mut c_void) -> c_int;
     // suffix_tree's node table with ordered children (children(), preorder(), leaves(), suffix_indices() read it)
     #[allow(dead_code)]
     fn sfx_suffix_tree_u32(text: *const u8, sa: *const u32, lcp: *const u32, n: u64, node_capacity: u64,
@@ -149,6 +164,35 @@ pub fn sais_table_with_lcp(text: &str) -> (Vec<u32>, Vec<u32>) {
         sfx_build_sa_lcp_u32(text.as_ptr(), text.len() as u64, sa.as_mut_ptr(), lcp.as_mut_ptr())
     }, "sfx_build_sa_lcp_u32");
     (sa, lcp)
+}
+
+/// Additive API: the Burrows-Wheeler transform of `text` with its suffix table, and the rows of the suffixes at every
+/// `sample_step`-th position (0 or a power of two; `samples[0]` is the primary row, 0 keeps the primary only).
+/// `bwt` is the last column of the sorted rotations of `text$` without its `$` entry.
+pub fn bwt(text: &[u8], table: &[u32], sample_step: u32) -> (Vec<u8>, Vec<u32>) {
+    assert!(text.len() <= u32::MAX as usize);
+    assert_eq!(text.len(), table.len());
+    assert!(sample_step & sample_step.wrapping_sub(1) == 0, "sample_step must be 0 or a power of two");
+    let cnt = unsafe { sfx_bwt_sample_count(text.len() as u64, sample_step) } as usize;
+    let (mut out, mut samples) = (vec![0u8; text.len()], vec![0u32; cnt]);
+    check(unsafe {
+        sfx_bwt_u32(text.as_ptr(), text.len() as u64, table.as_ptr(), sample_step, out.as_mut_ptr(), samples.as_mut_ptr())
+    }, "sfx_bwt_u32");
+    (out, samples)
+}
+
+/// The inverse of `bwt`: the text whose transform `(bwt, samples)` is, or `None` where the pair is the transform of no
+/// text (the walks check themselves: `Some` means the pair IS the transform of what is returned).
+pub fn unbwt(bwt: &[u8], samples: &[u32], sample_step: u32) -> Option<Vec<u8>> {
+    let mut out = vec![0u8; bwt.len()];
+    let rc = unsafe {
+        sfx_unbwt(bwt.as_ptr(), bwt.len() as u64, samples.as_ptr(), samples.len() as u64, sample_step, out.as_mut_ptr())
+    };
+    if rc == 1 {
+        return None;                                       // SFX_ERR_ARG
+    }
+    check(rc, "sfx_unbwt");
+    Some(out)
 }
 
 /// Additive API: many `positions()` at once.  Returns (start, end) pairs;

@@ -93,6 +93,12 @@ ABI = [
     ("sfx_gindex_match_stats_dev", _int, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("sfx_index_match_stats", _int, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp]),
     ("sfx_gindex_match_stats", _int, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp]),
+    ("sfx_bwt_sample_count", _u64, [_u64, _u32]),
+    ("sfx_bwt_dev", _int, [_vp, _u64, _vp, _u32, _vp, _vp, _vp]),
+    ("sfx_bwt_u32", _int, [_vp, _u64, _vp, _u32, _vp, _vp]),
+    ("sfx_unbwt_workspace_bytes", _u64, [_u64]),
+    ("sfx_unbwt_dev", _int, [_vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
+    ("sfx_unbwt", _int, [_vp, _u64, _vp, _u64, _u32, _vp]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),

@@ -713,6 +713,74 @@ int sfx_gindex_match_stats(const sfx_gindex* gx, const uint8_t* query, uint64_t 
     return match_stats_host(nullptr, gx, query, m, max_len, len_out, src_out, start_out, end_out);
 }
 
+// ---- Burrows-Wheeler transform with sampled ranks, and its inverse (include/suffix_hip.h) ------
+uint64_t sfx_bwt_sample_count(uint64_t n, uint32_t sample_step) { return bwt_sample_count(n, sample_step); }
+int sfx_bwt_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t sample_step, uint8_t* d_bwt, uint32_t* d_samples,
+                void* stream)
+{
+    SFX_NEED_U32(d_sa, d_samples);
+    return bwt_dev(d_text, n, d_sa, sample_step, d_bwt, d_samples, (hipStream_t)stream);
+}
+int sfx_bwt_u32(const uint8_t* text, uint64_t n, const uint32_t* sa, uint32_t sample_step, uint8_t* bwt_out, uint32_t* samples_out)
+{
+    if (sample_step & (sample_step - 1u)) return SFX_ERR_ARG;
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!text || !bwt_out || !samples_out) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    const uint64_t cnt = bwt_sample_count(n, sample_step), wsb = sa ? 0 : sa_workspace_bytes(n);
+    DevBuf dt, ds, db, dm, dw;
+    SFX_TRY(dt.alloc(n));
+    SFX_TRY(ds.alloc(n * sizeof(uint32_t)));
+    SFX_TRY(db.alloc(n));
+    SFX_TRY(dm.alloc(cnt * sizeof(uint32_t)));
+    if (!sa) SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(dt.p, text, n, hipMemcpyHostToDevice, st));
+    if (sa)
+        SFX_HIP(hipMemcpyAsync(ds.p, sa, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    else
+        SFX_TRY(build_sa_u32_dev((const uint8_t*)dt.p, n, (uint32_t*)ds.p, dw.p, wsb, st));
+    SFX_TRY(bwt_dev((const uint8_t*)dt.p, n, (const uint32_t*)ds.p, sample_step, (uint8_t*)db.p, (uint32_t*)dm.p, st));
+    SFX_HIP(hipMemcpyAsync(bwt_out, db.p, n, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipMemcpyAsync(samples_out, dm.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+uint64_t sfx_unbwt_workspace_bytes(uint64_t n) { return unbwt_workspace_bytes(n); }
+int sfx_unbwt_dev(const uint8_t* d_bwt, uint64_t n, const uint32_t* d_samples, uint64_t nsamples, uint32_t sample_step,
+                  uint8_t* d_text_out, void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    SFX_NEED_U32(d_samples);
+    SFX_NEED_WS(d_workspace, workspace_bytes, unbwt_workspace_bytes(n));
+    return unbwt_dev(d_bwt, n, d_samples, nsamples, sample_step, d_text_out, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sfx_unbwt(const uint8_t* bwt, uint64_t n, const uint32_t* samples, uint64_t nsamples, uint32_t sample_step, uint8_t* text_out)
+{
+    if (sample_step & (sample_step - 1u)) return SFX_ERR_ARG;
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (nsamples != bwt_sample_count(n, sample_step)) return SFX_ERR_ARG;
+    if (n == 0) return SFX_OK;
+    if ((sample_step ? dmin<uint64_t>(n, sample_step) : n) > SFX_UNBWT_MAX_CHAIN) return SFX_ERR_ARG;
+    if (!bwt || !samples || !text_out) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    const uint64_t wsb = unbwt_workspace_bytes(n);
+    DevBuf db, dm, dt, dw;
+    SFX_TRY(db.alloc(n));
+    SFX_TRY(dm.alloc(nsamples * sizeof(uint32_t)));
+    SFX_TRY(dt.alloc(n));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    SFX_HIP(hipMemcpyAsync(db.p, bwt, n, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dm.p, samples, nsamples * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(unbwt_dev((const uint8_t*)db.p, n, (const uint32_t*)dm.p, nsamples, sample_step, (uint8_t*)dt.p, dw.p, wsb, st));
+    SFX_HIP(hipMemcpyAsync(text_out, dt.p, n, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+
 // ---- suffix-tree topology, generalized suffix array -------------------------------------------
 uint64_t sfx_lcp_intervals_workspace_bytes(uint64_t n) { return lcp_intervals_workspace_bytes(n); }
 int sfx_lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_t* d_rb, uint32_t* d_node,

@@ -457,6 +457,12 @@ int match_stats_dir_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
 int gindex_match_stats_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, const uint32_t* d_sa,
                            const uint32_t* d_da, const uint8_t* d_q, uint64_t m, uint32_t max_len, uint32_t* d_len,
                            uint32_t* d_src, uint32_t* d_start, uint32_t* d_end, hipStream_t st);
+// Burrows-Wheeler transform with sampled ranks and its inverse (sfx_tree.hip)
+uint64_t bwt_sample_count(uint64_t n, uint32_t step);
+int bwt_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t step, uint8_t* d_bwt, uint32_t* d_samples, hipStream_t st);
+uint64_t unbwt_workspace_bytes(uint64_t n);
+int unbwt_dev(const uint8_t* d_bwt, uint64_t n, const uint32_t* d_samples, uint64_t nsamples, uint32_t step, uint8_t* d_out, void* ws,
+              uint64_t ws_bytes, hipStream_t st);
 // bucket directory of the resident index (sfx_query.hip)
 int dir_shape(uint64_t n, int bits, int* k_out, int* dbits_out, uint64_t* entries_out);
 uint64_t dir_scratch_words(uint64_t entries);

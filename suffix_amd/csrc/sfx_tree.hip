@@ -1598,4 +1598,303 @@ int suffix_tree_dev(const uint8_t* d_text, const uint32_t* d_sa, const uint32_t*
     return SFX_OK;
 }
 
+// ---- Burrows-Wheeler transform with sampled ranks, and its inverse (include/suffix_hip.h) ----
+// Rows are the n + 1 sorted rotations of T$: row 0 begins with $, row R >= 1 with suffix sa[R-1]; the primary is the row
+// of suffix 0, and row R != primary sits at bwt[R < primary ? R : R - 1].
+// Forward: a pass over the table finds the primary (samples[0]), then one rank per lane gathers T[sa - 1].
+// Not covered: collections (per-document terminators), inversion without samples at scale (list ranking), occurrence
+// tables / backward search, the transform without a table.
+__global__ void __launch_bounds__(kBlock)
+k_bwt_primary(const uint32_t* __restrict__ sa, uint64_t n, uint32_t* __restrict__ samples)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += stride)
+        if (sa[r] == 0u) atomicMax(&samples[0], (uint32_t)(r + 1));       // (the largest of several zeros; none: stays 0)
+}
+// the index of row R in bwt, for a primary in [1, n] and R in [0, n], R != primary: always in [0, n-1]
+__device__ __forceinline__ uint64_t bwt_index(uint64_t R, uint64_t primary) { return R < primary ? R : R - 1; }
+// One row per lane: a coalesced read of the table, one random byte, a coalesced byte store at the shifted index, and the
+// sample scatter where sa % step == 0 (samples[0] is k_bwt_primary's and only read here).  The table is unchecked: a
+// primary of 0 (no zero entry) is clamped into [1, n], a second zero entry wraps to T[n-1], and with every entry < n
+// each index stays inside its array.
+__global__ void __launch_bounds__(kBlock)
+k_bwt_gather(const uint8_t* __restrict__ text, uint64_t n, const uint32_t* __restrict__ sa, uint32_t step, int shift,
+             uint8_t* __restrict__ bwt, uint32_t* __restrict__ samples)
+{
+    const uint64_t primary = dmin<uint64_t>(dmax<uint64_t>(samples[0], 1), n);
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t R = (uint64_t)blockIdx.x * kBlock + threadIdx.x; R <= n; R += stride) {
+        if (R == 0) { bwt[0] = text[n - 1]; continue; }
+        const uint64_t s = sa[R - 1];
+        const uint8_t c = text[s ? s - 1 : n - 1];
+        if (R != primary) bwt[bwt_index(R, primary)] = c;
+        if (step && s && (s & (uint64_t)(step - 1u)) == 0) samples[s >> shift] = (uint32_t)R;
+    }
+}
+__host__ __device__ inline bool bwt_step_ok(uint32_t step) { return (step & (step - 1u)) == 0; }
+uint64_t bwt_sample_count(uint64_t n, uint32_t step)
+{
+    if (n == 0 || !bwt_step_ok(step)) return 0;
+    return step ? (n + step - 1) / step : 1;
+}
+int bwt_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t step, uint8_t* d_bwt, uint32_t* d_samples, hipStream_t st)
+{
+    if (!bwt_step_ok(step)) return SFX_ERR_ARG;
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!d_text || !d_sa || !d_bwt || !d_samples) return SFX_ERR_ARG;
+    SFX_HIP(hipMemsetAsync(d_samples, 0, sizeof(uint32_t), st));
+    const unsigned pgrid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
+    SFX_LAUNCH("bwt_primary", (double)n * 4, k_bwt_primary, pgrid, kBlock, st, d_sa, n, d_samples);
+    const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock) / kBlock, kMaxGrid);
+    SFX_LAUNCH("bwt_gather", (double)n * 5 + (double)n * 64, k_bwt_gather, grid, kBlock, st, d_text, n, d_sa, step,
+               step ? bits_for(step) - 1 : 0, d_bwt, d_samples);
+    return SFX_OK;
+}
+
+// lf from bwt: a stable 256-way counting rank.  A tile is `tile` bytes (a multiple of kBlock), one workgroup, a quarter per
+// wave.  k_bwt_rank_count: per tile the count of every symbol, counts[tile][256].  k_bwt_rank_scan_*: per symbol the
+// exclusive scan of its column over the tiles -- thread d owns symbol d, a chunk of tiles per workgroup, the chunks' sums
+// scanned by one workgroup, which also lays down C[0..256] -- leaving 1 + C[d] + (occurrences in earlier tiles) in place.
+// k_bwt_rank: the tile's bases, split over its waves by their own counts, then the match-mask ranking of the radix
+// passes (rank_round's scheme) 64 bytes at a time.
+constexpr uint64_t kBwtTile = 16384;
+static uint64_t bwt_tile()
+{
+    static const uint64_t tile = [] {                   // test hook: SFX_BWT_TILE=<bytes>, so that small inputs span several tiles
+        const char* e = dev_env("SFX_BWT_TILE");
+        const long long v = e ? atoll(e) : 0;
+        return (v >= kBlock && v <= (long long)kBwtTile && v % kBlock == 0) ? (uint64_t)v : kBwtTile;
+    }();
+    return tile;
+}
+struct BwtRankLds {
+    unsigned long long flags[kWavesPerBlock][kRadixDev];
+    uint32_t cnt[kWavesPerBlock][kRadixDev];
+};
+// the counts of the calling wave's quarter of tile t into s.cnt[wave] (which the caller has zeroed)
+__device__ __forceinline__ void bwt_wave_count(const uint8_t* __restrict__ bwt, uint64_t n, uint64_t b, uint64_t e, uint32_t* cnt_w)
+{
+    for (uint64_t i = b + lane_id(); i < e; i += kWave) atomicAdd(&cnt_w[bwt[i]], 1u);
+    (void)n;
+}
+__global__ void __launch_bounds__(kBlock)
+k_bwt_rank_count(const uint8_t* __restrict__ bwt, uint64_t n, uint64_t tile, uint64_t ntiles, uint32_t* __restrict__ counts)
+{
+    __shared__ BwtRankLds s;
+    const unsigned tid = threadIdx.x, w = wave_id();
+    const uint64_t quarter = tile / kWavesPerBlock;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+#pragma unroll
+        for (int k = 0; k < kWavesPerBlock; k++) s.cnt[k][tid] = 0u;
+        __syncthreads();
+        const uint64_t b = dmin<uint64_t>(t * tile + w * quarter, n), e = dmin<uint64_t>(b + quarter, n);
+        bwt_wave_count(bwt, n, b, e, s.cnt[w]);
+        __syncthreads();
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < kWavesPerBlock; k++) sum += s.cnt[k][tid];
+        counts[t * kRadixDev + tid] = sum;
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(kBlock)
+k_bwt_rank_scan_count(const uint32_t* __restrict__ counts, uint64_t ntiles, uint64_t chunk, uint32_t* __restrict__ part)
+{
+    const uint64_t b = (uint64_t)blockIdx.x * chunk, e = dmin<uint64_t>(b + chunk, ntiles);
+    uint32_t acc = 0;
+    for (uint64_t t = b; t < e; t++) acc += counts[t * kRadixDev + threadIdx.x];
+    part[(uint64_t)blockIdx.x * kRadixDev + threadIdx.x] = acc;
+}
+// one workgroup: thread d scans the chunks' sums of symbol d, the symbols' totals are scanned into C, and every chunk's
+// carry becomes 1 + C[d] + (occurrences of d in earlier chunks): the lf value of the chunk's first d
+__global__ void __launch_bounds__(kBlock)
+k_bwt_rank_scan_top(uint32_t* __restrict__ part, unsigned nb, uint32_t* __restrict__ ctab)
+{
+    __shared__ uint32_t sh[kWavesPerBlock];
+    const unsigned d = threadIdx.x;
+    uint32_t run = 0;
+    for (unsigned b = 0; b < nb; b++) run += part[(uint64_t)b * kRadixDev + d];
+    uint32_t total;
+    const uint32_t C = block_scan_add_excl<uint32_t>(run, sh, total);
+    ctab[d] = C;
+    if (d == 0) ctab[kRadixDev] = total;
+    run = 1u + C;
+    for (unsigned b = 0; b < nb; b++) {
+        const uint32_t v = part[(uint64_t)b * kRadixDev + d];
+        part[(uint64_t)b * kRadixDev + d] = run;
+        run += v;
+    }
+}
+__global__ void __launch_bounds__(kBlock)
+k_bwt_rank_scan_apply(uint32_t* __restrict__ counts, uint64_t ntiles, uint64_t chunk, const uint32_t* __restrict__ part)
+{
+    const uint64_t b = (uint64_t)blockIdx.x * chunk, e = dmin<uint64_t>(b + chunk, ntiles);
+    uint32_t run = part[(uint64_t)blockIdx.x * kRadixDev + threadIdx.x];
+    for (uint64_t t = b; t < e; t++) {
+        const uint32_t v = counts[t * kRadixDev + threadIdx.x];
+        counts[t * kRadixDev + threadIdx.x] = run;
+        run += v;
+    }
+}
+__global__ void __launch_bounds__(kBlock)
+k_bwt_rank(const uint8_t* __restrict__ bwt, uint64_t n, uint64_t tile, uint64_t ntiles, const uint32_t* __restrict__ counts,
+           uint32_t* __restrict__ lf)
+{
+    __shared__ BwtRankLds s;
+    const unsigned tid = threadIdx.x, w = wave_id(), lane = lane_id();
+    const unsigned long long mybit = 1ull << lane;
+    const uint64_t quarter = tile / kWavesPerBlock;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+#pragma unroll
+        for (int k = 0; k < kWavesPerBlock; k++) {
+            s.cnt[k][tid] = 0u;
+            s.flags[k][tid] = 0ull;
+        }
+        __syncthreads();
+        const uint64_t b = dmin<uint64_t>(t * tile + w * quarter, n), e = dmin<uint64_t>(b + quarter, n);
+        bwt_wave_count(bwt, n, b, e, s.cnt[w]);
+        __syncthreads();
+        {                                                             // thread d: the waves' bases of symbol d
+            uint32_t run = counts[t * kRadixDev + tid];
+#pragma unroll
+            for (int k = 0; k < kWavesPerBlock; k++) {
+                const uint32_t c = s.cnt[k][tid];
+                s.cnt[k][tid] = run;
+                run += c;
+            }
+        }
+        __syncthreads();
+        // (a uniform trip count per wave: the ranking round has wave-level rendezvous; lanes past the end take no part)
+        for (uint64_t base = b; base < e; base += kWave) {
+            const uint64_t i = base + lane;
+            const bool live = i < e;
+            const unsigned d = live ? bwt[i] : 0u;
+            if (live) atomicOr(&s.flags[w][d], mybit);
+            wave_sync();
+            const unsigned long long peers = live ? s.flags[w][d] : 0ull;
+            const uint32_t pre = live ? s.cnt[w][d] : 0u;
+            wave_sync();
+            const unsigned below = lanes_below(peers);
+            if (live && below == 0) {
+                s.flags[w][d] = 0ull;
+                s.cnt[w][d] = pre + (uint32_t)__popcll(peers);
+            }
+            wave_sync();
+            if (live) lf[i] = pre + below;
+        }
+        __syncthreads();
+    }
+}
+
+// One lane per segment: `len` dependent steps, one random 4-byte read each.  The byte is recovered from lf[i] by a search
+// of C[0..256] in LDS: lf[i] - 1 lies in [C[c], C[c+1]) for exactly the c = bwt[i].  Bytes leave four at a time where
+// the address allows.  err[0]: a sample outside [1, n]; err[1]: a walk that met the primary row early or did not end at
+// samples[k].  No input can take an index out of [0, n-1]: R <= n always (lf values and checked samples), and the
+// primary row is never dereferenced.
+constexpr int kUnbwtBlock = 64;
+__global__ void __launch_bounds__(kUnbwtBlock)
+k_unbwt_walk(const uint32_t* __restrict__ lf, uint64_t n, const uint32_t* __restrict__ samples, uint64_t cnt, uint32_t step,
+             const uint32_t* __restrict__ ctab, uint8_t* __restrict__ out, uint32_t* __restrict__ err)
+{
+    __shared__ uint32_t C[kRadixDev + 1];
+    for (unsigned k = threadIdx.x; k <= (unsigned)kRadixDev; k += kUnbwtBlock) C[k] = ctab[k];
+    __syncthreads();
+    const uint64_t k = (uint64_t)blockIdx.x * kUnbwtBlock + threadIdx.x;
+    if (k >= cnt) return;
+    const uint64_t primary = samples[0], want = samples[k];
+    const uint64_t begin = step ? k * step : 0, end = (step && k + 1 < cnt) ? begin + step : n;
+    uint64_t R = k + 1 < cnt ? samples[k + 1] : 0;
+    if (primary < 1 || primary > n || want < 1 || want > n || R > n || (k + 1 < cnt && R < 1)) {
+        err[0] = 1u;
+        return;
+    }
+    uint32_t acc = 0;
+    int held = 0;                                                     // acc = the bytes of [pos, pos + held), lowest first
+    uint64_t pos = end;
+    while (pos > begin) {
+        if (R == primary) break;                                      // the $ row: this is no transform
+        const uint32_t v = lf[bwt_index(R, primary)];
+        unsigned lo = 0, hi = kRadixDev;                              // the c with C[c] <= v - 1 < C[c + 1]
+        while (hi - lo > 1) {
+            const unsigned mid = (lo + hi) >> 1;
+            if (C[mid] <= v - 1u) lo = mid; else hi = mid;
+        }
+        pos--;
+        acc = (acc << 8) | lo;
+        if (++held == 4) {
+            if (((uintptr_t)(out + pos) & 3u) == 0) {
+                *reinterpret_cast<uint32_t*>(out + pos) = acc;
+                held = 0;
+            } else {
+                out[pos + 3] = (uint8_t)(acc >> 24);
+                held = 3;
+            }
+        }
+        R = v;
+    }
+    for (int j = 0; j < held; j++) out[pos + j] = (uint8_t)(acc >> (8 * j));
+    if (pos != begin || R != want) err[1] = 1u;
+}
+
+// [err 64 words | C 257 words | lf n | counts ntiles x 256 | the scan's chunk sums]
+struct UnbwtWs {
+    uint32_t *err, *ctab, *lf, *counts, *part;
+};
+static unsigned bwt_scan_blocks(uint64_t ntiles) { return (unsigned)dmin<uint64_t>(ntiles, dmin<unsigned>(kMaxGrid, grid_cap())); }
+template <class A> static void unbwt_carve(A& a, uint64_t n, UnbwtWs* w)
+{
+    const uint64_t ntiles = (n + bwt_tile() - 1) / bwt_tile();
+    w->err = a.template take<uint32_t>(64);
+    w->ctab = a.template take<uint32_t>(kRadixDev + 1);
+    w->lf = a.template take<uint32_t>(n);
+    w->counts = a.template take<uint32_t>(ntiles * kRadixDev);
+    w->part = a.template take<uint32_t>((uint64_t)bwt_scan_blocks(ntiles) * kRadixDev);
+}
+uint64_t unbwt_workspace_bytes(uint64_t n)
+{
+    if (n == 0) return 0;
+    GsaSizer z;
+    UnbwtWs w;
+    unbwt_carve(z, n, &w);
+    return z.used;
+}
+int unbwt_dev(const uint8_t* d_bwt, uint64_t n, const uint32_t* d_samples, uint64_t nsamples, uint32_t step, uint8_t* d_out, void* ws,
+              uint64_t ws_bytes, hipStream_t st)
+{
+    if (!bwt_step_ok(step)) return SFX_ERR_ARG;
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (nsamples != bwt_sample_count(n, step)) return SFX_ERR_ARG;
+    if (n == 0) return SFX_OK;
+    if ((step ? dmin<uint64_t>(n, step) : n) > SFX_UNBWT_MAX_CHAIN) return SFX_ERR_ARG;
+    if (!d_bwt || !d_samples || !d_out) return SFX_ERR_ARG;
+    {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_bwt), b = reinterpret_cast<uintptr_t>(d_out);
+        if (a < b + n && b < a + n) return SFX_ERR_ARG;
+    }
+    if (!ws || ws_bytes < unbwt_workspace_bytes(n)) return SFX_ERR_WORKSPACE;
+    Arena a(ws, ws_bytes);
+    UnbwtWs w;
+    unbwt_carve(a, n, &w);
+    if (a.overflow) return SFX_ERR_INTERNAL;
+    const uint64_t tile = bwt_tile(), ntiles = (n + tile - 1) / tile;
+    SFX_HIP(hipMemsetAsync(w.err, 0, 64 * sizeof(uint32_t), st));
+    const unsigned tgrid = (unsigned)dmin<uint64_t>(ntiles, dmin<unsigned>(kMaxGrid, grid_cap()));
+    SFX_LAUNCH("bwt_rank", (double)n, k_bwt_rank_count, tgrid, kBlock, st, d_bwt, n, tile, ntiles, w.counts);
+    const unsigned nb = bwt_scan_blocks(ntiles);
+    const uint64_t chunk = (ntiles + nb - 1) / nb;
+    const double cbytes = (double)ntiles * kRadixDev * 4;
+    SFX_LAUNCH("bwt_rank", cbytes, k_bwt_rank_scan_count, nb, kBlock, st, (const uint32_t*)w.counts, ntiles, chunk, w.part);
+    SFX_LAUNCH("bwt_rank", (double)nb * kRadixDev * 8, k_bwt_rank_scan_top, 1, kBlock, st, w.part, nb, w.ctab);
+    SFX_LAUNCH("bwt_rank", cbytes * 2, k_bwt_rank_scan_apply, nb, kBlock, st, w.counts, ntiles, chunk, (const uint32_t*)w.part);
+    SFX_LAUNCH("bwt_rank", (double)n * 5 + cbytes, k_bwt_rank, tgrid, kBlock, st, d_bwt, n, tile, ntiles, (const uint32_t*)w.counts,
+               w.lf);
+    const uint64_t wgrid = (nsamples + kUnbwtBlock - 1) / kUnbwtBlock;           // (<= 2^32 / 64)
+    SFX_LAUNCH("unbwt_walk", (double)n * 65, k_unbwt_walk, (unsigned)wgrid, kUnbwtBlock, st, (const uint32_t*)w.lf, n, d_samples,
+               nsamples, step, (const uint32_t*)w.ctab, d_out, w.err);
+    uint32_t err[2] = {0, 0};
+    SFX_TRY(read_back(err, w.err, sizeof(err), st));
+    return (err[0] | err[1]) ? SFX_ERR_ARG : SFX_OK;
+}
+
 }  // namespace sfx

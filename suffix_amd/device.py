@@ -164,6 +164,72 @@ def match_stats(text, sa, query, max_len=0, want_src=False, want_interval=False,
     return _ms_result(ln, src, start, end, want_src, want_interval)
 
 
+def _bwt_step(sample_step):
+    step = int(sample_step or 0)
+    if step < 0 or step > 0x80000000 or step & (step - 1):
+        raise ValueError("sample_step must be 0 or a power of two of at most 2^31")
+    return step
+
+
+def bwt(text, sa, sample_step=256, out_bwt=None, out_samples=None, engine=None):
+    """Burrows-Wheeler transform of the uint8 tensor `text` with its suffix array `sa` (same device) -> (bwt, samples):
+    bwt = the last column of the sorted rotations of text$ without its $ entry (uint8, n bytes); samples[k] = the row
+    of the suffix that starts at k * sample_step (uint32 in int32 storage; samples[0] = the primary row; sample_step 0:
+    the primary only).  Runs on the current stream without a synchronisation (sfx_bwt_dev); the table is not checked."""
+    eng = engine or default_engine()
+    _check_u8(text)
+    n = text.numel()
+    _check_u32(sa, "sa", n)
+    if sa.device != text.device:
+        raise ValueError(f"sa must be on the text's device ({text.device})")
+    step = _bwt_step(sample_step)
+    cnt = int(eng.lib.sfx_bwt_sample_count(n, step))
+    if out_bwt is None:
+        out_bwt = torch.empty(n, dtype=torch.uint8, device=text.device)
+    if out_samples is None:
+        out_samples = torch.empty(cnt, dtype=torch.int32, device=text.device)
+    _check_u8(out_bwt)
+    _check_u32(out_samples, "out_samples", cnt)
+    if out_bwt.numel() != n:
+        raise ValueError(f"out_bwt must hold {n} bytes")
+    if text.is_cuda:
+        eng.require_device()
+    with _on(text):
+        eng.check(eng.lib.sfx_bwt_dev(_p(text), n, _p(sa), step, _p(out_bwt), _p(out_samples), _stream_ptr(text)), "sfx_bwt_dev")
+    return out_bwt, out_samples
+
+
+def unbwt_workspace(n, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_unbwt_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def unbwt(bwt, samples, sample_step, out=None, workspace=None, engine=None):
+    """The text whose transform (bwt, samples) is, as `bwt()` returns it, with the same sample_step.  One lane walks one
+    segment of sample_step bytes (at most 2^20; sample_step 0: the whole text as one chain).  Synchronises the current
+    stream once; a pair that is no transform of any text raises SuffixHipError (sfx_unbwt_dev)."""
+    eng = engine or default_engine()
+    _check_u8(bwt)
+    n = bwt.numel()
+    _check_u32(samples, "samples")
+    if samples.device != bwt.device:
+        raise ValueError(f"samples must be on the transform's device ({bwt.device})")
+    step = _bwt_step(sample_step)
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint8, device=bwt.device)
+    _check_u8(out)
+    if out.numel() != n:
+        raise ValueError(f"out must hold {n} bytes")
+    if workspace is None:
+        workspace = unbwt_workspace(n, bwt.device, eng)
+    if bwt.is_cuda:
+        eng.require_device()
+    with _on(bwt):
+        eng.check(eng.lib.sfx_unbwt_dev(_p(bwt), n, _p(samples), samples.numel(), step, _p(out), _p(workspace), workspace.numel(),
+                                        _stream_ptr(bwt)), "sfx_unbwt_dev")
+    return out
+
+
 class DeviceIndex:
     """Resident index over device tensors (text, suffix array): the engine adds its bucket directory
     (sfx_index_create_dev); `query` = batched positions() / contains() / any_position(); `match_stats` = the

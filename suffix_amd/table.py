@@ -18,6 +18,7 @@ Same method names, argument meaning and error behaviour as the Rust API:
     (none)                                   .positions_batch(qs) / .contains_batch(qs)
     (none)                                   .repeat_lens(scope) / .repeated_spans(min_len, scope)
     (none)                                   .match_stats(query, max_len) / .shared_spans(query, min_len)
+    (none)                                   .bwt(sample_step) / suffix_amd.unbwt(bwt, samples, sample_step)
 
 Text is indexed by BYTES (every UTF-8 byte offset has a suffix, :29-31 of the
 crate docs and :379); `str` input is encoded as UTF-8.  Construction, LCP and
@@ -109,6 +110,27 @@ def _shared_spans(eng, match_stats, query, min_len):
         raise ValueError("min_len must be in 1 .. 2^32 - 1")
     b, e = _repeat_spans(eng, match_stats(query, max_len=min_len), min_len, None)
     return list(zip(b.tolist(), e.tolist()))
+
+
+def _bwt_step(sample_step):
+    step = int(sample_step or 0)
+    if step < 0 or step > 0x80000000 or step & (step - 1):
+        raise ValueError("sample_step must be 0 or a power of two of at most 2^31")
+    return step
+
+
+def unbwt(bwt, samples, sample_step, engine=None):
+    """The text (bytes) whose Burrows-Wheeler transform is (bwt, samples) as SuffixTable.bwt(sample_step) returns it.
+    A pair that is the transform of no text raises SuffixHipError: the walks check themselves (sfx_unbwt)."""
+    eng = engine or default_engine()
+    b = np.frombuffer(_as_bytes(bwt), dtype=np.uint8)
+    sm = np.ascontiguousarray(samples, dtype=np.uint32)
+    step = _bwt_step(sample_step)
+    out = np.zeros(b.size, dtype=np.uint8)
+    if b.size:
+        eng.require_device()
+    eng.check(eng.lib.sfx_unbwt(_ptr(b), int(b.size), _ptr(sm), int(sm.size), step, _ptr(out)), "sfx_unbwt")
+    return out.tobytes()
 
 
 class SuffixTable:
@@ -292,6 +314,21 @@ class SuffixTable:
         bytes (scope as for repeat_lens; "earlier" keeps the first copy of everything out of the report)."""
         b, e = _repeat_spans(self._eng, self.repeat_lens(scope), min_len, None)
         return list(zip(b.tolist(), e.tolist()))
+
+    # -- Burrows-Wheeler transform ----------------------------------------------------------------
+    def bwt(self, sample_step=256):
+        """-> (bwt bytes, samples uint32): the last column of the sorted rotations of text$ without its $ entry, and the
+        row of the suffix at every sample_step-th text position (samples[0] = the primary row; 0: the primary only).
+        `suffix_amd.unbwt(bwt, samples, sample_step)` restores the text."""
+        step = _bwt_step(sample_step)
+        n = self.len()
+        out = np.zeros(n, dtype=np.uint8)
+        samples = np.zeros(int(self._eng.lib.sfx_bwt_sample_count(n, step)), dtype=np.uint32)
+        if n:
+            self._eng.require_device()
+            self._eng.check(self._eng.lib.sfx_bwt_u32(_ptr(self._tarr), n, _ptr(self._table), step, _ptr(out), _ptr(samples)),
+                            "sfx_bwt_u32")
+        return out.tobytes(), samples
 
     # -- matching statistics of a second text ---------------------------------------------------
     def match_stats(self, query, max_len=None, with_source=False, with_intervals=False):

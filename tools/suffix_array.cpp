@@ -3,7 +3,7 @@
 // over the MI355X engine's C++ host mirror (include/suffix_table.hpp -> libsuffix_hip.so),
 // extended into the large-file driver SURVEY.md 8(f) asks for:
 //
-//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--time]
+//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--bwt PREFIX [--step S]] [--time]
 //
 //   --dump PREFIX   write PREFIX.sa (and PREFIX.lcp with --lcp) as raw little-endian u32
 //                   arrays -- the on-disk form SuffixTable::from_parts (:111-119) reloads
@@ -16,6 +16,11 @@
 //                   one "begin end src" line per maximal run of FILE2's bytes inside a stretch of at least L bytes
 //                   (--min-len L, default 32) that also occurs in FILE; src = a position in FILE of the match that
 //                   starts at `begin`
+//   --bwt PREFIX    write the Burrows-Wheeler transform: PREFIX.bwt (n raw bytes) and PREFIX.bwi (little-endian u32: the
+//                   sample step S, then the sampled rows; --step S, 0 or a power of two, default 256)
+//   suffix-array PREFIX.bwt --unbwt PREFIX.bwi --out OUT
+//                   restore the file from such a pair (no table is built); a pair that is the transform of no file ends
+//                   with status 2 and a message, and OUT is not written
 //   --time          wall-clock milliseconds of construction / LCP (host pointers, i.e.
 //                   including the PCIe copies: the device-resident rate is bench.py's)
 //
@@ -61,8 +66,8 @@ static double ms_since(std::chrono::steady_clock::time_point t0)
 
 int main(int argc, char** argv)
 {
-    std::string file, dump, load, match;
-    long long min_len = 32;
+    std::string file, dump, load, match, bwt, unbwt, out;
+    long long min_len = 32, step = 256;
     std::vector<std::string> queries;
     bool want_lcp = false, timing = false, earlier = false;
     long long repeats = -1;
@@ -83,6 +88,13 @@ int main(int argc, char** argv)
             min_len = atoll(need("--min-len"));
             if (min_len < 1 || min_len > 0xFFFFFFFFll) { fprintf(stderr, "--min-len needs a length of at least 1\n"); return 1; }
         }
+        else if (a == "--bwt") bwt = need("--bwt");
+        else if (a == "--unbwt") unbwt = need("--unbwt");
+        else if (a == "--out") out = need("--out");
+        else if (a == "--step") {
+            step = atoll(need("--step"));
+            if (step < 0 || step > 0x80000000ll || (step & (step - 1))) { fprintf(stderr, "--step needs 0 or a power of two\n"); return 1; }
+        }
         else if (a == "--repeats") {
             repeats = atoll(need("--repeats"));
             if (repeats < 1 || repeats > 0xFFFFFFFFll) { fprintf(stderr, "--repeats needs a length of at least 1\n"); return 1; }
@@ -91,11 +103,35 @@ int main(int argc, char** argv)
         else file = a;
     }
     if (file.empty()) {
-        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--time]\n");
+        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--bwt PREFIX [--step S]] [--time]\n");
         return 1;
     }
     std::string text;
     if (!read_file(file, &text)) { fprintf(stderr, "cannot read %s\n", file.c_str()); return 1; }
+    if (!unbwt.empty()) {                                               // FILE is a transform: restore, build nothing
+        if (out.empty()) { fprintf(stderr, "--unbwt needs --out OUT\n"); return 1; }
+        std::vector<uint32_t> bwi;
+        std::string raw;
+        if (!read_file(unbwt, &raw)) { fprintf(stderr, "cannot read %s\n", unbwt.c_str()); return 1; }
+        if (raw.size() % 4 || raw.size() < 4) { fprintf(stderr, "suffix-array: %s is no sample file (corrupted pair)\n", unbwt.c_str()); return 2; }
+        bwi.resize(raw.size() / 4);
+        memcpy(bwi.data(), raw.data(), raw.size());
+        try {
+            const uint32_t s = bwi[0];
+            bwi.erase(bwi.begin());
+            const std::string restored = suffix::SuffixTable::unbwt(text, bwi, s);
+            std::ofstream f(out, std::ios::binary);
+            if (!f || (!restored.empty() && !f.write(restored.data(), (std::streamsize)restored.size()))) {
+                fprintf(stderr, "cannot write %s\n", out.c_str());
+                return 1;
+            }
+            std::cout << "Restored: " << restored.size() << " bytes\n";
+        } catch (const std::exception& ex) {
+            fprintf(stderr, "suffix-array: %s and %s are no transform of any file (corrupted pair): %s\n", file.c_str(), unbwt.c_str(), ex.what());
+            return 2;
+        }
+        return 0;
+    }
     std::string other;
     if (!match.empty() && !read_file(match, &other)) { fprintf(stderr, "cannot read %s\n", match.c_str()); return 1; }
     try {
@@ -151,6 +187,20 @@ int main(int argc, char** argv)
             for (const auto& be : spans) covered += be.second - be.first;
             std::cout << "Shared with " << match << " (>= " << min_len << " bytes): " << spans.size() << " spans, " << covered << " bytes\n";
             for (const auto& be : spans) std::cout << be.first << " " << be.second << " " << ms.src[be.first] << "\n";
+        }
+        if (!bwt.empty()) {
+            t0 = std::chrono::steady_clock::now();
+            const auto tr = st.bwt((uint32_t)step);
+            if (timing) std::cout << "bwt ms: " << ms_since(t0) << "\n";
+            std::vector<uint32_t> bwi(1, (uint32_t)step);
+            bwi.insert(bwi.end(), tr.samples.begin(), tr.samples.end());
+            std::ofstream f(bwt + ".bwt", std::ios::binary);
+            if (!f || (!tr.bwt.empty() && !f.write(tr.bwt.data(), (std::streamsize)tr.bwt.size())) || !write_u32(bwt + ".bwi", bwi)) {
+                fprintf(stderr, "cannot write %s.*\n", bwt.c_str());
+                return 1;
+            }
+            std::cout << "BWT: primary " << (tr.samples.empty() ? 0u : tr.samples[0]) << ", " << tr.samples.size() << " samples (step " << step
+                      << ")\n";
         }
     } catch (const std::exception& ex) {
         fprintf(stderr, "suffix-array: %s\n", ex.what());
