@@ -373,8 +373,7 @@ int sfx_gindex_match_stats(const sfx_gindex* gx, const uint8_t* query, uint64_t 
  *   GPU for minutes; 2^20 steps of one idle-latency HBM miss each (about 900 cycles) stay well under a few seconds.
  * sfx_unbwt: the same with host buffers.
  * Not covered: the transform of a collection (per-document terminators); inversion without samples at scale (list
- * ranking); occurrence tables and backward search (an FM-index -- its locate would reuse this sample layout); the
- * transform without a table. */
+ * ranking); the transform without a table. */
 #define SFX_UNBWT_MAX_CHAIN (1u << 20)
 uint64_t sfx_bwt_sample_count(uint64_t n, uint32_t sample_step);
 int sfx_bwt_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t sample_step,
@@ -386,6 +385,64 @@ int sfx_unbwt_dev(const uint8_t* d_bwt, uint64_t n, const uint32_t* d_samples, u
                   uint8_t* d_text_out, void* d_workspace, uint64_t workspace_bytes, void* stream);
 int sfx_unbwt(const uint8_t* bwt, uint64_t n, const uint32_t* samples, uint64_t nsamples, uint32_t sample_step,
               uint8_t* text_out);
+
+/* ---- FM-index: backward-search count and locate over the (bwt, samples) pair -----------
+ * Rows, primary, bwt, samples and sample_step s as above.  The index answers positions() / contains() from the pair
+ * alone -- neither the text nor the table -- in about 1.4-1.5 n bytes of HBM; a pattern of m bytes costs m steps
+ * whatever n is.
+ *   C[c]        the number of bytes of bwt below c
+ *   i(R)        R <= primary ? R : R - 1 for a row R in [0, n + 1]: the bwt entries in front of row R, in [0, n]
+ *   occ(c, R)   the number of c in bwt[0 .. i(R))
+ *   count       a non-empty pattern P starts from the rows [0, n + 1); for c = P[m-1] down to P[0]:
+ *               lo = 1 + C[c] + occ(c, lo), hi = 1 + C[c] + occ(c, hi); empty as soon as lo >= hi or c does not occur.
+ *               (start, end) = (lo - 1, hi - 1) are table ranks: exactly the interval sfx_positions_batch reports.
+ *               Every empty result is (0, 0): no match, the empty pattern, n == 0.
+ *   lookup      the table entry of rank r: R = r + 1, steps = 0; while R is no sampled row: c = bwt[i(R)],
+ *               R = 1 + C[c] + occ(c, R), steps++; at the row of sample k the answer is k * s + steps.  samples[0] =
+ *               primary is always sampled, so the $ row is never dereferenced; a true transform needs at most s - 1
+ *               steps (n - 1 for s == 0).
+ * The structure (one device allocation the handle owns; the caller may free the pair after creation): the live bytes
+ * get dense codes (sigma of them, sigma' = sigma rounded up to a multiple of 4); bwt is cut into blocks of occ_step = B
+ * entries laid out as [sigma' u32: occurrences of every code before the block | B bytes], one counts-only block behind
+ * the last; a bit per row marks the sampled rows, 480 rows and a running count per 64-byte line; one u32 per sample
+ * gives, in row order, its number k.  occ_step is a power of two in [32, 4096]; 0 picks the smallest power of two
+ * >= 16 sigma' within [64, 4096], which keeps the count words at or below n / 4 bytes.
+ *
+ * sfx_fm_bytes: an upper bound on the HBM a handle over such a pair holds, whatever its alphabet; 0 for n == 0 or
+ *   arguments creation would refuse.
+ * sfx_fm_create_dev: builds on the caller's stream and synchronises it (the alphabet is read back before the blocks
+ *   can be sized, one flag word at the end).  d_bwt may have any alignment, d_samples needs 4 bytes.  SFX_ERR_ARG:
+ *   a step that is neither 0 nor a power of two; nsamples != sfx_bwt_sample_count(n, sample_step); an occ_step that
+ *   is neither 0 nor a power of two in [32, 4096]; a sample outside [1, n]; two equal samples.  n > u32::MAX is
+ *   SFX_ERR_TOO_LARGE.  n == 0 gives a valid empty index.  Creation does NOT prove that the pair is a transform
+ *   (sfx_unbwt is the complete check); what holds for every pair it accepts is that no later call reads or writes out
+ *   of bounds: rows stay in [0, n], and a lookup walk is cut off after min(n, s) steps (n for s == 0).
+ * sfx_fm_count_dev / sfx_fm_lookup_dev: one launch on the caller's stream, no workspace, no synchronisation.
+ *   d_qbytes may have any alignment, d_qoff (nq + 1 offsets) needs 8 bytes, the u32 arrays 4.  d_ranks == NULL means the
+ *   ranks first + j, j in [0, count): first = 0, count = n regenerates the whole suffix array.  A rank >= n, a walk
+ *   that was cut off and a position that would lie outside the text (either only for a pair that is no transform) are
+ *   written as UINT32_MAX.  sfx_fm_lookup* is SFX_ERR_ARG on an index whose chain -- min(n, s), n for s == 0 -- exceeds
+ *   SFX_UNBWT_MAX_CHAIN; sfx_fm_count* works on such an index.
+ * sfx_fm_create / sfx_fm_count / sfx_fm_lookup: the same with host buffers.
+ * Not covered: collections (per-document terminators); 2-bit packing for DNA; building the index without first having
+ * a table; bidirectional search; the multi-GPU partitioned path. */
+typedef struct sfx_fm sfx_fm;
+typedef struct { uint64_t n, bytes; uint32_t sigma, occ_step, sample_step, nsamples; } sfx_fm_info_t;
+uint64_t sfx_fm_bytes(uint64_t n, uint32_t sample_step, uint32_t occ_step);
+int sfx_fm_create_dev(const uint8_t* d_bwt, uint64_t n, const uint32_t* d_samples, uint64_t nsamples,
+                      uint32_t sample_step, uint32_t occ_step, void* stream, sfx_fm** out);
+int sfx_fm_create(const uint8_t* bwt, uint64_t n, const uint32_t* samples, uint64_t nsamples,
+                  uint32_t sample_step, uint32_t occ_step, sfx_fm** out);
+void sfx_fm_destroy(sfx_fm* fm);
+int sfx_fm_info(const sfx_fm* fm, sfx_fm_info_t* info_out);
+int sfx_fm_count_dev(const sfx_fm* fm, const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq,
+                     uint32_t* d_start, uint32_t* d_end, void* stream);
+int sfx_fm_count(const sfx_fm* fm, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq,
+                 uint32_t* start_out, uint32_t* end_out);
+int sfx_fm_lookup_dev(const sfx_fm* fm, const uint32_t* d_ranks /* NULL: first + j */, uint64_t first, uint64_t count,
+                      uint32_t* d_pos, void* stream);
+int sfx_fm_lookup(const sfx_fm* fm, const uint32_t* ranks /* NULL: first + j */, uint64_t first, uint64_t count,
+                  uint32_t* pos_out);
 
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the

@@ -8,7 +8,8 @@
 //   new_ / new_naive (doc-hidden upstream, :93-100: the definition, sorted on the host -- the reference's own test oracle,
 //   tests/tests.rs:18-20; never a fallback of new_) / from_parts / into_parts / lcp_lens / table / text / len / is_empty /
 //   suffix / suffix_bytes / contains / positions / any_position,
-// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans and bwt / unbwt.  Errors that are panics
+// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans, bwt / unbwt and fm_index (class FmIndex
+// below: the same queries from the transform alone).  Errors that are panics
 // in the reference (assert! :380, assert_eq! :117) are std::runtime_error /
 // std::length_error here.  Text is indexed by BYTES (:379).
 #pragma once
@@ -236,6 +237,88 @@ private:
     std::string text_;
     std::vector<uint32_t> table_;
     mutable std::unique_ptr<LazyIndex> lazy_ = std::make_unique<LazyIndex>();
+};
+
+// additive: backward search over the pair of SuffixTable::bwt (suffix_hip.h, sfx_fm_*): count / contains / positions of a
+// pattern from (bwt, samples) alone.  The handle lives in device memory (about 1.4 n bytes: nbytes()); neither the text
+// nor the table is kept.  positions(q) equals SuffixTable::positions(q) element for element, in table order.
+class FmIndex {
+public:
+    static FmIndex from_bwt(std::string_view bwt, const std::vector<uint32_t>& samples, uint32_t sample_step, uint32_t occ_step = 0)
+    {
+        FmIndex fm;
+        check(sfx_fm_create(reinterpret_cast<const uint8_t*>(bwt.data()), bwt.size(), samples.data(), samples.size(), sample_step,
+                            occ_step, &fm.h_), "FmIndex::from_bwt");
+        check(sfx_fm_info(fm.h_, &fm.info_), "sfx_fm_info");
+        return fm;
+    }
+    static FmIndex from_table(const SuffixTable& st, uint32_t sample_step = 64, uint32_t occ_step = 0)
+    {
+        const SuffixTable::Bwt tr = st.bwt(sample_step);
+        return from_bwt(tr.bwt, tr.samples, sample_step, occ_step);
+    }
+    static FmIndex from_text(std::string text, uint32_t sample_step = 64, uint32_t occ_step = 0)
+    {
+        return from_table(SuffixTable::new_(std::move(text)), sample_step, occ_step);
+    }
+    FmIndex(FmIndex&& o) noexcept : h_(o.h_), info_(o.info_) { o.h_ = nullptr; }
+    FmIndex& operator=(FmIndex&& o) noexcept
+    {
+        if (this != &o) { if (h_) sfx_fm_destroy(h_); h_ = o.h_; info_ = o.info_; o.h_ = nullptr; }
+        return *this;
+    }
+    FmIndex(const FmIndex&) = delete;
+    FmIndex& operator=(const FmIndex&) = delete;
+    ~FmIndex() { if (h_) sfx_fm_destroy(h_); }
+
+    size_t len() const { return (size_t)info_.n; }
+    uint64_t nbytes() const { return info_.bytes; }
+    const sfx_fm_info_t& info() const { return info_; }
+    // (start, end) table ranks per pattern, (0, 0) where there is no match: what SuffixTable::positions_batch returns
+    std::vector<std::pair<uint32_t, uint32_t>> count_batch(const std::vector<std::string_view>& qs) const
+    {
+        std::vector<uint64_t> off(qs.size() + 1, 0);
+        std::string blob;
+        for (size_t k = 0; k < qs.size(); k++) { blob.append(qs[k]); off[k + 1] = blob.size(); }
+        std::vector<uint32_t> s(qs.size()), e(qs.size());
+        if (!qs.empty())
+            check(sfx_fm_count(h_, reinterpret_cast<const uint8_t*>(blob.data()), off.data(), qs.size(), s.data(), e.data()), "FmIndex::count");
+        std::vector<std::pair<uint32_t, uint32_t>> out(qs.size());
+        for (size_t k = 0; k < qs.size(); k++) out[k] = {s[k], e[k]};
+        return out;
+    }
+    uint64_t count(std::string_view q) const { const auto se = count_batch({q}); return se[0].second - se[0].first; }
+    bool contains(std::string_view q) const { return count(q) > 0; }
+    // table entries of the ranks first .. first + count - 1 (UINT32_MAX for a rank >= len())
+    std::vector<uint32_t> sa_range(uint64_t first, uint64_t count) const
+    {
+        std::vector<uint32_t> pos((size_t)count);
+        if (count) check(sfx_fm_lookup(h_, nullptr, first, count, pos.data()), "FmIndex::sa_range");
+        return pos;
+    }
+    std::vector<uint32_t> lookup(const std::vector<uint32_t>& ranks) const
+    {
+        std::vector<uint32_t> pos(ranks.size());
+        if (!ranks.empty()) check(sfx_fm_lookup(h_, ranks.data(), 0, ranks.size(), pos.data()), "FmIndex::lookup");
+        return pos;
+    }
+    std::vector<uint32_t> positions(std::string_view q) const
+    {
+        const auto se = count_batch({q});
+        return sa_range(se[0].first, se[0].second - se[0].first);
+    }
+
+private:
+    FmIndex() = default;
+    static void check(int status, const char* what)
+    {
+        if (status == SFX_OK) return;
+        std::string msg = std::string(what) + ": " + sfx_strerror(status) + " " + sfx_last_hip_error();
+        if (status == SFX_ERR_TOO_LARGE) throw std::length_error(msg);
+        throw std::runtime_error(msg);
+    }
+    sfx_fm* h_ = nullptr;
+    sfx_fm_info_t info_{};
 };
 
 }  // namespace suffix

@@ -75,6 +75,9 @@ extern "C" {
     fn sfx_unbwt_dev(d_bwt: *const u8, n: u64, d_samples: *const u32, nsamples: u64, sample_step: u32,
                      d_text_out: *mut u8, d_workspace: *mut c_void, workspace_bytes: u64,
                      stream: *mut c_void) -> c_int;
+    // FM-index over that pair (sfx_fm_*): the size bound; the handle functions take `sfx_fm*`, a type the signature check
+    // of this block (tests/test_rust_crate.py) has no mapping for yet, so they are not bound here
+    fn sfx_fm_bytes(n: u64, sample_step: u32, occ_step: u32) -> u64;
     // suffix_tree's node table with ordered children (children(), preorder(), leaves(), suffix_indices() read it)
     #[allow(dead_code)]
     fn sfx_suffix_tree_u32(text: *const u8, sa: *const u32, lcp: *const u32, n: u64, node_capacity: u64,
@@ -193,6 +196,13 @@ pub fn unbwt(bwt: &[u8], samples: &[u32], sample_step: u32) -> Option<Vec<u8>> {
     }
     check(rc, "sfx_unbwt");
     Some(out)
+}
+
+/// An upper bound on the device memory an FM-index over the transform of `n` bytes holds (`sfx_fm_create`), whatever the
+/// alphabet; 0 for `n == 0` or steps the engine refuses (`sample_step`: 0 or a power of two; `occ_step`: 0 or a power of
+/// two in 32..=4096).
+pub fn fm_index_bytes(n: usize, sample_step: u32, occ_step: u32) -> u64 {
+    unsafe { sfx_fm_bytes(n as u64, sample_step, occ_step) }
 }
 
 /// Additive API: many `positions()` at once.  Returns (start, end) pairs;

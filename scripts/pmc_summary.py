@@ -81,6 +81,7 @@ NAMES = [
     ("k_doc_lookup", "doc_lookup"), ("k_query_batch_tree", "query_batch_tree"),
     ("k_query_batch_dir", "query_batch_dir"), ("k_query_tree_long", "query_tree_long"), ("k_query_batch", "query_batch"),
     ("k_bwt_primary", "bwt_primary"), ("k_bwt_gather", "bwt_gather"), ("k_bwt_rank", "bwt_rank"), ("k_unbwt_walk", "unbwt_walk"),
+    ("k_fm_count", "fm_count"), ("k_fm_lookup", "fm_lookup"), ("k_fm_", "fm_build"),
     ("k_ms_search_dir", "ms_search_dir"), ("k_ms_search", "ms_search"), ("k_ms_gsa_search", "ms_gsa_search"),
     # -- not part of a build's profile: the polled read-back and the memory-system probes
     ("detail::k_post_words", "post_words"), ("k_mb_copy", "mb_copy"), ("k_mb_gather", "mb_gather"), ("k_mb_scatter", "mb_scatter"),

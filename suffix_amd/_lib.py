@@ -40,6 +40,13 @@ class BuildStats(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
+class FmInfo(ctypes.Structure):
+    _fields_ = [("n", _u64), ("bytes", _u64), ("sigma", _u32), ("occ_step", _u32), ("sample_step", _u32), ("nsamples", _u32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # every symbol include/suffix_hip.h declares: (name, restype, argtypes)
 ABI = [
     ("sfx_strerror", ctypes.c_char_p, [_int]),
@@ -99,6 +106,15 @@ ABI = [
     ("sfx_unbwt_workspace_bytes", _u64, [_u64]),
     ("sfx_unbwt_dev", _int, [_vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, _vp]),
     ("sfx_unbwt", _int, [_vp, _u64, _vp, _u64, _u32, _vp]),
+    ("sfx_fm_bytes", _u64, [_u64, _u32, _u32]),
+    ("sfx_fm_create_dev", _int, [_vp, _u64, _vp, _u64, _u32, _u32, _vp, ctypes.POINTER(_vp)]),
+    ("sfx_fm_create", _int, [_vp, _u64, _vp, _u64, _u32, _u32, ctypes.POINTER(_vp)]),
+    ("sfx_fm_destroy", None, [_vp]),
+    ("sfx_fm_info", _int, [_vp, ctypes.POINTER(FmInfo)]),
+    ("sfx_fm_count_dev", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    ("sfx_fm_count", _int, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    ("sfx_fm_lookup_dev", _int, [_vp, _vp, _u64, _u64, _vp, _vp]),
+    ("sfx_fm_lookup", _int, [_vp, _vp, _u64, _u64, _vp]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "sfx_host.hpp"
+#include "sfx_fm.hip"   // the FM-index: kernels and host side, one translation unit with its entry points below
 
 namespace sfx {
 
@@ -777,6 +778,83 @@ int sfx_unbwt(const uint8_t* bwt, uint64_t n, const uint32_t* samples, uint64_t 
     SFX_HIP(hipMemcpyAsync(dm.p, samples, nsamples * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     SFX_TRY(unbwt_dev((const uint8_t*)db.p, n, (const uint32_t*)dm.p, nsamples, sample_step, (uint8_t*)dt.p, dw.p, wsb, st));
     SFX_HIP(hipMemcpyAsync(text_out, dt.p, n, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+
+// ---- FM-index over the (bwt, samples) pair (include/suffix_hip.h) -------------------------------
+uint64_t sfx_fm_bytes(uint64_t n, uint32_t sample_step, uint32_t occ_step) { return fm_bytes(n, sample_step, occ_step); }
+int sfx_fm_create_dev(const uint8_t* d_bwt, uint64_t n, const uint32_t* d_samples, uint64_t nsamples, uint32_t sample_step,
+                      uint32_t occ_step, void* stream, sfx_fm** out)
+{
+    SFX_NEED_U32(d_samples);
+    return fm_create_dev(d_bwt, n, d_samples, nsamples, sample_step, occ_step, (hipStream_t)stream, out);
+}
+int sfx_fm_create(const uint8_t* bwt, uint64_t n, const uint32_t* samples, uint64_t nsamples, uint32_t sample_step, uint32_t occ_step,
+                  sfx_fm** out)
+{
+    if (n == 0 || n > 0xFFFFFFFFull || nsamples != bwt_sample_count(n, sample_step) || !bwt || !samples)
+        return fm_create_dev(nullptr, n, nullptr, nsamples, sample_step, occ_step, nullptr, out);       // (decided on the host)
+    SFX_TRY(check_device());
+    DevBuf db, dm;
+    SFX_TRY(db.alloc(n));
+    SFX_TRY(dm.alloc(nsamples * sizeof(uint32_t)));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    SFX_HIP(hipMemcpyAsync(db.p, bwt, n, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dm.p, samples, nsamples * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    return fm_create_dev((const uint8_t*)db.p, n, (const uint32_t*)dm.p, nsamples, sample_step, occ_step, st, out);
+}
+void sfx_fm_destroy(sfx_fm* fm) { fm_destroy(fm); }
+int sfx_fm_info(const sfx_fm* fm, sfx_fm_info_t* info_out) { return fm_info(fm, info_out); }
+int sfx_fm_count_dev(const sfx_fm* fm, const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq, uint32_t* d_start, uint32_t* d_end,
+                     void* stream)
+{
+    SFX_NEED_U64(d_qoff);
+    SFX_NEED_U32(d_start, d_end);
+    return fm_count_dev(fm, d_qbytes, d_qoff, nq, d_start, d_end, (hipStream_t)stream);
+}
+int sfx_fm_count(const sfx_fm* fm, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq, uint32_t* start_out, uint32_t* end_out)
+{
+    if (!fm) return SFX_ERR_ARG;
+    if (nq == 0) return SFX_OK;
+    if (!qoff || !start_out || !end_out) return SFX_ERR_ARG;
+    const uint64_t qb = qoff[nq];
+    if (qb && !qbytes) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    DevBuf dq, dof, ds, de;
+    SFX_TRY(dq.alloc(qb));
+    SFX_TRY(dof.alloc((nq + 1) * sizeof(uint64_t)));
+    SFX_TRY(ds.alloc(nq * sizeof(uint32_t)));
+    SFX_TRY(de.alloc(nq * sizeof(uint32_t)));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    if (qb) SFX_HIP(hipMemcpyAsync(dq.p, qbytes, qb, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dof.p, qoff, (nq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(fm_count_dev(fm, (const uint8_t*)dq.p, (const uint64_t*)dof.p, nq, (uint32_t*)ds.p, (uint32_t*)de.p, st));
+    SFX_HIP(hipMemcpyAsync(start_out, ds.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipMemcpyAsync(end_out, de.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+int sfx_fm_lookup_dev(const sfx_fm* fm, const uint32_t* d_ranks, uint64_t first, uint64_t count, uint32_t* d_pos, void* stream)
+{
+    SFX_NEED_U32(d_ranks, d_pos);
+    return fm_lookup_dev(fm, d_ranks, first, count, d_pos, (hipStream_t)stream);
+}
+int sfx_fm_lookup(const sfx_fm* fm, const uint32_t* ranks, uint64_t first, uint64_t count, uint32_t* pos_out)
+{
+    if (!fm) return SFX_ERR_ARG;
+    if (count && !pos_out) return SFX_ERR_ARG;
+    if (count) SFX_TRY(check_device());
+    DevBuf dr, dp;
+    if (ranks) SFX_TRY(dr.alloc(count * sizeof(uint32_t)));
+    SFX_TRY(dp.alloc(count * sizeof(uint32_t)));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    if (ranks && count) SFX_HIP(hipMemcpyAsync(dr.p, ranks, count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(fm_lookup_dev(fm, ranks ? (const uint32_t*)dr.p : nullptr, first, count, (uint32_t*)dp.p, st));
+    if (count) SFX_HIP(hipMemcpyAsync(pos_out, dp.p, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     SFX_HIP(hipStreamSynchronize(st));
     return SFX_OK;
 }

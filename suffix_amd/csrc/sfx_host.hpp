@@ -463,6 +463,15 @@ int bwt_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t st
 uint64_t unbwt_workspace_bytes(uint64_t n);
 int unbwt_dev(const uint8_t* d_bwt, uint64_t n, const uint32_t* d_samples, uint64_t nsamples, uint32_t step, uint8_t* d_out, void* ws,
               uint64_t ws_bytes, hipStream_t st);
+// FM-index over the (bwt, samples) pair (sfx_fm.hip); creation synchronises the stream
+uint64_t fm_bytes(uint64_t n, uint32_t step, uint32_t occ_step);
+int fm_create_dev(const uint8_t* d_bwt, uint64_t n, const uint32_t* d_samples, uint64_t nsamples, uint32_t step, uint32_t occ_step,
+                  hipStream_t st, sfx_fm** out);
+void fm_destroy(sfx_fm* fm);
+int fm_info(const sfx_fm* fm, sfx_fm_info_t* info);
+int fm_count_dev(const sfx_fm* fm, const uint8_t* d_q, const uint64_t* d_qoff, uint64_t nq, uint32_t* d_start, uint32_t* d_end,
+                 hipStream_t st);
+int fm_lookup_dev(const sfx_fm* fm, const uint32_t* d_ranks, uint64_t first, uint64_t count, uint32_t* d_pos, hipStream_t st);
 // bucket directory of the resident index (sfx_query.hip)
 int dir_shape(uint64_t n, int bits, int* k_out, int* dbits_out, uint64_t* entries_out);
 uint64_t dir_scratch_words(uint64_t entries);

@@ -1602,8 +1602,8 @@ int suffix_tree_dev(const uint8_t* d_text, const uint32_t* d_sa, const uint32_t*
 // Rows are the n + 1 sorted rotations of T$: row 0 begins with $, row R >= 1 with suffix sa[R-1]; the primary is the row
 // of suffix 0, and row R != primary sits at bwt[R < primary ? R : R - 1].
 // Forward: a pass over the table finds the primary (samples[0]), then one rank per lane gathers T[sa - 1].
-// Not covered: collections (per-document terminators), inversion without samples at scale (list ranking), occurrence
-// tables / backward search, the transform without a table.
+// Not covered: collections (per-document terminators), inversion without samples at scale (list ranking), the transform
+// without a table.  (Occurrence tables and backward search: sfx_fm.hip.)
 __global__ void __launch_bounds__(kBlock)
 k_bwt_primary(const uint32_t* __restrict__ sa, uint64_t n, uint32_t* __restrict__ samples)
 {

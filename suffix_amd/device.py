@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from ._lib import REP_SCOPES, default_engine
+from ._lib import REP_SCOPES, FmInfo, default_engine
 
 
 def _on(t):
@@ -228,6 +228,92 @@ def unbwt(bwt, samples, sample_step, out=None, workspace=None, engine=None):
         eng.check(eng.lib.sfx_unbwt_dev(_p(bwt), n, _p(samples), samples.numel(), step, _p(out), _p(workspace), workspace.numel(),
                                         _stream_ptr(bwt)), "sfx_unbwt_dev")
     return out
+
+
+class FmDeviceIndex:
+    """FM-index over the device tensors (bwt, samples) of `bwt()`: backward-search count and locate from the pair alone
+    (sfx_fm_create_dev).  The handle owns its HBM and the binding keeps no reference to the pair -- it may be freed afterwards.  Creation synchronises the current
+    stream; `count`, `lookup` and `sa_range` queue on it without a synchronisation."""
+
+    def __init__(self, bwt, samples, sample_step, occ_step=0, engine=None):
+        self._eng = engine or default_engine()
+        _check_u8(bwt)
+        _check_u32(samples, "samples")
+        if samples.device != bwt.device:
+            raise ValueError(f"samples must be on the transform's device ({bwt.device})")
+        step = _bwt_step(sample_step)
+        if bwt.is_cuda:
+            self._eng.require_device()
+        self._dev = bwt.device
+        # (a tensor of the device, for _on / _stream_ptr; its own storage: a slice of bwt would keep the transform in HBM)
+        self._on = torch.empty(0, dtype=torch.uint8, device=bwt.device)
+        h = ctypes.c_void_p()
+        with _on(bwt):
+            self._eng.check(self._eng.lib.sfx_fm_create_dev(_p(bwt), bwt.numel(), _p(samples), samples.numel(), step, int(occ_step),
+                                                            _stream_ptr(bwt), ctypes.byref(h)), "sfx_fm_create_dev")
+        self._h = h
+        info = FmInfo()
+        self._eng.check(self._eng.lib.sfx_fm_info(h, ctypes.byref(info)), "sfx_fm_info")
+        self.info = info.as_dict()
+
+    def _check_queries(self, qbytes, qoff):
+        if qbytes.dtype != torch.uint8 or qbytes.dim() != 1 or not qbytes.is_contiguous():
+            raise TypeError("qbytes must be a contiguous 1-D uint8 tensor")
+        if qoff.dtype != torch.int64 or qoff.dim() != 1 or not qoff.is_contiguous() or qoff.numel() < 1:
+            raise TypeError("qoff must be a contiguous 1-D int64 tensor of nq + 1 offsets")
+        if qbytes.device != self._dev or qoff.device != self._dev:
+            raise ValueError(f"qbytes and qoff must be on the index's device ({self._dev})")
+
+    def count(self, qbytes, qoff):
+        """-> (start, end): the table ranks of the suffixes that begin with pattern k = qbytes[qoff[k]:qoff[k + 1]],
+        (0, 0) where there is none -- the interval DeviceIndex.query reports."""
+        self._check_queries(qbytes, qoff)
+        nq = qoff.numel() - 1
+        start = torch.empty(nq, dtype=torch.int32, device=self._dev)
+        end = torch.empty(nq, dtype=torch.int32, device=self._dev)
+        with _on(self._on):
+            self._eng.check(self._eng.lib.sfx_fm_count_dev(self._h, _p(qbytes), _p(qoff), nq, _p(start), _p(end), _stream_ptr(self._on)),
+                            "sfx_fm_count_dev")
+        return start, end
+
+    def lookup(self, ranks):
+        """The table entries of `ranks` (uint32 in int32 storage); 0xFFFFFFFF for a rank >= n."""
+        _check_u32(ranks, "ranks")
+        if ranks.device != self._dev:
+            raise ValueError(f"ranks must be on the index's device ({self._dev})")
+        pos = torch.empty(ranks.numel(), dtype=torch.int32, device=self._dev)
+        with _on(self._on):
+            self._eng.check(self._eng.lib.sfx_fm_lookup_dev(self._h, _p(ranks), 0, ranks.numel(), _p(pos), _stream_ptr(self._on)),
+                            "sfx_fm_lookup_dev")
+        return pos
+
+    def sa_range(self, first, count):
+        """table[first : first + count] regenerated from the index (sa_range(0, n): the whole suffix array)."""
+        pos = torch.empty(int(count), dtype=torch.int32, device=self._dev)
+        with _on(self._on):
+            self._eng.check(self._eng.lib.sfx_fm_lookup_dev(self._h, None, int(first), int(count), _p(pos), _stream_ptr(self._on)),
+                            "sfx_fm_lookup_dev")
+        return pos
+
+    def locate(self, qbytes, qoff):
+        """-> (offsets int64[nq + 1], positions): positions[offsets[k]:offsets[k + 1]] = the occurrences of pattern k in
+        table order.  The rank list between count and lookup is torch plumbing; reading its total synchronises."""
+        start, end = self.count(qbytes, qoff)
+        s = start.to(torch.int64) & 0xFFFFFFFF
+        cnt = (end.to(torch.int64) & 0xFFFFFFFF) - s
+        offsets = torch.zeros(cnt.numel() + 1, dtype=torch.int64, device=self._dev)
+        offsets[1:] = torch.cumsum(cnt, 0)
+        total = int(offsets[-1])
+        which = torch.repeat_interleave(torch.arange(cnt.numel(), device=self._dev), cnt)
+        ranks = s[which] + (torch.arange(total, device=self._dev) - offsets[:-1][which])
+        return offsets, self.lookup(ranks.to(torch.int32))
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._eng.lib.sfx_fm_destroy(h)
+
+    __del__ = close
 
 
 class DeviceIndex:

@@ -19,6 +19,7 @@ Same method names, argument meaning and error behaviour as the Rust API:
     (none)                                   .repeat_lens(scope) / .repeated_spans(min_len, scope)
     (none)                                   .match_stats(query, max_len) / .shared_spans(query, min_len)
     (none)                                   .bwt(sample_step) / suffix_amd.unbwt(bwt, samples, sample_step)
+    (none)                                   .fm_index(sample_step) / suffix_amd.FmIndex: the same queries from the transform alone
 
 Text is indexed by BYTES (every UTF-8 byte offset has a suffix, :29-31 of the
 crate docs and :379); `str` input is encoded as UTF-8.  Construction, LCP and
@@ -28,7 +29,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import REP_SCOPES, default_engine
+from ._lib import REP_SCOPES, FmInfo, default_engine
 
 _NONE = 0xFFFFFFFF
 
@@ -330,6 +331,12 @@ class SuffixTable:
                             "sfx_bwt_u32")
         return out.tobytes(), samples
 
+    def fm_index(self, sample_step=64, occ_step=0):
+        """An FmIndex over this table's transform: the same positions() / contains() / count() from about 1.4 n bytes
+        of HBM, without the text or the table."""
+        b, sm = self.bwt(sample_step)
+        return FmIndex.from_bwt(b, sm, sample_step, occ_step=occ_step, engine=self._eng)
+
     # -- matching statistics of a second text ---------------------------------------------------
     def match_stats(self, query, max_len=None, with_source=False, with_intervals=False):
         """len[i] = the longest prefix of query[i:] (at most max_len bytes; None = no cap) that occurs in the text --
@@ -352,3 +359,85 @@ class SuffixTable:
             lines.append(f"suffix[{rank}] {s}, {self._text[s:].decode('utf-8', 'replace')}")
         lines.append("-----------------------------------------")
         return "\n".join(lines) + "\n"
+
+
+class FmIndex:
+    """Backward search over the Burrows-Wheeler pair of SuffixTable.bwt(): count(), contains() and positions() of a
+    pattern from (bwt, samples) alone (sfx_fm_*; include/suffix_hip.h).  The handle lives in HBM (`nbytes`); neither the
+    text nor the table is kept.  A pattern of m bytes costs m steps whatever the text's length; every position costs at
+    most sample_step - 1 more."""
+
+    def __init__(self, handle, engine):
+        self._eng, self._h = engine, handle
+        info = FmInfo()
+        engine.check(engine.lib.sfx_fm_info(handle, ctypes.byref(info)), "sfx_fm_info")
+        self.info = info.as_dict()
+
+    @classmethod
+    def from_bwt(cls, bwt, samples, sample_step, occ_step=0, engine=None):
+        """(bwt, samples) as SuffixTable.bwt(sample_step) returns them.  Creation checks the samples, not that the
+        pair is a transform (suffix_amd.unbwt does)."""
+        eng = engine or default_engine()
+        b = np.frombuffer(_as_bytes(bwt), dtype=np.uint8)
+        sm = np.ascontiguousarray(samples, dtype=np.uint32)
+        step = _bwt_step(sample_step)
+        if b.size:
+            eng.require_device()
+        h = ctypes.c_void_p()
+        eng.check(eng.lib.sfx_fm_create(_ptr(b), int(b.size), _ptr(sm), int(sm.size), step, int(occ_step), ctypes.byref(h)),
+                  "sfx_fm_create")
+        return cls(h, eng)
+
+    @classmethod
+    def from_text(cls, text, sample_step=64, occ_step=0, engine=None):
+        return SuffixTable(text, engine=engine).fm_index(sample_step, occ_step)
+
+    def len(self):
+        return self.info["n"]
+
+    __len__ = len
+
+    @property
+    def nbytes(self):
+        return self.info["bytes"]
+
+    def count_batch(self, queries):
+        """-> (start, end) uint32 arrays of table ranks, as SuffixTable.positions_batch."""
+        blob, off = SuffixTable._pack(queries)
+        nq = off.size - 1
+        start = np.zeros(nq, dtype=np.uint32)
+        end = np.zeros(nq, dtype=np.uint32)
+        if nq:
+            self._eng.check(self._eng.lib.sfx_fm_count(self._h, _ptr(blob), _ptr(off), nq, _ptr(start), _ptr(end)), "sfx_fm_count")
+        return start, end
+
+    def count(self, query):
+        s, e = self.count_batch([query])
+        return int(e[0]) - int(s[0])
+
+    def contains(self, query):
+        return self.count(query) > 0
+
+    def lookup(self, ranks=None, first=0, count=None):
+        """Table entries of the given ranks (uint32 array), or of first .. first + count - 1; 0xFFFFFFFF for a rank >= n."""
+        if ranks is not None:
+            r = np.ascontiguousarray(ranks, dtype=np.uint32)
+            count = int(r.size)
+        else:
+            r, count = None, max(0, int(self.len() - first if count is None else count))
+        pos = np.zeros(count, dtype=np.uint32)
+        self._eng.check(self._eng.lib.sfx_fm_lookup(self._h, _ptr(r) if r is not None else None, int(first), count, _ptr(pos)),
+                        "sfx_fm_lookup")
+        return pos
+
+    def positions(self, query):
+        """The occurrences of `query` in table order: element for element SuffixTable.positions(query)."""
+        s, e = self.count_batch([query])
+        return self.lookup(first=int(s[0]), count=int(e[0]) - int(s[0]))
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._eng.lib.sfx_fm_destroy(h)
+
+    __del__ = close

@@ -21,6 +21,10 @@
 //   suffix-array PREFIX.bwt --unbwt PREFIX.bwi --out OUT
 //                   restore the file from such a pair (no table is built); a pair that is the transform of no file ends
 //                   with status 2 and a message, and OUT is not written
+//   suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]
+//                   answer the queries from such a pair through an FM-index: the same positions("Q") lines as
+//                   `suffix-array FILE --query Q`; no table is built and the text is never held (--occ-step B: the
+//                   entries per occurrence block, a power of two in 32 .. 4096; default: chosen from the alphabet)
 //   --time          wall-clock milliseconds of construction / LCP (host pointers, i.e.
 //                   including the PCIe copies: the device-resident rate is bench.py's)
 //
@@ -66,8 +70,8 @@ static double ms_since(std::chrono::steady_clock::time_point t0)
 
 int main(int argc, char** argv)
 {
-    std::string file, dump, load, match, bwt, unbwt, out;
-    long long min_len = 32, step = 256;
+    std::string file, dump, load, match, bwt, unbwt, out, fm;
+    long long min_len = 32, step = 256, occ_step = 0;
     std::vector<std::string> queries;
     bool want_lcp = false, timing = false, earlier = false;
     long long repeats = -1;
@@ -91,6 +95,11 @@ int main(int argc, char** argv)
         else if (a == "--bwt") bwt = need("--bwt");
         else if (a == "--unbwt") unbwt = need("--unbwt");
         else if (a == "--out") out = need("--out");
+        else if (a == "--fm") fm = need("--fm");
+        else if (a == "--occ-step") {
+            occ_step = atoll(need("--occ-step"));
+            if (occ_step < 32 || occ_step > 4096 || (occ_step & (occ_step - 1))) { fprintf(stderr, "--occ-step needs a power of two in 32 .. 4096\n"); return 1; }
+        }
         else if (a == "--step") {
             step = atoll(need("--step"));
             if (step < 0 || step > 0x80000000ll || (step & (step - 1))) { fprintf(stderr, "--step needs 0 or a power of two\n"); return 1; }
@@ -103,7 +112,7 @@ int main(int argc, char** argv)
         else file = a;
     }
     if (file.empty()) {
-        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--bwt PREFIX [--step S]] [--time]\n");
+        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--bwt PREFIX [--step S]] [--time]\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
         return 1;
     }
     std::string text;
@@ -128,6 +137,36 @@ int main(int argc, char** argv)
             std::cout << "Restored: " << restored.size() << " bytes\n";
         } catch (const std::exception& ex) {
             fprintf(stderr, "suffix-array: %s and %s are no transform of any file (corrupted pair): %s\n", file.c_str(), unbwt.c_str(), ex.what());
+            return 2;
+        }
+        return 0;
+    }
+    if (!fm.empty()) {                                                  // FILE is a transform: query it, build nothing
+        std::string raw;
+        if (!read_file(fm, &raw)) { fprintf(stderr, "cannot read %s\n", fm.c_str()); return 1; }
+        if (raw.size() % 4 || raw.size() < 4) { fprintf(stderr, "suffix-array: %s is no sample file (corrupted pair)\n", fm.c_str()); return 2; }
+        std::vector<uint32_t> bwi(raw.size() / 4);
+        memcpy(bwi.data(), raw.data(), raw.size());
+        try {
+            const uint32_t s = bwi[0];
+            bwi.erase(bwi.begin());
+            auto t0 = std::chrono::steady_clock::now();
+            const suffix::FmIndex ix = suffix::FmIndex::from_bwt(text, bwi, s, (uint32_t)occ_step);
+            std::string().swap(text);                                   // the index owns a copy in device memory
+            std::cout << "Suffixes: " << ix.len() << "\n";
+            if (timing) std::cout << "fm-index ms: " << ms_since(t0) << " (" << ix.nbytes() << " bytes)\n";
+            std::vector<std::string_view> qs(queries.begin(), queries.end());
+            const auto se = ix.count_batch(qs);
+            for (size_t k = 0; k < qs.size(); k++) {
+                const uint32_t st = se[k].first, e = se[k].second;
+                const std::vector<uint32_t> pos = ix.sa_range(st, std::min<uint32_t>(e - st, 8));
+                std::cout << "positions(\"" << queries[k] << "\"): " << (e - st);
+                for (size_t r = 0; r < pos.size(); r++) std::cout << (r == 0 ? " [" : ", ") << pos[r];
+                if (e > st) std::cout << (e - st > 8 ? ", ...]" : "]");
+                std::cout << "\n";
+            }
+        } catch (const std::exception& ex) {
+            fprintf(stderr, "suffix-array: %s\n", ex.what());
             return 2;
         }
         return 0;
