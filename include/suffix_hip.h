@@ -373,7 +373,8 @@ int sfx_gindex_match_stats(const sfx_gindex* gx, const uint8_t* query, uint64_t 
  *   GPU for minutes; 2^20 steps of one idle-latency HBM miss each (about 900 cycles) stay well under a few seconds.
  * sfx_unbwt: the same with host buffers.
  * Not covered: the transform of a collection (per-document terminators); inversion without samples at scale (list
- * ranking); the transform without a table. */
+ * ranking); the transform without a table.
+ * (The LZ77 calls further down have a per-launch bound of their own, SFX_LZ_MAX_STEPS = 4096 dependent loads per lane.) */
 #define SFX_UNBWT_MAX_CHAIN (1u << 20)
 uint64_t sfx_bwt_sample_count(uint64_t n, uint32_t sample_step);
 int sfx_bwt_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, uint32_t sample_step,
@@ -443,6 +444,52 @@ int sfx_fm_lookup_dev(const sfx_fm* fm, const uint32_t* d_ranks /* NULL: first +
                       uint32_t* d_pos, void* stream);
 int sfx_fm_lookup(const sfx_fm* fm, const uint32_t* ranks /* NULL: first + j */, uint64_t first, uint64_t count,
                   uint32_t* pos_out);
+
+/* ---- LZ77 factorization from the longest-previous-factor array, and its decoder ----------
+ * rep, src: n u32 values as sfx_repeat_lens_dev(..., SFX_REP_EARLIER, d_rep, d_src) writes them.  min_len >= 1.
+ *   r(p)      min(rep[p], n - p)
+ *   step(p)   r(p) if r(p) >= min_len, else 1;  next(p) = p + step(p)
+ *   phrases   the chain b_0 = 0, b_(k+1) = next(b_k) while b_k < n; z is their number
+ *   copy      phrase k with r(b_k) >= min_len: len = r, src = src[b_k], lit = 0
+ *   literal   every other phrase: len = 1, src = UINT32_MAX, lit = text[b_k]
+ * min_len = 1 is the classical self-referential LZ77 parse.  (begin, len) are unique; which src is reported is
+ * arbitrary, as everywhere in this library.  With the rep / src of a generalized table (truncated suffixes) phrases
+ * end at document ends by themselves.  next() is non-decreasing only for a true LPF array at min_len = 1; the
+ * kernels do not rely on it.
+ * Decoding z phrases (len, src, lit) into n bytes: begin = the exclusive sum of len; byte i of a literal is lit[k];
+ * byte i of a copy equals byte src[k] + (i - begin[k]); src[k] < begin[k] is required and overlap with the phrase
+ * itself is allowed ("a" * n is a literal and one copy of n - 1 bytes from position 0).
+ *
+ * sfx_lz_parse_dev: on the caller's stream, synchronised once at the end (z and two flags come back in one read).
+ *   *count_out is the total z; only the first `capacity` phrases are written and nothing past them; n always
+ *   suffices as capacity.  d_begin may be NULL; d_text == NULL writes no d_lit.  rep[p] is clipped to n - p before
+ *   it is used and no src is used as an address, so unchecked arrays stay in bounds and every loop ends; an entry
+ *   rep[p] > n - p anywhere, or a copy phrase with src >= begin, is SFX_ERR_ARG.  SFX_OK means the phrases tile [0, n)
+ *   and every copy points backwards -- not that the copied bytes are equal (decode and compare for that).
+ *   min_len == 0 is SFX_ERR_ARG, n > u32::MAX SFX_ERR_TOO_LARGE, n == 0 succeeds with z = 0, a workspace off
+ *   SFX_WORKSPACE_ALIGN is SFX_ERR_ARG and a short one SFX_ERR_WORKSPACE.  Workspace <= 9 n + 64 KiB bytes.
+ * sfx_lz_decode_dev: checks the whole list first (a zero len, a literal whose len is not 1, a copy with
+ *   src >= begin, lengths that do not sum to n: SFX_ERR_ARG with d_text_out untouched), then writes the text; it
+ *   synchronises for that check and once every few pointer-jumping rounds.  d_text_out overlapping an input is
+ *   SFX_ERR_ARG.  Workspace <= 5 n + 8 z + 64 KiB bytes.
+ * No lane of either call follows more than SFX_LZ_MAX_STEPS dependent global loads, for any input of n < 2^32:
+ *   a tile is SFX_LZ_MAX_STEPS positions, a group 2^8 tiles, and a text has at most 2^12 groups of 2^20 positions.
+ * sfx_lz77_u32 / sfx_unlz: the same with host buffers; sa / lcp == NULL are built.
+ * Not covered: LZ-End, LZ78, non-overlapping variants, entropy coding, an LZ index, the multi-GPU path, n >= 2^32. */
+#define SFX_LZ_MAX_STEPS (1u << 12)
+uint64_t sfx_lz_parse_workspace_bytes(uint64_t n);
+int sfx_lz_parse_dev(const uint32_t* d_rep, const uint32_t* d_src, const uint8_t* d_text /* NULL: no d_lit */,
+                     uint64_t n, uint32_t min_len,
+                     uint32_t* d_begin /* may be NULL */, uint32_t* d_len, uint32_t* d_psrc, uint8_t* d_lit,
+                     uint64_t capacity, uint64_t* count_out /* host */,
+                     void* d_workspace, uint64_t workspace_bytes, void* stream);
+uint64_t sfx_lz_decode_workspace_bytes(uint64_t n, uint64_t z);
+int sfx_lz_decode_dev(const uint32_t* d_len, const uint32_t* d_psrc, const uint8_t* d_lit, uint64_t z,
+                      uint64_t n, uint8_t* d_text_out, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_lz77_u32(const uint8_t* text, uint64_t n, const uint32_t* sa /* NULL: build */, const uint32_t* lcp /* NULL: build */,
+                 uint32_t min_len, uint32_t* begin_out, uint32_t* len_out, uint32_t* src_out, uint8_t* lit_out,
+                 uint64_t capacity, uint64_t* count_out);
+int sfx_unlz(const uint32_t* len, const uint32_t* src, const uint8_t* lit, uint64_t z, uint64_t n, uint8_t* text_out);
 
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the

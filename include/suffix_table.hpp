@@ -8,7 +8,7 @@
 //   new_ / new_naive (doc-hidden upstream, :93-100: the definition, sorted on the host -- the reference's own test oracle,
 //   tests/tests.rs:18-20; never a fallback of new_) / from_parts / into_parts / lcp_lens / table / text / len / is_empty /
 //   suffix / suffix_bytes / contains / positions / any_position,
-// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans, bwt / unbwt and fm_index (class FmIndex
+// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans, bwt / unbwt, lz77 / unlz and fm_index (class FmIndex
 // below: the same queries from the transform alone).  Errors that are panics
 // in the reference (assert! :380, assert_eq! :117) are std::runtime_error /
 // std::length_error here.  Text is indexed by BYTES (:379).
@@ -206,6 +206,42 @@ public:
                         reinterpret_cast<uint8_t*>(&out[0])), "unbwt");
         return out;
     }
+    // additive: the greedy LZ77 factorization (suffix_hip.h, sfx_lz77_u32): one entry per phrase.  A copy repeats len bytes
+    // from position src < its own begin (it may run into itself) and has lit 0; a literal has len 1, src UINT32_MAX and
+    // its byte in lit.  min_len >= 1: shorter repeats become literals; 1 is the classical parse.  size() = z.
+    struct Lz77 {
+        std::vector<uint32_t> begin, len, src;
+        std::string lit;
+        size_t size() const { return len.size(); }
+    };
+    Lz77 lz77(uint32_t min_len = 1) const
+    {
+        if (min_len == 0) throw std::invalid_argument("lz77: min_len must be at least 1");
+        const size_t n = text_.size();
+        Lz77 f{std::vector<uint32_t>(n), std::vector<uint32_t>(n), std::vector<uint32_t>(n), std::string(n, '\0')};
+        uint64_t z = 0;
+        if (n)
+            check(sfx_lz77_u32(bytes(text_), n, table_.data(), nullptr, min_len, f.begin.data(), f.len.data(), f.src.data(),
+                               reinterpret_cast<uint8_t*>(&f.lit[0]), n, &z), "lz77");
+        f.begin.resize((size_t)z);
+        f.len.resize((size_t)z);
+        f.src.resize((size_t)z);
+        f.lit.resize((size_t)z);
+        return f;
+    }
+    // ... and its decoder: the text of the phrases (len, src, lit).  A list that is no factorization -- a zero length, a
+    // literal of another length than 1, a copy that does not point backwards -- throws std::runtime_error.
+    static std::string unlz(const std::vector<uint32_t>& len, const std::vector<uint32_t>& src, std::string_view lit)
+    {
+        if (src.size() != len.size() || lit.size() != len.size()) throw std::invalid_argument("unlz: one entry per phrase");
+        uint64_t n = 0;
+        for (uint32_t l : len) n += l;
+        if (n > 0xFFFFFFFFull) throw std::length_error("unlz: more than u32::MAX bytes");
+        std::string out((size_t)n, '\0');
+        check(sfx_unlz(len.data(), src.data(), reinterpret_cast<const uint8_t*>(lit.data()), len.size(), n,
+                       reinterpret_cast<uint8_t*>(&out[0])), "unlz");
+        return out;
+    }
 
 private:
     SuffixTable() = default;
@@ -238,6 +274,11 @@ private:
     std::vector<uint32_t> table_;
     mutable std::unique_ptr<LazyIndex> lazy_ = std::make_unique<LazyIndex>();
 };
+
+inline std::string unlz(const std::vector<uint32_t>& len, const std::vector<uint32_t>& src, std::string_view lit)
+{
+    return SuffixTable::unlz(len, src, lit);
+}
 
 // additive: backward search over the pair of SuffixTable::bwt (suffix_hip.h, sfx_fm_*): count / contains / positions of a
 // pattern from (bwt, samples) alone.  The handle lives in device memory (about 1.4 n bytes: nbytes()); neither the text

@@ -75,6 +75,22 @@ extern "C" {
     fn sfx_unbwt_dev(d_bwt: *const u8, n: u64, d_samples: *const u32, nsamples: u64, sample_step: u32,
                      d_text_out: *mut u8, d_workspace: *mut c_void, workspace_bytes: u64,
                      stream: *mut c_void) -> c_int;
+    // LZ77 factorization from the EARLIER repeat lengths and its decoder (lz77 / unlz below; the *_dev forms for callers that
+    // keep their arrays in device memory)
+    #[allow(dead_code)]
+    fn sfx_lz_parse_workspace_bytes(n: u64) -> u64;
+    #[allow(dead_code)]
+    fn sfx_lz_parse_dev(d_rep: *const u32, d_src: *const u32, d_text: *const u8, n: u64, min_len: u32, d_begin: *mut u32,
+                        d_len: *mut u32, d_psrc: *mut u32, d_lit: *mut u8, capacity: u64, count_out: *mut u64,
+                        d_workspace: *mut c_void, workspace_bytes: u64, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_lz_decode_workspace_bytes(n: u64, z: u64) -> u64;
+    #[allow(dead_code)]
+    fn sfx_lz_decode_dev(d_len: *const u32, d_psrc: *const u32, d_lit: *const u8, z: u64, n: u64, d_text_out: *mut u8,
+                         d_workspace: *mut c_void, workspace_bytes: u64, stream: *mut c_void) -> c_int;
+    fn sfx_lz77_u32(text: *const u8, n: u64, sa: *const u32, lcp: *const u32, min_len: u32, begin_out: *mut u32,
+                    len_out: *mut u32, src_out: *mut u32, lit_out: *mut u8, capacity: u64, count_out: *mut u64) -> c_int;
+    fn sfx_unlz(len: *const u32, src: *const u32, lit: *const u8, z: u64, n: u64, text_out: *mut u8) -> c_int;
     // FM-index over that pair (sfx_fm_*): the size bound; the handle functions take `sfx_fm*`, a type the signature check
     // of this block (tests/test_rust_crate.py) has no mapping for yet, so they are not bound here
     fn sfx_fm_bytes(n: u64, sample_step: u32, occ_step: u32) -> u64;
@@ -195,6 +211,51 @@ pub fn unbwt(bwt: &[u8], samples: &[u32], sample_step: u32) -> Option<Vec<u8>> {
         return None;                                       // SFX_ERR_ARG
     }
     check(rc, "sfx_unbwt");
+    Some(out)
+}
+
+/// The greedy LZ77 factorization of a text: one entry per phrase in `len` / `src` / `lit`.  A copy repeats `len` bytes from
+/// position `src`, which lies before the phrase's own begin (it may run into itself) and has `lit` 0; a literal has
+/// `len` 1, `src` `u32::MAX` and its byte in `lit`.  The begins are the running sums of `len`.
+pub struct Lz77 {
+    pub len: Vec<u32>,
+    pub src: Vec<u32>,
+    pub lit: Vec<u8>,
+}
+
+/// The factorization of `text`: every phrase is the longest prefix of what is left that also starts at an earlier position
+/// when that is at least `min_len` (>= 1) bytes, else one literal byte.  `table`: the text's suffix array, or `None` to
+/// build it.
+pub fn lz77(text: &[u8], table: Option<&[u32]>, min_len: u32) -> Lz77 {
+    assert!(min_len >= 1, "min_len must be at least 1");
+    if let Some(t) = table {
+        assert_eq!(t.len(), text.len());
+    }
+    let n = text.len();
+    let (mut len, mut src, mut lit) = (vec![0u32; n], vec![0u32; n], vec![0u8; n]);
+    let mut count = 0u64;
+    check(unsafe {
+        sfx_lz77_u32(text.as_ptr(), n as u64, table.map_or(std::ptr::null(), |t| t.as_ptr()), std::ptr::null(), min_len,
+                     std::ptr::null_mut(), len.as_mut_ptr(), src.as_mut_ptr(), lit.as_mut_ptr(), n as u64, &mut count)
+    }, "sfx_lz77_u32");
+    let z = count as usize;
+    len.truncate(z);
+    src.truncate(z);
+    lit.truncate(z);
+    Lz77 { len, src, lit }
+}
+
+/// The text of a factorization, or `None` where the list is none: a zero length, a literal of another length than 1, a copy
+/// that does not point backwards.
+pub fn unlz(f: &Lz77) -> Option<Vec<u8>> {
+    assert!(f.src.len() == f.len.len() && f.lit.len() == f.len.len());
+    let n: u64 = f.len.iter().map(|&l| l as u64).sum();
+    let mut out = vec![0u8; n as usize];
+    let rc = unsafe { sfx_unlz(f.len.as_ptr(), f.src.as_ptr(), f.lit.as_ptr(), f.len.len() as u64, n, out.as_mut_ptr()) };
+    if rc == 1 {
+        return None;                                       // SFX_ERR_ARG
+    }
+    check(rc, "sfx_unlz");
     Some(out)
 }
 

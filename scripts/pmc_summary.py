@@ -81,6 +81,9 @@ NAMES = [
     ("k_doc_lookup", "doc_lookup"), ("k_query_batch_tree", "query_batch_tree"),
     ("k_query_batch_dir", "query_batch_dir"), ("k_query_tree_long", "query_tree_long"), ("k_query_batch", "query_batch"),
     ("k_bwt_primary", "bwt_primary"), ("k_bwt_gather", "bwt_gather"), ("k_bwt_rank", "bwt_rank"), ("k_unbwt_walk", "unbwt_walk"),
+    ("k_lz_exit", "lz_exit"), ("k_lz_hop", "lz_hop"), ("k_lz_walk_groups", "lz_walk_groups"), ("k_lz_walk_tiles", "lz_walk_tiles"),
+    ("k_lz_count", "lz_count"), ("k_lz_emit", "lz_emit"), ("k_lz_unscan_check", "unlz_scan"), ("k_lz_unorigin", "unlz_origin"),
+    ("k_lz_unjump", "unlz_jump"), ("k_lz_unfill", "unlz_fill"),
     ("k_fm_count", "fm_count"), ("k_fm_lookup", "fm_lookup"), ("k_fm_", "fm_build"),
     ("k_ms_search_dir", "ms_search_dir"), ("k_ms_search", "ms_search"), ("k_ms_gsa_search", "ms_gsa_search"),
     # -- not part of a build's profile: the polled read-back and the memory-system probes

@@ -115,6 +115,12 @@ ABI = [
     ("sfx_fm_count", _int, [_vp, _vp, _vp, _u64, _vp, _vp]),
     ("sfx_fm_lookup_dev", _int, [_vp, _vp, _u64, _u64, _vp, _vp]),
     ("sfx_fm_lookup", _int, [_vp, _vp, _u64, _u64, _vp]),
+    ("sfx_lz_parse_workspace_bytes", _u64, [_u64]),
+    ("sfx_lz_parse_dev", _int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64, _vp]),
+    ("sfx_lz_decode_workspace_bytes", _u64, [_u64, _u64]),
+    ("sfx_lz_decode_dev", _int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp]),
+    ("sfx_lz77_u32", _int, [_vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64)]),
+    ("sfx_unlz", _int, [_vp, _vp, _vp, _u64, _u64, _vp]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),

@@ -10,6 +10,7 @@
 
 #include "sfx_host.hpp"
 #include "sfx_fm.hip"   // the FM-index: kernels and host side, one translation unit with its entry points below
+#include "sfx_lz.hip"   // LZ77 factorization and its decoder, likewise
 
 namespace sfx {
 
@@ -855,6 +856,99 @@ int sfx_fm_lookup(const sfx_fm* fm, const uint32_t* ranks, uint64_t first, uint6
     if (ranks && count) SFX_HIP(hipMemcpyAsync(dr.p, ranks, count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     SFX_TRY(fm_lookup_dev(fm, ranks ? (const uint32_t*)dr.p : nullptr, first, count, (uint32_t*)dp.p, st));
     if (count) SFX_HIP(hipMemcpyAsync(pos_out, dp.p, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+
+// ---- LZ77 factorization from the EARLIER repeat lengths, and its decoder (include/suffix_hip.h) -----------------
+uint64_t sfx_lz_parse_workspace_bytes(uint64_t n) { return lz_parse_workspace_bytes(n); }
+int sfx_lz_parse_dev(const uint32_t* d_rep, const uint32_t* d_src, const uint8_t* d_text, uint64_t n, uint32_t min_len, uint32_t* d_begin,
+                     uint32_t* d_len, uint32_t* d_psrc, uint8_t* d_lit, uint64_t capacity, uint64_t* count_out, void* d_workspace,
+                     uint64_t workspace_bytes, void* stream)
+{
+    SFX_NEED_U32(d_rep, d_src, d_begin, d_len, d_psrc);
+    SFX_NEED_WS(d_workspace, workspace_bytes, lz_parse_workspace_bytes(n));
+    return lz_parse_dev(d_rep, d_src, d_text, n, min_len, d_begin, d_len, d_psrc, d_lit, capacity, count_out, d_workspace, workspace_bytes,
+                        (hipStream_t)stream);
+}
+uint64_t sfx_lz_decode_workspace_bytes(uint64_t n, uint64_t z) { return lz_decode_workspace_bytes(n, z); }
+int sfx_lz_decode_dev(const uint32_t* d_len, const uint32_t* d_psrc, const uint8_t* d_lit, uint64_t z, uint64_t n, uint8_t* d_text_out,
+                      void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    SFX_NEED_U32(d_len, d_psrc);
+    SFX_NEED_WS(d_workspace, workspace_bytes, lz_decode_workspace_bytes(n, z));
+    return lz_decode_dev(d_len, d_psrc, d_lit, z, n, d_text_out, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sfx_lz77_u32(const uint8_t* text, uint64_t n, const uint32_t* sa, const uint32_t* lcp, uint32_t min_len, uint32_t* begin_out,
+                 uint32_t* len_out, uint32_t* src_out, uint8_t* lit_out, uint64_t capacity, uint64_t* count_out)
+{
+    if (!count_out || min_len == 0) return SFX_ERR_ARG;
+    *count_out = 0;
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!text || (capacity && (!len_out || !src_out || !lit_out))) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    if (capacity > n) capacity = n;                                      // (no parse is longer)
+    const uint64_t bytes = n * sizeof(uint32_t), cb = capacity * sizeof(uint32_t);
+    const uint64_t wsb = dmax(dmax(sa ? (lcp ? 0 : lcp_workspace_bytes(n)) : sa_lcp_workspace_bytes(n),
+                                   repeat_lens_workspace_bytes(n, SFX_REP_EARLIER)), lz_parse_workspace_bytes(n));
+    DevBuf dt, ds, dl, dr, dq, db, dn, dp, dc, dw;
+    SFX_TRY(dt.alloc(n));
+    SFX_TRY(ds.alloc(bytes));
+    SFX_TRY(dl.alloc(bytes));
+    SFX_TRY(dr.alloc(bytes));
+    SFX_TRY(dq.alloc(bytes));
+    if (begin_out) SFX_TRY(db.alloc(cb));
+    SFX_TRY(dn.alloc(cb));
+    SFX_TRY(dp.alloc(cb));
+    SFX_TRY(dc.alloc(capacity));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(dt.p, text, n, hipMemcpyHostToDevice, st));
+    if (!sa) {
+        SFX_TRY(build_sa_lcp_u32_dev((const uint8_t*)dt.p, n, (uint32_t*)ds.p, (uint32_t*)dl.p, dw.p, wsb, st));
+    } else {
+        SFX_HIP(hipMemcpyAsync(ds.p, sa, bytes, hipMemcpyHostToDevice, st));
+        if (lcp)
+            SFX_HIP(hipMemcpyAsync(dl.p, lcp, bytes, hipMemcpyHostToDevice, st));
+        else
+            SFX_TRY(build_lcp_u32_dev((const uint8_t*)dt.p, n, (const uint32_t*)ds.p, (uint32_t*)dl.p, dw.p, wsb, st));
+    }
+    SFX_TRY(repeat_lens_dev((const uint32_t*)ds.p, (const uint32_t*)dl.p, nullptr, n, SFX_REP_EARLIER, (uint32_t*)dr.p, (uint32_t*)dq.p, dw.p,
+                            wsb, st));
+    SFX_TRY(lz_parse_dev((const uint32_t*)dr.p, (const uint32_t*)dq.p, (const uint8_t*)dt.p, n, min_len, begin_out ? (uint32_t*)db.p : nullptr,
+                         (uint32_t*)dn.p, (uint32_t*)dp.p, (uint8_t*)dc.p, capacity, count_out, dw.p, wsb, st));
+    const uint64_t k = dmin<uint64_t>(*count_out, capacity);
+    if (k) {
+        if (begin_out) SFX_HIP(hipMemcpyAsync(begin_out, db.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(len_out, dn.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(src_out, dp.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(lit_out, dc.p, k, hipMemcpyDeviceToHost, st));
+    }
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+int sfx_unlz(const uint32_t* len, const uint32_t* src, const uint8_t* lit, uint64_t z, uint64_t n, uint8_t* text_out)
+{
+    if (n > 0xFFFFFFFFull || z > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return z == 0 ? SFX_OK : SFX_ERR_ARG;
+    if (z == 0 || z > n || !len || !src || !lit || !text_out) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    const uint64_t wsb = lz_decode_workspace_bytes(n, z);
+    DevBuf dn, dp, dc, dt, dw;
+    SFX_TRY(dn.alloc(z * sizeof(uint32_t)));
+    SFX_TRY(dp.alloc(z * sizeof(uint32_t)));
+    SFX_TRY(dc.alloc(z));
+    SFX_TRY(dt.alloc(n));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    SFX_HIP(hipMemcpyAsync(dn.p, len, z * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dp.p, src, z * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dc.p, lit, z, hipMemcpyHostToDevice, st));
+    SFX_TRY(lz_decode_dev((const uint32_t*)dn.p, (const uint32_t*)dp.p, (const uint8_t*)dc.p, z, n, (uint8_t*)dt.p, dw.p, wsb, st));
+    SFX_HIP(hipMemcpyAsync(text_out, dt.p, n, hipMemcpyDeviceToHost, st));
     SFX_HIP(hipStreamSynchronize(st));
     return SFX_OK;
 }

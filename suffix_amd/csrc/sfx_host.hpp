@@ -472,6 +472,18 @@ int fm_info(const sfx_fm* fm, sfx_fm_info_t* info);
 int fm_count_dev(const sfx_fm* fm, const uint8_t* d_q, const uint64_t* d_qoff, uint64_t nq, uint32_t* d_start, uint32_t* d_end,
                  hipStream_t st);
 int fm_lookup_dev(const sfx_fm* fm, const uint32_t* d_ranks, uint64_t first, uint64_t count, uint32_t* d_pos, hipStream_t st);
+// exclusive scan of `count` u32 values, out[count] = the total; in place when the output is u32 too; part: kMaxGrid + 64
+// elements of the output type (sfx_tree.hip)
+int scan_u32_excl_dev(const uint32_t* in, uint64_t count, uint32_t* out, uint32_t* part, hipStream_t st);
+int scan_u32_to_u64_excl_dev(const uint32_t* in, uint64_t count, uint64_t* out, uint64_t* part, hipStream_t st);
+// LZ77 factorization from the EARLIER repeat lengths and its decoder (sfx_lz.hip); both synchronise the stream
+uint64_t lz_parse_workspace_bytes(uint64_t n);
+int lz_parse_dev(const uint32_t* d_rep, const uint32_t* d_src, const uint8_t* d_text, uint64_t n, uint32_t min_len, uint32_t* d_begin,
+                 uint32_t* d_len, uint32_t* d_psrc, uint8_t* d_lit, uint64_t capacity, uint64_t* count_out, void* ws, uint64_t ws_bytes,
+                 hipStream_t st);
+uint64_t lz_decode_workspace_bytes(uint64_t n, uint64_t z);
+int lz_decode_dev(const uint32_t* d_len, const uint32_t* d_psrc, const uint8_t* d_lit, uint64_t z, uint64_t n, uint8_t* d_out, void* ws,
+                  uint64_t ws_bytes, hipStream_t st);
 // bucket directory of the resident index (sfx_query.hip)
 int dir_shape(uint64_t n, int bits, int* k_out, int* dbits_out, uint64_t* entries_out);
 uint64_t dir_scratch_words(uint64_t entries);

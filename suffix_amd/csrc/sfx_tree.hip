@@ -466,6 +466,15 @@ static int gsa_scan(const uint32_t* in, uint64_t count, T* out, T* part, hipStre
                (const T*)part, out);
     return SFX_OK;
 }
+// the same scan for other translation units (sfx_lz.hip): part is kMaxGrid + 64 elements of the output type
+int scan_u32_excl_dev(const uint32_t* in, uint64_t count, uint32_t* out, uint32_t* part, hipStream_t st)
+{
+    return gsa_scan<uint32_t>(in, count, out, part, st);
+}
+int scan_u32_to_u64_excl_dev(const uint32_t* in, uint64_t count, uint64_t* out, uint64_t* part, hipStream_t st)
+{
+    return gsa_scan<uint64_t>(in, count, out, part, st);
+}
 // the affected suffixes in plain-rank order: key = L << 32 | position (sorted on the position bits first), value = rank
 __global__ void __launch_bounds__(kBlock)
 k_gsa_compact(const uint32_t* __restrict__ P, const uint32_t* __restrict__ sa, const uint32_t* __restrict__ rem, uint64_t n,

@@ -548,6 +548,87 @@ def repeat_spans(rep, min_len, doc_starts=None, engine=None):
     return torch.stack((begin[:k], end[:k]), dim=1)
 
 
+def lz_parse_workspace(n, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_lz_parse_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def lz_parse(rep, src, text=None, min_len=1, want_begin=True, workspace=None, engine=None):
+    """The greedy LZ77 factorization from the longest-previous-factor array: rep, src = repeat_lens(sa, lcp, "earlier",
+    want_src=True).  A phrase at position b copies rep[b] bytes from src[b] when rep[b] >= min_len and is the single
+    byte text[b] otherwise.  -> (begin, len, src, lit) cut to the z phrases: begin is None without want_begin, a
+    literal has src 0xFFFFFFFF (-1 in int32 storage), lit (uint8, None without text) is 0 for a copy.  Synchronises
+    the current stream once; arrays that are no repeat lengths raise SuffixHipError (sfx_lz_parse_dev)."""
+    eng = engine or default_engine()
+    _check_u32(rep, "rep")
+    n = rep.numel()
+    _check_u32(src, "src", n)
+    min_len = int(min_len)
+    if min_len < 1 or min_len > 0xFFFFFFFF:
+        raise ValueError("min_len must be in 1 .. 2^32 - 1")
+    if text is not None:
+        _check_u8(text)
+        if text.numel() != n:
+            raise ValueError(f"text must hold {n} bytes")
+    for t in (src, text):
+        if t is not None and t.device != rep.device:
+            raise ValueError(f"all arrays must be on one device ({rep.device})")
+    if rep.is_cuda:
+        eng.require_device()
+    dev = rep.device
+    begin = torch.empty(n, dtype=torch.int32, device=dev) if want_begin else None
+    ln = torch.empty(n, dtype=torch.int32, device=dev)
+    psrc = torch.empty(n, dtype=torch.int32, device=dev)
+    lit = torch.empty(n, dtype=torch.uint8, device=dev) if text is not None else None
+    if workspace is None:
+        workspace = lz_parse_workspace(n, dev, eng)
+    count = ctypes.c_uint64(0)
+    with _on(rep):
+        eng.check(eng.lib.sfx_lz_parse_dev(_p(rep), _p(src), _p(text), n, min_len, _p(begin), _p(ln), _p(psrc), _p(lit), n,
+                                           ctypes.byref(count), _p(workspace), workspace.numel(), _stream_ptr(rep)),
+                  "sfx_lz_parse_dev")
+    z = int(count.value)
+    cut = lambda t: None if t is None else t[:z].clone()          # (the phrases, not n entries of storage behind them)
+    return cut(begin), cut(ln), cut(psrc), cut(lit)
+
+
+def lz_decode_workspace(n, z, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_lz_decode_workspace_bytes(int(n), int(z))), dtype=torch.uint8, device=device)
+
+
+def lz_decode(len, src, lit, n=None, out=None, workspace=None, engine=None):
+    """The text of the phrases (len, src, lit) as lz_parse returns them; n = the sum of len when not given (one
+    read-back).  A list that is no factorization -- a zero length, a literal of another length than 1, a copy that
+    does not point backwards, a wrong sum -- raises SuffixHipError with `out` untouched (sfx_lz_decode_dev)."""
+    eng = engine or default_engine()
+    _check_u32(len, "len")
+    z = len.numel()
+    _check_u32(src, "src", z)
+    _check_u8(lit)
+    if lit.numel() != z:
+        raise ValueError(f"lit must hold {z} bytes")
+    for t in (src, lit):
+        if t.device != len.device:
+            raise ValueError(f"all arrays must be on one device ({len.device})")
+    if n is None:
+        n = int((len.to(torch.int64) & 0xFFFFFFFF).sum().item()) if z else 0
+    n = int(n)
+    if out is None:
+        out = torch.empty(min(n, 0xFFFFFFFF), dtype=torch.uint8, device=len.device)
+    _check_u8(out)
+    if out.numel() != min(n, 0xFFFFFFFF) or out.device != len.device:
+        raise ValueError(f"out must hold {n} bytes on {len.device}")
+    if workspace is None:
+        workspace = lz_decode_workspace(n, z, len.device, eng)
+    if len.is_cuda:
+        eng.require_device()
+    with _on(len):
+        eng.check(eng.lib.sfx_lz_decode_dev(_p(len), _p(src), _p(lit), z, n, _p(out), _p(workspace), workspace.numel(),
+                                            _stream_ptr(len)), "sfx_lz_decode_dev")
+    return out
+
+
 class GeneralizedDeviceIndex:
     """Resident generalized index over device tensors (text, doc_starts, GSA, DA) -- borrowed, keep them alive;
     `query` = per query (start, end, found, any, ndocs): matches inside one document only, ndocs = the number of

@@ -134,6 +134,46 @@ def unbwt(bwt, samples, sample_step, engine=None):
     return out.tobytes()
 
 
+def unlz(len, src, lit, engine=None):
+    """The text (bytes) of the LZ77 phrases (len, src, lit) as LzFactorization holds them: a literal (src 0xFFFFFFFF,
+    len 1) is its byte, a copy repeats len bytes from position src < its own begin and may overlap itself.  A list
+    that is no factorization raises SuffixHipError (sfx_unlz)."""
+    eng = engine or default_engine()
+    ln = np.ascontiguousarray(len, dtype=np.uint32)
+    sr = np.ascontiguousarray(src, dtype=np.uint32)
+    lt = np.frombuffer(_as_bytes(lit), dtype=np.uint8)
+    if sr.size != ln.size or lt.size != ln.size:
+        raise ValueError("len, src and lit must have one entry per phrase")
+    n = int(ln.sum(dtype=np.uint64))
+    out = np.zeros(min(n, _NONE), dtype=np.uint8)
+    if n:
+        eng.require_device()
+    eng.check(eng.lib.sfx_unlz(_ptr(ln), _ptr(sr), _ptr(lt), int(ln.size), n, _ptr(out)), "sfx_unlz")
+    return out.tobytes()
+
+
+class LzFactorization:
+    """The greedy LZ77 parse of a text (SuffixTable.lz77): numpy arrays begin / len / src (uint32) and lit (uint8), one
+    entry per phrase, and the text length n.  len(f) = z; iteration yields (begin, len, src) with src None for a literal."""
+
+    def __init__(self, begin, len, src, lit, n, engine=None):
+        self.begin, self.len, self.src, self.lit, self.n = begin, len, src, lit, int(n)
+        self._eng = engine
+
+    def __len__(self):
+        return int(self.len.size)
+
+    def __iter__(self):
+        for b, l, s in zip(self.begin.tolist(), self.len.tolist(), self.src.tolist()):
+            yield b, l, (None if s == _NONE else s)
+
+    def decode(self):
+        return unlz(self.len, self.src, self.lit, engine=self._eng)
+
+    def __repr__(self):
+        return f"LzFactorization(n={self.n}, z={len(self)})"
+
+
 class SuffixTable:
     def __init__(self, text, _table=None, engine=None):
         self._eng = engine or default_engine()
@@ -330,6 +370,24 @@ class SuffixTable:
             self._eng.check(self._eng.lib.sfx_bwt_u32(_ptr(self._tarr), n, _ptr(self._table), step, _ptr(out), _ptr(samples)),
                             "sfx_bwt_u32")
         return out.tobytes(), samples
+
+    # -- LZ77 factorization ---------------------------------------------------------------------------
+    def lz77(self, min_len=1):
+        """The greedy LZ77 factorization (LzFactorization): every phrase is the longest prefix of what is left that also
+        starts at an earlier position -- it may run into itself -- when that is at least min_len bytes, else one literal
+        byte.  min_len = 1 is the classical parse; len(result) is the phrase count z."""
+        min_len = int(min_len)
+        if min_len < 1 or min_len > 0xFFFFFFFF:
+            raise ValueError("min_len must be in 1 .. 2^32 - 1")
+        n = self.len()
+        arrs = [np.zeros(n, dtype=np.uint32) for _ in range(3)] + [np.zeros(n, dtype=np.uint8)]
+        count = ctypes.c_uint64(0)
+        if n:
+            self._eng.require_device()
+            self._eng.check(self._eng.lib.sfx_lz77_u32(_ptr(self._tarr), n, _ptr(self._table), None, min_len, *[_ptr(a) for a in arrs],
+                                                       n, ctypes.byref(count)), "sfx_lz77_u32")
+        z = int(count.value)
+        return LzFactorization(*[a[:z].copy() for a in arrs], n, engine=self._eng)
 
     def fm_index(self, sample_step=64, occ_step=0):
         """An FmIndex over this table's transform: the same positions() / contains() / count() from about 1.4 n bytes

@@ -3,7 +3,7 @@
 // over the MI355X engine's C++ host mirror (include/suffix_table.hpp -> libsuffix_hip.so),
 // extended into the large-file driver SURVEY.md 8(f) asks for:
 //
-//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--bwt PREFIX [--step S]] [--time]
+//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]
 //
 //   --dump PREFIX   write PREFIX.sa (and PREFIX.lcp with --lcp) as raw little-endian u32
 //                   arrays -- the on-disk form SuffixTable::from_parts (:111-119) reloads
@@ -25,6 +25,12 @@
 //                   answer the queries from such a pair through an FM-index: the same positions("Q") lines as
 //                   `suffix-array FILE --query Q`; no table is built and the text is never held (--occ-step B: the
 //                   entries per occurrence block, a power of two in 32 .. 4096; default: chosen from the alphabet)
+//   --lz PREFIX     write the greedy LZ77 factorization as PREFIX.lz and print "LZ77: z Z, literals K, longest L": a 16-byte
+//                   header (the magic "SFXLZ1\0\0", u32 n, u32 z, little-endian), then len[z], src[z] (u32) and lit[z] (bytes);
+//                   repeats shorter than --min-len L (default here: 1, the classical parse) become literals
+//   suffix-array PREFIX.lz --unlz --out OUT
+//                   restore the file from a factorization (no table is built); a truncated or corrupted one ends with
+//                   status 2 and a message, and OUT is not written
 //   --time          wall-clock milliseconds of construction / LCP (host pointers, i.e.
 //                   including the PCIe copies: the device-resident rate is bench.py's)
 //
@@ -63,6 +69,7 @@ static bool read_u32(const std::string& path, std::vector<uint32_t>* v)
     if (!raw.empty()) memcpy(v->data(), raw.data(), raw.size());
     return true;
 }
+static const char kLzMagic[8] = {'S', 'F', 'X', 'L', 'Z', '1', 0, 0};
 static double ms_since(std::chrono::steady_clock::time_point t0)
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -70,10 +77,10 @@ static double ms_since(std::chrono::steady_clock::time_point t0)
 
 int main(int argc, char** argv)
 {
-    std::string file, dump, load, match, bwt, unbwt, out, fm;
+    std::string file, dump, load, match, bwt, unbwt, out, fm, lz;
     long long min_len = 32, step = 256, occ_step = 0;
     std::vector<std::string> queries;
-    bool want_lcp = false, timing = false, earlier = false;
+    bool want_lcp = false, timing = false, earlier = false, unlz = false, min_len_given = false;
     long long repeats = -1;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -90,12 +97,15 @@ int main(int argc, char** argv)
         else if (a == "--match") match = need("--match");
         else if (a == "--min-len") {
             min_len = atoll(need("--min-len"));
+            min_len_given = true;
             if (min_len < 1 || min_len > 0xFFFFFFFFll) { fprintf(stderr, "--min-len needs a length of at least 1\n"); return 1; }
         }
         else if (a == "--bwt") bwt = need("--bwt");
         else if (a == "--unbwt") unbwt = need("--unbwt");
         else if (a == "--out") out = need("--out");
         else if (a == "--fm") fm = need("--fm");
+        else if (a == "--lz") lz = need("--lz");
+        else if (a == "--unlz") unlz = true;
         else if (a == "--occ-step") {
             occ_step = atoll(need("--occ-step"));
             if (occ_step < 32 || occ_step > 4096 || (occ_step & (occ_step - 1))) { fprintf(stderr, "--occ-step needs a power of two in 32 .. 4096\n"); return 1; }
@@ -112,7 +122,7 @@ int main(int argc, char** argv)
         else file = a;
     }
     if (file.empty()) {
-        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--bwt PREFIX [--step S]] [--time]\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
+        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]\n       suffix-array PREFIX.lz --unlz --out OUT\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
         return 1;
     }
     std::string text;
@@ -137,6 +147,35 @@ int main(int argc, char** argv)
             std::cout << "Restored: " << restored.size() << " bytes\n";
         } catch (const std::exception& ex) {
             fprintf(stderr, "suffix-array: %s and %s are no transform of any file (corrupted pair): %s\n", file.c_str(), unbwt.c_str(), ex.what());
+            return 2;
+        }
+        return 0;
+    }
+    if (unlz) {                                                         // FILE is a factorization: restore, build nothing
+        if (out.empty()) { fprintf(stderr, "--unlz needs --out OUT\n"); return 1; }
+        uint32_t hdr[2] = {0, 0};
+        if (text.size() >= 16) memcpy(hdr, text.data() + 8, 8);
+        const uint64_t n = hdr[0], z = hdr[1];
+        if (text.size() < 16 || memcmp(text.data(), kLzMagic, 8) != 0 || text.size() != 16 + 9 * z) {
+            fprintf(stderr, "suffix-array: %s is no factorization (truncated or corrupted)\n", file.c_str());
+            return 2;
+        }
+        std::vector<uint32_t> len((size_t)z), src((size_t)z);
+        if (z) {
+            memcpy(len.data(), text.data() + 16, 4 * z);
+            memcpy(src.data(), text.data() + 16 + 4 * z, 4 * z);
+        }
+        try {
+            const std::string restored = suffix::unlz(len, src, std::string_view(text.data() + 16 + 8 * z, (size_t)z));
+            if (restored.size() != n) throw std::runtime_error("the lengths do not sum to the header's n");
+            std::ofstream f(out, std::ios::binary);
+            if (!f || (!restored.empty() && !f.write(restored.data(), (std::streamsize)restored.size()))) {
+                fprintf(stderr, "cannot write %s\n", out.c_str());
+                return 1;
+            }
+            std::cout << "Restored: " << restored.size() << " bytes\n";
+        } catch (const std::exception& ex) {
+            fprintf(stderr, "suffix-array: %s is no factorization of any file (corrupted): %s\n", file.c_str(), ex.what());
             return 2;
         }
         return 0;
@@ -240,6 +279,27 @@ int main(int argc, char** argv)
             }
             std::cout << "BWT: primary " << (tr.samples.empty() ? 0u : tr.samples[0]) << ", " << tr.samples.size() << " samples (step " << step
                       << ")\n";
+        }
+        if (!lz.empty()) {
+            t0 = std::chrono::steady_clock::now();
+            const auto f = st.lz77(min_len_given ? (uint32_t)min_len : 1u);
+            if (timing) std::cout << "lz77 ms: " << ms_since(t0) << "\n";
+            uint64_t literals = 0;
+            uint32_t longest = 0;
+            for (size_t k = 0; k < f.size(); k++) {
+                literals += f.src[k] == 0xFFFFFFFFu;
+                if (f.len[k] > longest) longest = f.len[k];
+            }
+            const uint32_t hdr[2] = {(uint32_t)st.len(), (uint32_t)f.size()};
+            std::ofstream o(lz + ".lz", std::ios::binary);
+            if (!o || !o.write(kLzMagic, 8) || !o.write(reinterpret_cast<const char*>(hdr), 8)
+                || (f.size() && (!o.write(reinterpret_cast<const char*>(f.len.data()), (std::streamsize)(4 * f.size()))
+                                 || !o.write(reinterpret_cast<const char*>(f.src.data()), (std::streamsize)(4 * f.size()))
+                                 || !o.write(f.lit.data(), (std::streamsize)f.size())))) {
+                fprintf(stderr, "cannot write %s.lz\n", lz.c_str());
+                return 1;
+            }
+            std::cout << "LZ77: z " << f.size() << ", literals " << literals << ", longest " << longest << "\n";
         }
     } catch (const std::exception& ex) {
         fprintf(stderr, "suffix-array: %s\n", ex.what());
