@@ -491,6 +491,70 @@ int sfx_lz77_u32(const uint8_t* text, uint64_t n, const uint32_t* sa /* NULL: bu
                  uint64_t capacity, uint64_t* count_out);
 int sfx_unlz(const uint32_t* len, const uint32_t* src, const uint8_t* lit, uint64_t z, uint64_t n, uint8_t* text_out);
 
+/* ---- maximal exact matches of a query text against the table ------------------------------
+ * T = the indexed text of n bytes with table sa, Q = a query text of m bytes, L = min_len >= 1.
+ * A maximal exact match (MEM) is a triple (i, p, l) with l >= L and Q[i .. i+l) == T[p .. p+l) that can be extended
+ * in neither direction:
+ *   left    i == 0, or p == 0, or Q[i-1] != T[p-1]
+ *   right   i + l == m, or p + l == n, or Q[i+l] != T[p+l]
+ * For a collection (sfx_gindex) a match lies inside ONE document: the start of p's document plays the part of p == 0
+ * and its end the part of n (the truncated-suffix model of sfx_build_gsa_u32); p is a text position
+ * doc_starts[d] + offset.  With SFX_MEM_UNIQUE only those MEMs are kept whose l bytes occur exactly once in T (once
+ * among all truncated suffixes of a collection).
+ * Order: ascending by i, for equal i by the table rank of p -- the output is determined bit for bit by
+ * (T, sa, Q, L, flags), and the unique list is the full list filtered, in the same order.
+ * Two counts: P = the number of candidate pairs (i, r), r a rank whose suffix shares at least L bytes with Q[i..]
+ * = the sum of end - start over the positions whose capped (max_len = L) matching statistic reaches L; Z = the number
+ * of MEMs reported.  Work is proportional to P plus the bytes of the matches, not to Z: a shared stretch of M bytes
+ * is M - L + 1 pairs and one MEM, and Q = T = a^n has about n^2 / 2 pairs.  The caller therefore gives a pair_limit,
+ * the same duty as max_len on an uncapped sfx_match_stats_dev.  With P_k = P at min_len = k:
+ *   Z(L) = P_L - P_(L+1)                     (a pair is not left-maximal iff the pair one byte earlier is an (L+1)-pair)
+ *   the sum of (l - L + 1) over the MEMs = P_L   (every L-pair lies on exactly one MEM's diagonal)
+ *
+ * sfx_mems_dev / sfx_index_mems_dev / sfx_gindex_mems_dev: everything is queued on the caller's stream, which is
+ *   synchronised ONCE, at the end, to read (P, Z) back.  The calls keep no state in the index and allocate nothing:
+ *   any number of threads may call on one index at once, each with its own workspace.
+ *   *pairs_out = P always.  P <= pair_limit: *count_out = Z, the first min(Z, capacity) triples are written and
+ *   nothing past them; a caller that sees count > capacity calls again with more room.  P > pair_limit: SFX_OK,
+ *   no triple is written and *count_out = 0 -- the refusal is recognised by *pairs_out > pair_limit.
+ *   SFX_ERR_ARG: min_len == 0, pair_limit == 0, unknown flag bits, pairs_out / count_out NULL, an output array NULL
+ *   while capacity > 0, a NULL input of a non-empty call, a workspace off SFX_WORKSPACE_ALIGN.  m or n > u32::MAX is
+ *   SFX_ERR_TOO_LARGE, a workspace below sfx_mems_workspace_bytes(m, pair_limit) SFX_ERR_WORKSPACE.
+ *   m == 0, n == 0 or L > min(m, n): SFX_OK with P = Z = 0.
+ *   Workspace <= 24 m + pair_limit / 4 + 64 KiB bytes (a pair_limit above m * u32::MAX counts as that).
+ *   d_text and d_query may have any alignment, the u32 arrays need 4 bytes.  Outside the caller's buffers nothing is
+ *   written; outside Q, T, sa (da and doc_starts of a collection) and the workspace nothing is read.
+ *   sfx_mems_dev takes text and table as they are, like sfx_match_stats_dev: for any table whose entries are all < n
+ *   nothing is read or written out of bounds and every loop ends; what is reported for a table that is not the
+ *   text's suffix array is unspecified.  The index entries rely on the check made when the index was created;
+ *   sfx_index_mems_dev starts the search in the bucket directory, sfx_gindex_mems_dev uses the collection's search.
+ * sfx_index_mems / sfx_gindex_mems: the same with host buffers, staged through HBM.
+ * Not covered: matches unique in the query too (MUMmer's -mum), MEMs over the FM-index, approximate matches,
+ * chaining of seeds, the multi-GPU path. */
+enum { SFX_MEM_UNIQUE = 1 };
+uint64_t sfx_mems_workspace_bytes(uint64_t m, uint64_t pair_limit);
+int sfx_mems_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint8_t* d_query, uint64_t m,
+                 uint32_t min_len, uint32_t flags, uint64_t pair_limit,
+                 uint32_t* d_qpos, uint32_t* d_tpos, uint32_t* d_len, uint64_t capacity,
+                 uint64_t* pairs_out /* host */, uint64_t* count_out /* host */,
+                 void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_index_mems_dev(const sfx_index* ix, const uint8_t* d_query, uint64_t m,
+                       uint32_t min_len, uint32_t flags, uint64_t pair_limit,
+                       uint32_t* d_qpos, uint32_t* d_tpos, uint32_t* d_len, uint64_t capacity,
+                       uint64_t* pairs_out /* host */, uint64_t* count_out /* host */,
+                       void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_gindex_mems_dev(const sfx_gindex* gx, const uint8_t* d_query, uint64_t m,
+                        uint32_t min_len, uint32_t flags, uint64_t pair_limit,
+                        uint32_t* d_qpos, uint32_t* d_tpos, uint32_t* d_len, uint64_t capacity,
+                        uint64_t* pairs_out /* host */, uint64_t* count_out /* host */,
+                        void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_index_mems(const sfx_index* ix, const uint8_t* query, uint64_t m, uint32_t min_len, uint32_t flags,
+                   uint64_t pair_limit, uint32_t* qpos_out, uint32_t* tpos_out, uint32_t* len_out, uint64_t capacity,
+                   uint64_t* pairs_out, uint64_t* count_out);
+int sfx_gindex_mems(const sfx_gindex* gx, const uint8_t* query, uint64_t m, uint32_t min_len, uint32_t flags,
+                    uint64_t pair_limit, uint32_t* qpos_out, uint32_t* tpos_out, uint32_t* len_out, uint64_t capacity,
+                    uint64_t* pairs_out, uint64_t* count_out);
+
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the
  * text shard [shard_begin, shard_end).

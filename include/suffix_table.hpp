@@ -8,7 +8,7 @@
 //   new_ / new_naive (doc-hidden upstream, :93-100: the definition, sorted on the host -- the reference's own test oracle,
 //   tests/tests.rs:18-20; never a fallback of new_) / from_parts / into_parts / lcp_lens / table / text / len / is_empty /
 //   suffix / suffix_bytes / contains / positions / any_position,
-// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans, bwt / unbwt, lz77 / unlz and fm_index (class FmIndex
+// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans, bwt / unbwt, lz77 / unlz, mems and fm_index (class FmIndex
 // below: the same queries from the transform alone).  Errors that are panics
 // in the reference (assert! :380, assert_eq! :117) are std::runtime_error /
 // std::length_error here.  Text is indexed by BYTES (:379).
@@ -170,6 +170,38 @@ public:
     {
         if (min_len == 0) throw std::invalid_argument("shared_spans: min_len must be at least 1");
         return spans_of(match_stats(query, min_len).len, min_len);
+    }
+    // additive: the maximal exact matches of at least min_len bytes between a second text and this one (suffix_hip.h,
+    // sfx_index_mems): query[qpos .. qpos + len) == text[tpos .. tpos + len), extendable neither to the left nor to the
+    // right; ascending by qpos, then by the table rank of tpos.  unique: only matches whose bytes occur once in the text.
+    // pairs = the candidate pairs the call looked at; more than max_pairs of them throw std::runtime_error naming the
+    // count (a shared stretch of M bytes is M - min_len + 1 pairs; two copies of a^n about n^2 / 2).
+    struct Mems {
+        std::vector<uint32_t> qpos, tpos, len;
+        uint64_t pairs = 0;
+        size_t size() const { return len.size(); }
+    };
+    Mems mems(std::string_view query, uint32_t min_len, bool unique = false, uint64_t max_pairs = 1ull << 30) const
+    {
+        if (min_len == 0 || max_pairs == 0) throw std::invalid_argument("mems: min_len and max_pairs must be at least 1");
+        Mems r;
+        if (query.empty() || text_.empty()) return r;
+        uint64_t cap = query.size() < 1024 ? 1024 : query.size(), z = 0;
+        for (int round = 0; round < 2; round++) {                                    // the room is a guess: once more when there were more
+            r.qpos.resize((size_t)cap);
+            r.tpos.resize((size_t)cap);
+            r.len.resize((size_t)cap);
+            check(sfx_index_mems(index(), reinterpret_cast<const uint8_t*>(query.data()), query.size(), min_len, unique ? SFX_MEM_UNIQUE : 0u,
+                                 max_pairs, r.qpos.data(), r.tpos.data(), r.len.data(), cap, &r.pairs, &z), "mems");
+            if (r.pairs > max_pairs)
+                throw std::runtime_error("mems: " + std::to_string(r.pairs) + " candidate pairs exceed max_pairs = " + std::to_string(max_pairs));
+            if (z <= cap) break;
+            cap = z;
+        }
+        r.qpos.resize((size_t)z);
+        r.tpos.resize((size_t)z);
+        r.len.resize((size_t)z);
+        return r;
     }
     // the spans of a rep-shaped array (repeat_lens, match_stats().len) at min_len >= 1
     static std::vector<std::pair<uint32_t, uint32_t>> spans_of(const std::vector<uint32_t>& rep, uint32_t min_len)

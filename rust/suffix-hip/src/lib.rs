@@ -60,6 +60,14 @@ extern "C" {
     fn sfx_match_stats_dev(d_text: *const u8, n: u64, d_sa: *const u32, d_query: *const u8, m: u64, max_len: u32,
                            d_len: *mut u32, d_src: *mut u32, d_start: *mut u32, d_end: *mut u32,
                            stream: *mut c_void) -> c_int;
+    // maximal exact matches of a second text against the resident index (host buffers; the outputs may be null at capacity 0)
+    fn sfx_index_mems(ix: *const SfxIndex, query: *const u8, m: u64, min_len: u32, flags: u32, pair_limit: u64,
+                      qpos_out: *mut u32, tpos_out: *mut u32, len_out: *mut u32, capacity: u64, pairs_out: *mut u64,
+                      count_out: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_index_mems_dev(ix: *const SfxIndex, d_query: *const u8, m: u64, min_len: u32, flags: u32, pair_limit: u64,
+                          d_qpos: *mut u32, d_tpos: *mut u32, d_len: *mut u32, capacity: u64, pairs_out: *mut u64,
+                          count_out: *mut u64, d_workspace: *mut c_void, workspace_bytes: u64, stream: *mut c_void) -> c_int;
     // Burrows-Wheeler transform with sampled ranks and its inverse (host buffers; sa may be null: the table is built)
     fn sfx_bwt_sample_count(n: u64, sample_step: u32) -> u64;
     fn sfx_bwt_u32(text: *const u8, n: u64, sa: *const u32, sample_step: u32, bwt_out: *mut u8,
@@ -91,6 +99,14 @@ extern "C" {
     fn sfx_lz77_u32(text: *const u8, n: u64, sa: *const u32, lcp: *const u32, min_len: u32, begin_out: *mut u32,
                     len_out: *mut u32, src_out: *mut u32, lit_out: *mut u8, capacity: u64, count_out: *mut u64) -> c_int;
     fn sfx_unlz(len: *const u32, src: *const u32, lit: *const u8, z: u64, n: u64, text_out: *mut u8) -> c_int;
+    // maximal exact matches of a query text (sfx_mems_dev: text and table in device memory; DeviceIndex::mems below goes
+    // through the same kernels with host buffers)
+    #[allow(dead_code)]
+    fn sfx_mems_workspace_bytes(m: u64, pair_limit: u64) -> u64;
+    #[allow(dead_code)]
+    fn sfx_mems_dev(d_text: *const u8, n: u64, d_sa: *const u32, d_query: *const u8, m: u64, min_len: u32, flags: u32,
+                    pair_limit: u64, d_qpos: *mut u32, d_tpos: *mut u32, d_len: *mut u32, capacity: u64, pairs_out: *mut u64,
+                    count_out: *mut u64, d_workspace: *mut c_void, workspace_bytes: u64, stream: *mut c_void) -> c_int;
     // FM-index over that pair (sfx_fm_*): the size bound; the handle functions take `sfx_fm*`, a type the signature check
     // of this block (tests/test_rust_crate.py) has no mapping for yet, so they are not bound here
     fn sfx_fm_bytes(n: u64, sample_step: u32, occ_step: u32) -> u64;
@@ -320,6 +336,46 @@ impl DeviceIndex {
         }, "sfx_index_match_stats");
         (len, src)
     }
+    /// Additive API: the maximal exact matches of at least `min_len` (>= 1) bytes between `query` and the indexed text:
+    /// `query[qpos..qpos + len] == text[tpos..tpos + len]`, extendable neither to the left nor to the right, ascending by
+    /// `qpos` and then by the table rank of `tpos`.  `unique`: only matches whose bytes occur once in the text.
+    /// `Err(pairs)`: the call would look at `pairs` > `max_pairs` candidate pairs (a shared stretch of M bytes is
+    /// M - min_len + 1 of them) and wrote nothing; raise `min_len` or `max_pairs`.
+    pub fn mems(&self, query: &[u8], min_len: u32, unique: bool, max_pairs: u64) -> Result<Mems, u64> {
+        assert!(min_len >= 1 && max_pairs >= 1 && query.len() <= u32::MAX as usize);
+        let mut cap = query.len().max(1024);
+        let (mut pairs, mut count) = (0u64, 0u64);
+        let mut r = Mems { qpos: Vec::new(), tpos: Vec::new(), len: Vec::new(), pairs: 0 };
+        for _ in 0..2 {                                        // the room is a guess: once more when there were more
+            r.qpos.resize(cap, 0);
+            r.tpos.resize(cap, 0);
+            r.len.resize(cap, 0);
+            check(unsafe {
+                sfx_index_mems(self.0, query.as_ptr(), query.len() as u64, min_len, if unique { 1 } else { 0 }, max_pairs,
+                               r.qpos.as_mut_ptr(), r.tpos.as_mut_ptr(), r.len.as_mut_ptr(), cap as u64, &mut pairs, &mut count)
+            }, "sfx_index_mems");
+            if pairs > max_pairs {
+                return Err(pairs);
+            }
+            if count as usize <= cap {
+                break;
+            }
+            cap = count as usize;
+        }
+        r.qpos.truncate(count as usize);
+        r.tpos.truncate(count as usize);
+        r.len.truncate(count as usize);
+        r.pairs = pairs;
+        Ok(r)
+    }
+}
+/// The maximal exact matches of a query text (`DeviceIndex::mems`): one entry per match, and the number of candidate
+/// pairs the call looked at.
+pub struct Mems {
+    pub qpos: Vec<u32>,
+    pub tpos: Vec<u32>,
+    pub len: Vec<u32>,
+    pub pairs: u64,
 }
 impl DeviceIndex {
     pub fn len(&self) -> usize {

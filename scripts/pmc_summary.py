@@ -84,6 +84,7 @@ NAMES = [
     ("k_lz_exit", "lz_exit"), ("k_lz_hop", "lz_hop"), ("k_lz_walk_groups", "lz_walk_groups"), ("k_lz_walk_tiles", "lz_walk_tiles"),
     ("k_lz_count", "lz_count"), ("k_lz_emit", "lz_emit"), ("k_lz_unscan_check", "unlz_scan"), ("k_lz_unorigin", "unlz_origin"),
     ("k_lz_unjump", "unlz_jump"), ("k_lz_unfill", "unlz_fill"),
+    ("k_mem_cand", "mem_cand"), ("k_mem_count", "mem_count"), ("k_mem_emit", "mem_emit"),
     ("k_fm_count", "fm_count"), ("k_fm_lookup", "fm_lookup"), ("k_fm_", "fm_build"),
     ("k_ms_search_dir", "ms_search_dir"), ("k_ms_search", "ms_search"), ("k_ms_gsa_search", "ms_gsa_search"),
     # -- not part of a build's profile: the polled read-back and the memory-system probes

@@ -121,6 +121,15 @@ ABI = [
     ("sfx_lz_decode_dev", _int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp]),
     ("sfx_lz77_u32", _int, [_vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64)]),
     ("sfx_unlz", _int, [_vp, _vp, _vp, _u64, _u64, _vp]),
+    ("sfx_mems_workspace_bytes", _u64, [_u64, _u64]),
+    ("sfx_mems_dev", _int, [_vp, _u64, _vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                            _vp, _u64, _vp]),
+    ("sfx_index_mems_dev", _int, [_vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                  _vp, _u64, _vp]),
+    ("sfx_gindex_mems_dev", _int, [_vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                   _vp, _u64, _vp]),
+    ("sfx_index_mems", _int, [_vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    ("sfx_gindex_mems", _int, [_vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),

@@ -11,6 +11,7 @@
 #include "sfx_host.hpp"
 #include "sfx_fm.hip"   // the FM-index: kernels and host side, one translation unit with its entry points below
 #include "sfx_lz.hip"   // LZ77 factorization and its decoder, likewise
+#include "sfx_mem.hip"  // maximal exact matches, likewise
 
 namespace sfx {
 
@@ -951,6 +952,92 @@ int sfx_unlz(const uint32_t* len, const uint32_t* src, const uint8_t* lit, uint6
     SFX_HIP(hipMemcpyAsync(text_out, dt.p, n, hipMemcpyDeviceToHost, st));
     SFX_HIP(hipStreamSynchronize(st));
     return SFX_OK;
+}
+
+// ---- maximal exact matches of a query text (include/suffix_hip.h) ---------------------------------------------
+uint64_t sfx_mems_workspace_bytes(uint64_t m, uint64_t pair_limit) { return mems_workspace_bytes(m, pair_limit); }
+#define SFX_MEM_TAIL_PARAMS                                                                                                     \
+    uint32_t min_len, uint32_t flags, uint64_t pair_limit, uint32_t *d_qpos, uint32_t *d_tpos, uint32_t *d_len, uint64_t capacity, \
+        uint64_t *pairs_out, uint64_t *count_out, void *d_workspace, uint64_t workspace_bytes, void *stream
+#define SFX_MEM_TAIL_ARGS \
+    min_len, flags, pair_limit, d_qpos, d_tpos, d_len, capacity, pairs_out, count_out, d_workspace, workspace_bytes, (hipStream_t)stream
+int sfx_mems_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint8_t* d_query, uint64_t m, SFX_MEM_TAIL_PARAMS)
+{
+    SFX_NEED_U32(d_sa, d_qpos, d_tpos, d_len);
+    SFX_NEED_WS(d_workspace, workspace_bytes, mems_workspace_bytes(m, pair_limit));
+    const MemSource s = {d_text, n, d_sa, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0};
+    return mems_dev(s, d_query, m, SFX_MEM_TAIL_ARGS);
+}
+int sfx_index_mems_dev(const sfx_index* ix, const uint8_t* d_query, uint64_t m, SFX_MEM_TAIL_PARAMS)
+{
+    SFX_NEED_U32(d_qpos, d_tpos, d_len);
+    if (!ix) return SFX_ERR_ARG;
+    SFX_NEED_WS(d_workspace, workspace_bytes, mems_workspace_bytes(m, pair_limit));
+    // (a directory that was never built, or a cap below its k symbols, takes the whole-table search: match_stats_dir_dev)
+    const MemSource s = {ix->d_text, ix->n, ix->d_sa, ix->d_dir, ix->d_lut, ix->bits, ix->k, ix->dbits, nullptr, nullptr, 0};
+    return mems_dev(s, d_query, m, SFX_MEM_TAIL_ARGS);
+}
+int sfx_gindex_mems_dev(const sfx_gindex* gx, const uint8_t* d_query, uint64_t m, SFX_MEM_TAIL_PARAMS)
+{
+    SFX_NEED_U32(d_qpos, d_tpos, d_len);
+    if (!gx) return SFX_ERR_ARG;
+    SFX_NEED_WS(d_workspace, workspace_bytes, mems_workspace_bytes(m, pair_limit));
+    if (gx->n && (!gx->d_starts || !gx->d_da || gx->ndocs == 0)) return SFX_ERR_ARG;
+    const MemSource s = {gx->d_text, gx->n, gx->d_sa, nullptr, nullptr, 0, 0, 0, gx->d_starts, gx->d_da, gx->ndocs};
+    return mems_dev(s, d_query, m, SFX_MEM_TAIL_ARGS);
+}
+#undef SFX_MEM_TAIL_PARAMS
+#undef SFX_MEM_TAIL_ARGS
+// host buffers staged through HBM on the calling thread's stream; exactly one of ix / gx is given
+static int mems_host(const sfx_index* ix, const sfx_gindex* gx, const uint8_t* query, uint64_t m, uint32_t min_len, uint32_t flags,
+                     uint64_t pair_limit, uint32_t* qpos_out, uint32_t* tpos_out, uint32_t* len_out, uint64_t capacity,
+                     uint64_t* pairs_out, uint64_t* count_out)
+{
+    if ((!ix && !gx) || !pairs_out || !count_out || min_len == 0 || pair_limit == 0 || (flags & ~(uint32_t)SFX_MEM_UNIQUE)) return SFX_ERR_ARG;
+    *pairs_out = *count_out = 0;
+    const uint64_t n = ix ? ix->n : gx->n;
+    if (m > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (capacity && (!qpos_out || !tpos_out || !len_out)) return SFX_ERR_ARG;
+    if (m == 0 || n == 0 || min_len > dmin(m, n)) return SFX_OK;
+    if (!query) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    pair_limit = dmin(pair_limit, m * n);                                // (P cannot be larger: the workspace need not be either)
+    capacity = dmin(capacity, pair_limit);
+    const uint64_t wsb = mems_workspace_bytes(m, pair_limit), cb = capacity * sizeof(uint32_t);
+    DevBuf dq, di, dp, dl, dw;
+    SFX_TRY(dq.alloc(m));
+    SFX_TRY(di.alloc(cb));
+    SFX_TRY(dp.alloc(cb));
+    SFX_TRY(dl.alloc(cb));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(dq.p, query, m, hipMemcpyHostToDevice, st));
+    uint32_t *oi = capacity ? (uint32_t*)di.p : nullptr, *op = capacity ? (uint32_t*)dp.p : nullptr, *ol = capacity ? (uint32_t*)dl.p : nullptr;
+    if (ix)
+        SFX_TRY(sfx_index_mems_dev(ix, (const uint8_t*)dq.p, m, min_len, flags, pair_limit, oi, op, ol, capacity, pairs_out, count_out, dw.p,
+                                   wsb, st));
+    else
+        SFX_TRY(sfx_gindex_mems_dev(gx, (const uint8_t*)dq.p, m, min_len, flags, pair_limit, oi, op, ol, capacity, pairs_out, count_out, dw.p,
+                                    wsb, st));
+    const uint64_t k = dmin<uint64_t>(*count_out, capacity);
+    if (k) {
+        SFX_HIP(hipMemcpyAsync(qpos_out, di.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(tpos_out, dp.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(len_out, dl.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+int sfx_index_mems(const sfx_index* ix, const uint8_t* query, uint64_t m, uint32_t min_len, uint32_t flags, uint64_t pair_limit,
+                   uint32_t* qpos_out, uint32_t* tpos_out, uint32_t* len_out, uint64_t capacity, uint64_t* pairs_out, uint64_t* count_out)
+{
+    return mems_host(ix, nullptr, query, m, min_len, flags, pair_limit, qpos_out, tpos_out, len_out, capacity, pairs_out, count_out);
+}
+int sfx_gindex_mems(const sfx_gindex* gx, const uint8_t* query, uint64_t m, uint32_t min_len, uint32_t flags, uint64_t pair_limit,
+                    uint32_t* qpos_out, uint32_t* tpos_out, uint32_t* len_out, uint64_t capacity, uint64_t* pairs_out, uint64_t* count_out)
+{
+    return mems_host(nullptr, gx, query, m, min_len, flags, pair_limit, qpos_out, tpos_out, len_out, capacity, pairs_out, count_out);
 }
 
 // ---- suffix-tree topology, generalized suffix array -------------------------------------------

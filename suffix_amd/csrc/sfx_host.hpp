@@ -484,6 +484,12 @@ int lz_parse_dev(const uint32_t* d_rep, const uint32_t* d_src, const uint8_t* d_
 uint64_t lz_decode_workspace_bytes(uint64_t n, uint64_t z);
 int lz_decode_dev(const uint32_t* d_len, const uint32_t* d_psrc, const uint8_t* d_lit, uint64_t z, uint64_t n, uint8_t* d_out, void* ws,
                   uint64_t ws_bytes, hipStream_t st);
+// maximal exact matches of a query text (sfx_mem.hip); synchronises the stream once, for (P, Z)
+struct MemSource;
+uint64_t mems_workspace_bytes(uint64_t m, uint64_t pair_limit);
+int mems_dev(const MemSource& s, const uint8_t* d_q, uint64_t m, uint32_t min_len, uint32_t flags, uint64_t pair_limit, uint32_t* d_qpos,
+             uint32_t* d_tpos, uint32_t* d_len, uint64_t capacity, uint64_t* pairs_out, uint64_t* count_out, void* ws, uint64_t ws_bytes,
+             hipStream_t st);
 // bucket directory of the resident index (sfx_query.hip)
 int dir_shape(uint64_t n, int bits, int* k_out, int* dbits_out, uint64_t* entries_out);
 uint64_t dir_scratch_words(uint64_t entries);

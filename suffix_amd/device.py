@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from ._lib import REP_SCOPES, FmInfo, default_engine
+from ._lib import REP_SCOPES, FmInfo, SuffixHipError, default_engine
 
 
 def _on(t):
@@ -352,6 +352,13 @@ class DeviceIndex:
                                                                     _p(end), _stream_ptr(self._text)), "sfx_index_match_stats_dev")
         return _ms_result(ln, src, start, end, want_src, want_interval)
 
+    def mems(self, query, min_len, unique=False, max_pairs=1 << 30, capacity=None, workspace=None):
+        """As the module's mems, against the index's text and (checked) table, searching through its directory
+        (sfx_index_mems_dev).  Keeps no state in the index: threads may call at once."""
+        call = lambda *tail: self._eng.lib.sfx_index_mems_dev(self._h, *tail)
+        return _mems(self._eng, call, "sfx_index_mems_dev", self._text.numel(), query, self._text, min_len, unique, max_pairs,
+                     capacity, workspace)
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
@@ -629,6 +636,63 @@ def lz_decode(len, src, lit, n=None, out=None, workspace=None, engine=None):
     return out
 
 
+def mems_workspace(m, max_pairs, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_mems_workspace_bytes(int(m), int(max_pairs))), dtype=torch.uint8, device=device)
+
+
+def _mems(eng, call, name, n, query, anchor, min_len, unique, max_pairs, capacity, workspace):
+    """The checks, buffers and the repeated call every mems entry shares; call(tail...) -> status."""
+    if query.dtype != torch.uint8 or query.dim() != 1 or not query.is_contiguous():
+        raise TypeError("query must be a contiguous 1-D uint8 tensor")
+    dev = anchor.device
+    if query.device != dev:
+        raise ValueError(f"query must be on the text's device ({dev})")
+    min_len, max_pairs = int(min_len), int(max_pairs)
+    if min_len < 1 or min_len > 0xFFFFFFFF:
+        raise ValueError("min_len must be in 1 .. 2^32 - 1")
+    if max_pairs < 1:
+        raise ValueError("max_pairs must be at least 1")
+    m = query.numel()
+    max_pairs = min(max_pairs, max(m * n, 1))                # (there are no more pairs: keeps the workspace small)
+    if anchor.is_cuda:
+        eng.require_device()
+    if workspace is None:
+        workspace = mems_workspace(m, max_pairs, dev, eng)
+    cap = min(max(m, 1024), max_pairs) if capacity is None else int(capacity)
+    pairs, count = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    for _ in range(2):
+        out = [torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3)]
+        with _on(anchor):
+            eng.check(call(_p(query), m, min_len, 1 if unique else 0, max_pairs, _p(out[0]), _p(out[1]), _p(out[2]), cap,
+                           ctypes.byref(pairs), ctypes.byref(count), _p(workspace), workspace.numel(), _stream_ptr(anchor)), name)
+        if pairs.value > max_pairs:
+            raise SuffixHipError(f"{name}: {pairs.value} candidate pairs exceed max_pairs = {max_pairs}; raise min_len or max_pairs")
+        if count.value <= cap or capacity is not None:
+            break
+        cap = int(count.value)
+    z = min(int(count.value), cap)
+    return out[0][:z].clone(), out[1][:z].clone(), out[2][:z].clone(), int(pairs.value)
+
+
+def mems(text, sa, query, min_len, unique=False, max_pairs=1 << 30, capacity=None, workspace=None, engine=None):
+    """The maximal exact matches of at least min_len bytes between the uint8 tensor `query` and (text, sa), all on one
+    device: -> (qpos, tpos, len, pairs), three uint32 tensors in int32 storage cut to the matches -- ascending by qpos,
+    then by the table rank of tpos -- and the number of candidate pairs looked at.  unique: only matches whose bytes
+    occur once in the text.  More than max_pairs candidate pairs raise SuffixHipError naming the count.  The room is
+    guessed (one match per query byte) and the call repeated once when there were more; with `capacity` it runs once
+    and returns the first `capacity` matches.  Runs on the current stream and synchronises it once per call; the table
+    is not checked (sfx_mems_dev)."""
+    eng = engine or default_engine()
+    _check_u8(text)
+    _check_u32(sa, "sa", text.numel())
+    if sa.device != text.device:
+        raise ValueError(f"sa must be on the text's device ({text.device})")
+    n = text.numel()
+    call = lambda *tail: eng.lib.sfx_mems_dev(_p(text), n, _p(sa), *tail)
+    return _mems(eng, call, "sfx_mems_dev", n, query, text, min_len, unique, max_pairs, capacity, workspace)
+
+
 class GeneralizedDeviceIndex:
     """Resident generalized index over device tensors (text, doc_starts, GSA, DA) -- borrowed, keep them alive;
     `query` = per query (start, end, found, any, ndocs): matches inside one document only, ndocs = the number of
@@ -673,6 +737,13 @@ class GeneralizedDeviceIndex:
             self._eng.check(self._eng.lib.sfx_gindex_match_stats_dev(self._h, _p(query), m, max_len, _p(ln), _p(src), _p(start),
                                                                      _p(end), _stream_ptr(self._text)), "sfx_gindex_match_stats_dev")
         return _ms_result(ln, src, start, end, want_src, want_interval)
+
+    def mems(self, query, min_len, unique=False, max_pairs=1 << 30, capacity=None, workspace=None):
+        """As the module's mems, against the collection: a match lies inside one document, tpos is a text position
+        (sfx_gindex_mems_dev)."""
+        call = lambda *tail: self._eng.lib.sfx_gindex_mems_dev(self._h, *tail)
+        return _mems(self._eng, call, "sfx_gindex_mems_dev", self._text.numel(), query, self._text, min_len, unique, max_pairs,
+                     capacity, workspace)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

@@ -14,6 +14,7 @@ no match spans two documents.
     repeated_spans(min_len, ...)  [(document, begin_offset, end_offset)] of the bytes inside such repeats
     match_stats(query, max_len)   longest match of every suffix of a NEW text inside one document of the collection
     shared_spans(query, min_len)  [(begin, end)] of the query bytes inside such matches of at least min_len bytes
+    mems(query, min_len, unique)  the maximal exact matches of a NEW text, each inside one document
 
 Construction and queries run on the GPU through the C ABI (sfx_build_gsa_u32, sfx_gindex_*); there is no CPU
 path except `new_naive`, the definition itself.
@@ -23,7 +24,7 @@ import ctypes
 import numpy as np
 
 from ._lib import default_engine
-from .table import _as_bytes, _match_stats, _ptr, _repeat_lens, _repeat_spans, _shared_spans
+from .table import Mems, _as_bytes, _match_stats, _mems, _ptr, _repeat_lens, _repeat_spans, _shared_spans
 
 _NONE = 0xFFFFFFFF
 
@@ -236,3 +237,14 @@ class GeneralizedSuffixTable:
         """[(begin, end)] in query coordinates, ascending: the query bytes inside a stretch of at least min_len bytes
         that occurs within one document."""
         return _shared_spans(self._eng, self.match_stats, query, min_len)
+
+    def mems(self, query, min_len, unique=False, max_pairs=1 << 30):
+        """As SuffixTable.mems, against the collection: a match lies inside ONE document and ends at its ends; tpos is
+        a text position doc_starts[doc] + offset, and the result also has the arrays doc and offset.  unique: the
+        bytes occur once among all documents."""
+        qpos, tpos, ln, pairs = _mems(self._eng, self._eng.lib.sfx_gindex_mems, "sfx_gindex_mems", self._ensure_index, self.len(),
+                                      query, min_len, unique, max_pairs)
+        # the document of a match: the last one that starts at or before tpos and is not empty (a match has bytes)
+        d = np.searchsorted(self._starts, tpos.astype(np.uint64), side="right").astype(np.int64) - 1
+        off = (tpos.astype(np.int64) - self._starts[d].astype(np.int64)).astype(np.uint32) if tpos.size else tpos.copy()
+        return Mems(qpos, tpos, ln, pairs, doc=d.astype(np.uint32), offset=off)

@@ -3,7 +3,7 @@
 // over the MI355X engine's C++ host mirror (include/suffix_table.hpp -> libsuffix_hip.so),
 // extended into the large-file driver SURVEY.md 8(f) asks for:
 //
-//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]
+//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]
 //
 //   --dump PREFIX   write PREFIX.sa (and PREFIX.lcp with --lcp) as raw little-endian u32
 //                   arrays -- the on-disk form SuffixTable::from_parts (:111-119) reloads
@@ -16,6 +16,12 @@
 //                   one "begin end src" line per maximal run of FILE2's bytes inside a stretch of at least L bytes
 //                   (--min-len L, default 32) that also occurs in FILE; src = a position in FILE of the match that
 //                   starts at `begin`
+//   --match FILE2 --mems L [--unique] [--max-pairs P]
+//                   the maximal exact matches of at least L bytes between FILE2 and FILE instead of the spans: "MEMs with
+//                   FILE2 (>= L bytes): Z matches, P pairs", then one "qpos tpos len" line per match -- FILE2[qpos .. qpos+len)
+//                   == FILE[tpos .. tpos+len), extendable in neither direction -- ascending by qpos, then by the table rank
+//                   of tpos; --unique keeps the matches whose bytes occur once in FILE; more than P candidate pairs
+//                   (default 2^30) end with status 2 and a message naming the count
 //   --bwt PREFIX    write the Burrows-Wheeler transform: PREFIX.bwt (n raw bytes) and PREFIX.bwi (little-endian u32: the
 //                   sample step S, then the sampled rows; --step S, 0 or a power of two, default 256)
 //   suffix-array PREFIX.bwt --unbwt PREFIX.bwi --out OUT
@@ -78,9 +84,9 @@ static double ms_since(std::chrono::steady_clock::time_point t0)
 int main(int argc, char** argv)
 {
     std::string file, dump, load, match, bwt, unbwt, out, fm, lz;
-    long long min_len = 32, step = 256, occ_step = 0;
+    long long min_len = 32, step = 256, occ_step = 0, mems = -1, max_pairs = 1ll << 30;
     std::vector<std::string> queries;
-    bool want_lcp = false, timing = false, earlier = false, unlz = false, min_len_given = false;
+    bool want_lcp = false, timing = false, earlier = false, unlz = false, min_len_given = false, unique = false, max_pairs_given = false;
     long long repeats = -1;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -99,6 +105,16 @@ int main(int argc, char** argv)
             min_len = atoll(need("--min-len"));
             min_len_given = true;
             if (min_len < 1 || min_len > 0xFFFFFFFFll) { fprintf(stderr, "--min-len needs a length of at least 1\n"); return 1; }
+        }
+        else if (a == "--mems") {
+            mems = atoll(need("--mems"));
+            if (mems < 1 || mems > 0xFFFFFFFFll) { fprintf(stderr, "--mems needs a length of at least 1\n"); return 1; }
+        }
+        else if (a == "--unique") unique = true;
+        else if (a == "--max-pairs") {
+            max_pairs = atoll(need("--max-pairs"));
+            max_pairs_given = true;
+            if (max_pairs < 1) { fprintf(stderr, "--max-pairs needs a count of at least 1\n"); return 1; }
         }
         else if (a == "--bwt") bwt = need("--bwt");
         else if (a == "--unbwt") unbwt = need("--unbwt");
@@ -121,8 +137,11 @@ int main(int argc, char** argv)
         else if (!a.empty() && a[0] == '-') { fprintf(stderr, "unknown option %s\n", a.c_str()); return 1; }
         else file = a;
     }
+    if (mems > 0 && match.empty()) { fprintf(stderr, "--mems needs --match FILE2\n"); return 1; }
+    if (mems > 0 && min_len_given && lz.empty()) { fprintf(stderr, "--mems L takes its length itself: --min-len belongs to the span report of --match alone\n"); return 1; }
+    if (mems < 0 && (unique || max_pairs_given)) { fprintf(stderr, "--unique and --max-pairs need --mems L\n"); return 1; }
     if (file.empty()) {
-        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]\n       suffix-array PREFIX.lz --unlz --out OUT\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
+        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]\n       suffix-array PREFIX.lz --unlz --out OUT\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
         return 1;
     }
     std::string text;
@@ -256,7 +275,14 @@ int main(int argc, char** argv)
             if (timing) std::cout << "repeats ms: " << ms_since(t0) << "\n";
             for (const auto& be : spans) std::cout << be.first << " " << be.second << "\n";
         }
-        if (!match.empty()) {
+        if (!match.empty() && mems > 0) {
+            t0 = std::chrono::steady_clock::now();
+            const auto r = st.mems(other, (uint32_t)mems, unique, (uint64_t)max_pairs);
+            if (timing) std::cout << "mems ms: " << ms_since(t0) << "\n";
+            std::cout << "MEMs with " << match << " (>= " << mems << " bytes" << (unique ? ", unique" : "") << "): " << r.size() << " matches, "
+                      << r.pairs << " pairs\n";
+            for (size_t k = 0; k < r.size(); k++) std::cout << r.qpos[k] << " " << r.tpos[k] << " " << r.len[k] << "\n";
+        } else if (!match.empty()) {
             t0 = std::chrono::steady_clock::now();
             const auto ms = st.match_stats(other, (uint32_t)min_len);           // a span report at L needs no more than max_len = L
             const auto spans = suffix::SuffixTable::spans_of(ms.len, (uint32_t)min_len);
