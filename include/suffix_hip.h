@@ -555,6 +555,70 @@ int sfx_gindex_mems(const sfx_gindex* gx, const uint8_t* query, uint64_t m, uint
                     uint64_t pair_limit, uint32_t* qpos_out, uint32_t* tpos_out, uint32_t* len_out, uint64_t capacity,
                     uint64_t* pairs_out, uint64_t* count_out);
 
+/* ---- LCE index: inverse table, LCP range minima, k-mismatch extension -------- */
+/* How far do the suffixes at two positions of the indexed text agree?  T has n bytes, with table sa and lcp as
+ * sfx_build_sa_lcp_u32* write them; a collection uses the sa / in-document lcp of sfx_build_gsa_u32* plus doc_starts.
+ * end(p) = n for a plain table, the end of p's document for a collection (the truncated-suffix model).
+ *
+ *   inverse table    isa[sa[r]] = r for r in [0, n).
+ *   range_min(lo,hi) the minimum of lcp[lo .. hi) for 0 <= lo < hi <= n; UINT32_MAX for an empty range (lo >= hi) or
+ *                    hi > n.  lcp[0] is taken as stored.
+ *   LCE(i, j)        for i, j in [0, n): the largest l with T[i..i+l) = T[j..j+l), i + l <= end(i), j + l <= end(j)
+ *                    = min(range_min(lo + 1, hi + 1), end(i) - i, end(j) - j), lo < hi the ranks of i and j.
+ *                    i == j: end(i) - i.  A position equal to n gives 0, a position above n UINT32_MAX.
+ *   LCE_k(i, j)      max_mismatches = k: the largest l within the same bounds such that T[i..i+l) and T[j..j+l) differ
+ *                    in at most k places: l = LCE(i, j); while mismatches remain and both i + l and j + l are below
+ *                    their ends, one mismatch is counted and stepped over (l += 1) and LCE(i + l, j + l) is added --
+ *                    at most k + 1 rounds.  k is the same for the whole batch.  i == j gives end(i) - i for every k.
+ *   The results are determined bit for bit by (T, sa, lcp, doc_starts, i, j, k).
+ *
+ * Structure: isa (4n bytes) and a 32-ary min-tree over lcp whose level 0 is the LCP array itself; every level above
+ * starts on a 128-byte boundary, so a node is one line, and a range touches at most two lines per level.  The levels
+ * above 0 take 4n/31 bytes plus padding: sfx_lce_bytes(n) <= 4n + n/7 + 64 KiB bounds what a handle from
+ * sfx_lce_create_dev holds; the host route adds 4n for its copy of lcp (and 8 ndocs for doc_starts).  The index needs
+ * neither T nor sa after creation.
+ *
+ * sfx_lce_create_dev borrows d_lcp and d_doc_starts (keep them alive until sfx_lce_destroy, like the arrays of
+ * sfx_index_create_dev); d_sa is free again when it returns.  sfx_lce_create copies.  n == 0 gives a valid empty
+ * handle, n > u32::MAX SFX_ERR_TOO_LARGE.  d_doc_starts == NULL (then ndocs == 0): a plain table.  The alignment rules
+ * are those of the first comment: a 4-byte-aligned lcp works, 16-byte alignment lets level 0 be read 16 bytes at a time.
+ *
+ * What creation proves: every sa entry is < n and every one of the n slots of isa was written, hence sa is a
+ * permutation of [0, n); doc_starts starts with 0, never decreases and stays <= n.  Otherwise SFX_ERR_ARG, with
+ * nothing read or written out of bounds on any input.  What it does not prove: that lcp belongs to sa.  No address
+ * depends on a value read from lcp and every result is clamped to min(end(i) - i, end(j) - j), so with a foreign lcp
+ * the values are unspecified and nothing else.  Creation synchronises the stream once (the two flags);
+ * sfx_inverse_table_dev likewise.  Creation allocates the handle's memory, and takes its scratch -- 256 bytes, from
+ * 2^27 entries on 16 n bytes + the radix scratch of the partitioned scatter -- from the buffer pool of the host-pointer
+ * entry points: a loop of creates at one size allocates it once, sfx_release_cached_buffers() returns it.  The query calls queue on the caller's stream, take no workspace and do not
+ * synchronise; a handle may be queried from several threads at once.
+ *
+ * sfx_inverse_table_dev: isa alone, with the same proof (SFX_ERR_ARG for a table that is no permutation); a workspace
+ * below sfx_inverse_table_workspace_bytes(n) is SFX_ERR_WORKSPACE.  sfx_lce_ranks*: rank[q] = isa[pos[q]], UINT32_MAX
+ * for pos >= n.  sfx_lce_u32: create, query, destroy over host buffers.
+ *
+ * Not covered: the argmin of a range, suffix-tree LCA on top of it, LCE between a query text and the index (that is
+ * sfx_match_stats), positions >= 2^32, the multi-GPU path. */
+uint64_t sfx_inverse_table_workspace_bytes(uint64_t n);
+int sfx_inverse_table_dev(const uint32_t* d_sa, uint64_t n, uint32_t* d_isa, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_inverse_table_u32(const uint32_t* sa, uint64_t n, uint32_t* isa_out);
+
+typedef struct sfx_lce sfx_lce;
+uint64_t sfx_lce_bytes(uint64_t n);
+int sfx_lce_create_dev(const uint32_t* d_sa, const uint32_t* d_lcp, uint64_t n, const uint64_t* d_doc_starts /* NULL: plain */,
+                       uint64_t ndocs, void* stream, sfx_lce** out);
+int sfx_lce_create(const uint32_t* sa, const uint32_t* lcp, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs, sfx_lce** out);
+void sfx_lce_destroy(sfx_lce* lx);
+int sfx_lce_query_dev(const sfx_lce* lx, const uint32_t* d_a, const uint32_t* d_b, uint64_t nq, uint32_t max_mismatches,
+                      uint32_t* d_len, void* stream);
+int sfx_lce_query(const sfx_lce* lx, const uint32_t* a, const uint32_t* b, uint64_t nq, uint32_t max_mismatches, uint32_t* len_out);
+int sfx_lce_range_min_dev(const sfx_lce* lx, const uint32_t* d_lo, const uint32_t* d_hi, uint64_t nq, uint32_t* d_min, void* stream);
+int sfx_lce_range_min(const sfx_lce* lx, const uint32_t* lo, const uint32_t* hi, uint64_t nq, uint32_t* min_out);
+int sfx_lce_ranks_dev(const sfx_lce* lx, const uint32_t* d_pos, uint64_t nq, uint32_t* d_rank, void* stream);
+int sfx_lce_ranks(const sfx_lce* lx, const uint32_t* pos, uint64_t nq, uint32_t* rank_out);
+int sfx_lce_u32(const uint32_t* sa, const uint32_t* lcp, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs,
+                const uint32_t* a, const uint32_t* b, uint64_t nq, uint32_t max_mismatches, uint32_t* len_out);
+
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the
  * text shard [shard_begin, shard_end).

@@ -8,8 +8,8 @@
 //   new_ / new_naive (doc-hidden upstream, :93-100: the definition, sorted on the host -- the reference's own test oracle,
 //   tests/tests.rs:18-20; never a fallback of new_) / from_parts / into_parts / lcp_lens / table / text / len / is_empty /
 //   suffix / suffix_bytes / contains / positions / any_position,
-// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans, bwt / unbwt, lz77 / unlz, mems and fm_index (class FmIndex
-// below: the same queries from the transform alone).  Errors that are panics
+// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans, bwt / unbwt, lz77 / unlz, mems,
+// inverse_table / lce / lcp_range_min and fm_index (class FmIndex below: the same queries from the transform alone).  Errors that are panics
 // in the reference (assert! :380, assert_eq! :117) are std::runtime_error /
 // std::length_error here.  Text is indexed by BYTES (:379).
 #pragma once
@@ -203,6 +203,33 @@ public:
         r.len.resize((size_t)z);
         return r;
     }
+    // additive: longest common extensions between two positions of this text (suffix_hip.h, sfx_lce_*).  inverse_table():
+    // isa[table()[r]] = r; throws std::runtime_error for a table (from_parts) that is no permutation.  lce(i, j, k): how
+    // far the suffixes at i and j agree when up to k bytes may differ, never past the end of the text; a position equal
+    // to len() gives 0, one above 0xFFFFFFFF.  lcp_range_min(lo, hi): min lcp_lens()[lo .. hi), 0xFFFFFFFF for an empty
+    // range or hi > len().  The handle (inverse table + min-tree over lcp_lens()) is made on the first call.
+    std::vector<uint32_t> inverse_table() const
+    {
+        std::vector<uint32_t> isa(table_.size());
+        check(sfx_inverse_table_u32(table_.data(), table_.size(), isa.data()), "inverse_table");
+        return isa;
+    }
+    std::vector<uint32_t> lce_batch(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, uint32_t mismatches = 0) const
+    {
+        if (a.size() != b.size()) throw std::invalid_argument("lce_batch: one position of each list per pair");
+        std::vector<uint32_t> len(a.size());
+        if (!a.empty()) check(sfx_lce_query(lce_index(), a.data(), b.data(), a.size(), mismatches, len.data()), "lce_batch");
+        return len;
+    }
+    uint32_t lce(uint32_t i, uint32_t j, uint32_t mismatches = 0) const { return lce_batch({i}, {j}, mismatches)[0]; }
+    std::vector<uint32_t> lcp_range_min_batch(const std::vector<uint32_t>& lo, const std::vector<uint32_t>& hi) const
+    {
+        if (lo.size() != hi.size()) throw std::invalid_argument("lcp_range_min_batch: one bound of each list per range");
+        std::vector<uint32_t> out(lo.size());
+        if (!lo.empty()) check(sfx_lce_range_min(lce_index(), lo.data(), hi.data(), lo.size(), out.data()), "lcp_range_min_batch");
+        return out;
+    }
+    uint32_t lcp_range_min(uint32_t lo, uint32_t hi) const { return lcp_range_min_batch({lo}, {hi})[0]; }
     // the spans of a rep-shaped array (repeat_lens, match_stats().len) at min_len >= 1
     static std::vector<std::pair<uint32_t, uint32_t>> spans_of(const std::vector<uint32_t>& rep, uint32_t min_len)
     {
@@ -292,7 +319,9 @@ private:
     struct LazyIndex {
         std::once_flag once;
         sfx_index* ix = nullptr;
-        ~LazyIndex() { if (ix) sfx_index_destroy(ix); }
+        std::once_flag lce_once;
+        sfx_lce* lx = nullptr;
+        ~LazyIndex() { if (ix) sfx_index_destroy(ix); if (lx) sfx_lce_destroy(lx); }
     };
     sfx_index* index() const
     {
@@ -301,6 +330,15 @@ private:
             check(sfx_index_create(bytes(text_), text_.size(), table_.data(), &l.ix), "sfx_index_create");
         });
         return l.ix;
+    }
+    sfx_lce* lce_index() const
+    {
+        LazyIndex& l = *lazy_;
+        std::call_once(l.lce_once, [&] {
+            const std::vector<uint32_t> lcp = lcp_lens();
+            check(sfx_lce_create(table_.data(), lcp.data(), table_.size(), nullptr, 0, &l.lx), "sfx_lce_create");
+        });
+        return l.lx;
     }
     std::string text_;
     std::vector<uint32_t> table_;

@@ -110,6 +110,12 @@ extern "C" {
     // FM-index over that pair (sfx_fm_*): the size bound; the handle functions take `sfx_fm*`, a type the signature check
     // of this block (tests/test_rust_crate.py) has no mapping for yet, so they are not bound here
     fn sfx_fm_bytes(n: u64, sample_step: u32, occ_step: u32) -> u64;
+    // longest common extensions between two text positions (sfx_lce_*): the inverse table, the one-shot query and the size
+    // bound; the handle functions take `sfx_lce*`, which the signature check of this block has no mapping for either
+    fn sfx_inverse_table_u32(sa: *const u32, n: u64, isa_out: *mut u32) -> c_int;
+    fn sfx_lce_u32(sa: *const u32, lcp: *const u32, n: u64, doc_starts: *const u64, ndocs: u64, a: *const u32, b: *const u32,
+                   nq: u64, max_mismatches: u32, len_out: *mut u32) -> c_int;
+    fn sfx_lce_bytes(n: u64) -> u64;
     // suffix_tree's node table with ordered children (children(), preorder(), leaves(), suffix_indices() read it)
     #[allow(dead_code)]
     fn sfx_suffix_tree_u32(text: *const u8, sa: *const u32, lcp: *const u32, n: u64, node_capacity: u64,
@@ -280,6 +286,40 @@ pub fn unlz(f: &Lz77) -> Option<Vec<u8>> {
 /// two in 32..=4096).
 pub fn fm_index_bytes(n: usize, sample_step: u32, occ_step: u32) -> u64 {
     unsafe { sfx_fm_bytes(n as u64, sample_step, occ_step) }
+}
+
+/// The inverse of a suffix table: `isa[table[r]] = r`, or `None` where `table` is no permutation of `0..table.len()`.
+pub fn inverse_table(table: &[u32]) -> Option<Vec<u32>> {
+    let mut isa = vec![0u32; table.len()];
+    let rc = unsafe { sfx_inverse_table_u32(table.as_ptr(), table.len() as u64, isa.as_mut_ptr()) };
+    if rc == 1 {
+        return None;                                       // SFX_ERR_ARG
+    }
+    check(rc, "sfx_inverse_table_u32");
+    Some(isa)
+}
+
+/// Longest common extensions: for every pair `(a[q], b[q])` of byte positions of the text behind (`table`, `lcp`), how far
+/// the two suffixes agree when up to `max_mismatches` bytes may differ -- never past the end of the text, or with
+/// `doc_starts` (a collection: the table and in-document LCP of a generalized build) past the end of either position's
+/// document.  A position equal to the length gives 0, one above `u32::MAX`.  One shot: the index (inverse table and a
+/// min-tree over `lcp`) is built, queried and dropped.
+pub fn lce(table: &[u32], lcp: &[u32], doc_starts: Option<&[u64]>, a: &[u32], b: &[u32], max_mismatches: u32) -> Vec<u32> {
+    assert_eq!(table.len(), lcp.len());
+    assert_eq!(a.len(), b.len());
+    let mut len = vec![0u32; a.len()];
+    let (starts, ndocs) = doc_starts.map_or((std::ptr::null(), 0u64), |d| (d.as_ptr(), d.len() as u64));
+    check(unsafe {
+        sfx_lce_u32(table.as_ptr(), lcp.as_ptr(), table.len() as u64, starts, ndocs, a.as_ptr(), b.as_ptr(), a.len() as u64,
+                    max_mismatches, len.as_mut_ptr())
+    }, "sfx_lce_u32");
+    len
+}
+
+/// An upper bound on the device memory an LCE index over `n` suffixes holds: the inverse table and the levels above the
+/// LCP array, at most `4 n + n / 7 + 64 KiB`; 0 for `n == 0`.
+pub fn lce_index_bytes(n: usize) -> u64 {
+    unsafe { sfx_lce_bytes(n as u64) }
 }
 
 /// Additive API: many `positions()` at once.  Returns (start, end) pairs;

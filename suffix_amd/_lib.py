@@ -130,6 +130,20 @@ ABI = [
                                    _vp, _u64, _vp]),
     ("sfx_index_mems", _int, [_vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     ("sfx_gindex_mems", _int, [_vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    ("sfx_inverse_table_workspace_bytes", _u64, [_u64]),
+    ("sfx_inverse_table_dev", _int, [_vp, _u64, _vp, _vp, _u64, _vp]),
+    ("sfx_inverse_table_u32", _int, [_vp, _u64, _vp]),
+    ("sfx_lce_bytes", _u64, [_u64]),
+    ("sfx_lce_create_dev", _int, [_vp, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(_vp)]),
+    ("sfx_lce_create", _int, [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_vp)]),
+    ("sfx_lce_destroy", None, [_vp]),
+    ("sfx_lce_query_dev", _int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp]),
+    ("sfx_lce_query", _int, [_vp, _vp, _vp, _u64, _u32, _vp]),
+    ("sfx_lce_range_min_dev", _int, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    ("sfx_lce_range_min", _int, [_vp, _vp, _vp, _u64, _vp]),
+    ("sfx_lce_ranks_dev", _int, [_vp, _vp, _u64, _vp, _vp]),
+    ("sfx_lce_ranks", _int, [_vp, _vp, _u64, _vp]),
+    ("sfx_lce_u32", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u32, _vp]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),

@@ -12,6 +12,7 @@
 #include "sfx_fm.hip"   // the FM-index: kernels and host side, one translation unit with its entry points below
 #include "sfx_lz.hip"   // LZ77 factorization and its decoder, likewise
 #include "sfx_mem.hip"  // maximal exact matches, likewise
+#include "sfx_lce.hip"  // longest common extensions (inverse table + LCP min-tree), likewise
 
 namespace sfx {
 
@@ -859,6 +860,153 @@ int sfx_fm_lookup(const sfx_fm* fm, const uint32_t* ranks, uint64_t first, uint6
     if (count) SFX_HIP(hipMemcpyAsync(pos_out, dp.p, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     SFX_HIP(hipStreamSynchronize(st));
     return SFX_OK;
+}
+
+// ---- LCE index: inverse table, LCP range minima, k-mismatch extension (include/suffix_hip.h) ---------------------
+uint64_t sfx_inverse_table_workspace_bytes(uint64_t n) { return inverse_table_workspace_bytes(n); }
+int sfx_inverse_table_dev(const uint32_t* d_sa, uint64_t n, uint32_t* d_isa, void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    SFX_NEED_U32(d_sa, d_isa);
+    SFX_NEED_WS(d_workspace, workspace_bytes, inverse_table_workspace_bytes(n));
+    return inverse_table_dev(d_sa, n, d_isa, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sfx_inverse_table_u32(const uint32_t* sa, uint64_t n, uint32_t* isa_out)
+{
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!sa || !isa_out) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    const uint64_t wsb = inverse_table_workspace_bytes(n);
+    DevBuf ds, di, dw;
+    SFX_TRY(ds.alloc(n * sizeof(uint32_t)));
+    SFX_TRY(di.alloc(n * sizeof(uint32_t)));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    SFX_HIP(hipMemcpyAsync(ds.p, sa, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(inverse_table_dev((const uint32_t*)ds.p, n, (uint32_t*)di.p, dw.p, wsb, st));
+    SFX_HIP(hipMemcpyAsync(isa_out, di.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+uint64_t sfx_lce_bytes(uint64_t n) { return lce_bytes(n); }
+// A create's scratch (the two flags; from 2^27 entries on the 16 n bytes + radix scratch of the partitioned scatter) comes
+// from the pool of the host-pointer entry points: a loop of creates at one size allocates it once, and
+// sfx_release_cached_buffers() returns it.  It goes back to the pool when the create's work is done: after SFX_OK the
+// read-back of the flags was the last thing queued; after an error the stream is drained first.
+static int lce_create_pooled(const uint32_t* d_sa, const uint32_t* d_lcp, uint64_t n, const uint64_t* d_starts, uint64_t ndocs,
+                             hipStream_t st, bool own, sfx_lce** out)
+{
+    if (!out || n == 0 || n > 0xFFFFFFFFull || !d_sa || !d_lcp || (d_starts ? ndocs == 0 : ndocs != 0))
+        return lce_create_dev(d_sa, d_lcp, n, d_starts, ndocs, st, own, nullptr, 0, out);                   // (decided on the host)
+    const uint64_t need = inverse_table_workspace_bytes(n);
+    DevBuf scratch;
+    SFX_TRY(scratch.alloc(need));
+    const int rc = lce_create_dev(d_sa, d_lcp, n, d_starts, ndocs, st, own, scratch.p, need, out);
+    if (rc != SFX_OK) (void)hipStreamSynchronize(st);
+    return rc;
+}
+int sfx_lce_create_dev(const uint32_t* d_sa, const uint32_t* d_lcp, uint64_t n, const uint64_t* d_doc_starts, uint64_t ndocs, void* stream,
+                       sfx_lce** out)
+{
+    SFX_NEED_U32(d_sa, d_lcp);
+    SFX_NEED_U64(d_doc_starts);
+    return lce_create_pooled(d_sa, d_lcp, n, d_doc_starts, ndocs, (hipStream_t)stream, false, out);
+}
+int sfx_lce_create(const uint32_t* sa, const uint32_t* lcp, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs, sfx_lce** out)
+{
+    if (n == 0 || n > 0xFFFFFFFFull || !sa || !lcp || !out || (doc_starts ? ndocs == 0 : ndocs != 0))
+        return lce_create_dev(nullptr, nullptr, n, doc_starts, ndocs, nullptr, false, nullptr, 0, out);  // (decided on the host)
+    SFX_TRY(check_device());
+    DevBuf ds;
+    SFX_TRY(ds.alloc(n * sizeof(uint32_t)));
+    void* d_lcp = nullptr;
+    void* d_starts = nullptr;
+    hipStream_t st = call_stream();
+    int rc = SFX_OK;
+    {
+        StreamDrain drain{st};
+        rc = [&]() -> int {
+            SFX_HIP(hipMalloc(&d_lcp, n * sizeof(uint32_t)));                                               // the handle's own level 0
+            if (doc_starts) SFX_HIP(hipMalloc(&d_starts, ndocs * sizeof(uint64_t)));
+            SFX_HIP(hipMemcpyAsync(ds.p, sa, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            SFX_HIP(hipMemcpyAsync(d_lcp, lcp, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            if (doc_starts) SFX_HIP(hipMemcpyAsync(d_starts, doc_starts, ndocs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            return lce_create_pooled((const uint32_t*)ds.p, (const uint32_t*)d_lcp, n, (const uint64_t*)d_starts, ndocs, st, true, out);
+        }();
+    }
+    if (rc != SFX_OK) {
+        if (d_lcp) (void)hipFree(d_lcp);
+        if (d_starts) (void)hipFree(d_starts);
+    }
+    return rc;
+}
+void sfx_lce_destroy(sfx_lce* lx) { lce_destroy(lx); }
+int sfx_lce_query_dev(const sfx_lce* lx, const uint32_t* d_a, const uint32_t* d_b, uint64_t nq, uint32_t max_mismatches, uint32_t* d_len,
+                      void* stream)
+{
+    SFX_NEED_U32(d_a, d_b, d_len);
+    return lce_query_dev(lx, d_a, d_b, nq, max_mismatches, d_len, (hipStream_t)stream);
+}
+int sfx_lce_range_min_dev(const sfx_lce* lx, const uint32_t* d_lo, const uint32_t* d_hi, uint64_t nq, uint32_t* d_min, void* stream)
+{
+    SFX_NEED_U32(d_lo, d_hi, d_min);
+    return lce_range_min_dev(lx, d_lo, d_hi, nq, d_min, (hipStream_t)stream);
+}
+int sfx_lce_ranks_dev(const sfx_lce* lx, const uint32_t* d_pos, uint64_t nq, uint32_t* d_rank, void* stream)
+{
+    SFX_NEED_U32(d_pos, d_rank);
+    return lce_ranks_dev(lx, d_pos, nq, d_rank, (hipStream_t)stream);
+}
+// the host forms of the three queries: in0 / in1 (nullptr: one input) up, one launch, the answers down
+extern "C++" {
+template <class Run> static int lce_host_call(const sfx_lce* lx, const uint32_t* in0, const uint32_t* in1, bool two, uint64_t nq, uint32_t* out,
+                                              Run run)
+{
+    if (!lx) return SFX_ERR_ARG;
+    if (nq == 0) return SFX_OK;
+    if (!in0 || (two && !in1) || !out) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    DevBuf d0, d1, dout;
+    SFX_TRY(d0.alloc(nq * sizeof(uint32_t)));
+    if (two) SFX_TRY(d1.alloc(nq * sizeof(uint32_t)));
+    SFX_TRY(dout.alloc(nq * sizeof(uint32_t)));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    SFX_HIP(hipMemcpyAsync(d0.p, in0, nq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (two) SFX_HIP(hipMemcpyAsync(d1.p, in1, nq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(run((const uint32_t*)d0.p, (const uint32_t*)d1.p, (uint32_t*)dout.p, st));
+    SFX_HIP(hipMemcpyAsync(out, dout.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+}  // extern "C++"
+int sfx_lce_query(const sfx_lce* lx, const uint32_t* a, const uint32_t* b, uint64_t nq, uint32_t max_mismatches, uint32_t* len_out)
+{
+    return lce_host_call(lx, a, b, true, nq, len_out, [&](const uint32_t* da, const uint32_t* db, uint32_t* dl, hipStream_t st) {
+        return lce_query_dev(lx, da, db, nq, max_mismatches, dl, st);
+    });
+}
+int sfx_lce_range_min(const sfx_lce* lx, const uint32_t* lo, const uint32_t* hi, uint64_t nq, uint32_t* min_out)
+{
+    return lce_host_call(lx, lo, hi, true, nq, min_out, [&](const uint32_t* dl, const uint32_t* dh, uint32_t* dm, hipStream_t st) {
+        return lce_range_min_dev(lx, dl, dh, nq, dm, st);
+    });
+}
+int sfx_lce_ranks(const sfx_lce* lx, const uint32_t* pos, uint64_t nq, uint32_t* rank_out)
+{
+    return lce_host_call(lx, pos, nullptr, false, nq, rank_out, [&](const uint32_t* dp, const uint32_t*, uint32_t* dr, hipStream_t st) {
+        return lce_ranks_dev(lx, dp, nq, dr, st);
+    });
+}
+int sfx_lce_u32(const uint32_t* sa, const uint32_t* lcp, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs, const uint32_t* a,
+                const uint32_t* b, uint64_t nq, uint32_t max_mismatches, uint32_t* len_out)
+{
+    sfx_lce* lx = nullptr;
+    SFX_TRY(sfx_lce_create(sa, lcp, n, doc_starts, ndocs, &lx));
+    const int rc = sfx_lce_query(lx, a, b, nq, max_mismatches, len_out);
+    sfx_lce_destroy(lx);
+    return rc;
 }
 
 // ---- LZ77 factorization from the EARLIER repeat lengths, and its decoder (include/suffix_hip.h) -----------------

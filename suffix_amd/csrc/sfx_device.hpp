@@ -517,4 +517,29 @@ __device__ __forceinline__ void ms_positions(const uint8_t* __restrict__ text, c
     }
 }
 
+// ---- 64-ary pyramid of block minima over an LCP-shaped array (built by sfx_tree.hip) -----------------------------------
+constexpr int kPyrFan = 64;
+constexpr int kPyrMaxLevels = 6;                 // 64^6 > 2^32
+struct Pyramid {
+    const uint32_t* lvl[kPyrMaxLevels];          // lvl[0] = the LCP array itself
+    uint64_t len[kPyrMaxLevels];
+    int levels;
+};
+// min of lvl[0][lo..hi] (inclusive, 1 <= lo <= hi): at most 2 x 63 reads per level, whatever the values are
+__device__ __forceinline__ uint32_t range_min(const Pyramid& py, uint64_t lo, uint64_t hi)
+{
+    uint32_t m = 0xFFFFFFFFu;
+    for (int l = 0;; l++) {
+        const uint32_t* a = py.lvl[l];
+        if (l + 1 >= py.levels || hi - lo < 2 * kPyrFan) {
+            for (uint64_t i = lo; i <= hi; i++) m = dmin(m, a[i]);
+            return m;
+        }
+        while (lo % kPyrFan) m = dmin(m, a[lo++]);
+        while ((hi + 1) % kPyrFan) m = dmin(m, a[hi--]);
+        lo /= kPyrFan;                                   // (>= 1 block remains; block 0 of a level is never reached: lo >= 1)
+        hi = (hi + 1) / kPyrFan - 1;
+    }
+}
+
 }  // namespace sfx

@@ -490,6 +490,22 @@ uint64_t mems_workspace_bytes(uint64_t m, uint64_t pair_limit);
 int mems_dev(const MemSource& s, const uint8_t* d_q, uint64_t m, uint32_t min_len, uint32_t flags, uint64_t pair_limit, uint32_t* d_qpos,
              uint32_t* d_tpos, uint32_t* d_len, uint64_t capacity, uint64_t* pairs_out, uint64_t* count_out, void* ws, uint64_t ws_bytes,
              hipStream_t st);
+#ifdef SFX_DEV_HOOKS
+// the 64-ary pyramid of sfx_tree.hip over any LCP-shaped array (entry 0 as it is): lcp_pyramid_words(n) u32 at w
+uint64_t lcp_pyramid_words(uint64_t n);
+int lcp_pyramid_build_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* w, hipStream_t st, Pyramid* out);
+#endif
+// LCE index: inverse table + 32-ary min-tree over the LCP array (sfx_lce.hip); creation and inverse_table_dev synchronise
+// the stream once, for the permutation flags
+uint64_t inverse_table_workspace_bytes(uint64_t n);
+int inverse_table_dev(const uint32_t* d_sa, uint64_t n, uint32_t* d_isa, void* ws, uint64_t ws_bytes, hipStream_t st);
+uint64_t lce_bytes(uint64_t n);
+int lce_create_dev(const uint32_t* d_sa, const uint32_t* d_lcp, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, hipStream_t st,
+                   bool own, void* scratch, uint64_t scratch_bytes, sfx_lce** out);
+void lce_destroy(sfx_lce* lx);
+int lce_query_dev(const sfx_lce* lx, const uint32_t* d_a, const uint32_t* d_b, uint64_t nq, uint32_t k, uint32_t* d_len, hipStream_t st);
+int lce_range_min_dev(const sfx_lce* lx, const uint32_t* d_lo, const uint32_t* d_hi, uint64_t nq, uint32_t* d_min, hipStream_t st);
+int lce_ranks_dev(const sfx_lce* lx, const uint32_t* d_pos, uint64_t nq, uint32_t* d_rank, hipStream_t st);
 // bucket directory of the resident index (sfx_query.hip)
 int dir_shape(uint64_t n, int bits, int* k_out, int* dbits_out, uint64_t* entries_out);
 uint64_t dir_scratch_words(uint64_t entries);

@@ -20,15 +20,8 @@
 
 namespace sfx {
 
-constexpr int kPyrFan = 64;
-constexpr int kPyrMaxLevels = 6;                 // 64^6 > 2^32
+// (kPyrFan, kPyrMaxLevels, Pyramid and range_min live in sfx_device.hpp: the LCE index's development baseline reads them too)
 constexpr uint32_t kNoNode = 0xFFFFFFFFu;
-
-struct Pyramid {
-    const uint32_t* lvl[kPyrMaxLevels];          // lvl[0] = the LCP array itself
-    uint64_t len[kPyrMaxLevels];
-    int levels;
-};
 
 __global__ void __launch_bounds__(kBlock)
 k_pyr_reduce(const uint32_t* __restrict__ in, uint64_t n_in, uint32_t* __restrict__ out, uint64_t n_out, int first_is_zero)
@@ -297,6 +290,14 @@ static int pyramid_build(const uint32_t* d_lcp, uint64_t n, uint32_t* w, const c
     for (int l = py.levels; l < kPyrMaxLevels; l++) { py.lvl[l] = nullptr; py.len[l] = 0; }
     return SFX_OK;
 }
+#ifdef SFX_DEV_HOOKS
+// the same for the LCE index's development baseline in sfx_api.hip's translation unit: entry 0 as it is
+uint64_t lcp_pyramid_words(uint64_t n) { return pyramid_words(n); }
+int lcp_pyramid_build_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* w, hipStream_t st, Pyramid* out)
+{
+    return pyramid_build(d_lcp, n, w, "lce_pyramid", st, out, 0);
+}
+#endif
 // (+ the list of boundaries whose searches leave their tile: n / 16 entries, and its counter)
 static uint64_t open_list_cap(uint64_t n) { return n / 16 + 4096; }
 uint64_t lcp_intervals_workspace_bytes(uint64_t n)
@@ -369,22 +370,6 @@ __device__ __forceinline__ uint64_t gsa_doc_of(const uint64_t* __restrict__ star
 __device__ __forceinline__ uint64_t gsa_doc_end(const uint64_t* __restrict__ starts, uint64_t ndocs, uint64_t n, uint64_t d)
 {
     return d + 1 < ndocs ? starts[d + 1] : n;
-}
-// min of lvl[0][lo..hi] (inclusive, 1 <= lo <= hi): at most 2 x 63 reads per level, whatever the values are
-__device__ __forceinline__ uint32_t range_min(const Pyramid& py, uint64_t lo, uint64_t hi)
-{
-    uint32_t m = 0xFFFFFFFFu;
-    for (int l = 0;; l++) {
-        const uint32_t* a = py.lvl[l];
-        if (l + 1 >= py.levels || hi - lo < 2 * kPyrFan) {
-            for (uint64_t i = lo; i <= hi; i++) m = dmin(m, a[i]);
-            return m;
-        }
-        while (lo % kPyrFan) m = dmin(m, a[lo++]);
-        while ((hi + 1) % kPyrFan) m = dmin(m, a[hi--]);
-        lo /= kPyrFan;                                   // (>= 1 block remains; block 0 of a level is never reached: lo >= 1)
-        hi = (hi + 1) / kPyrFan - 1;
-    }
 }
 
 // doc_starts: [0] == 0, non-decreasing, none past n

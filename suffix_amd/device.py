@@ -693,6 +693,106 @@ def mems(text, sa, query, min_len, unique=False, max_pairs=1 << 30, capacity=Non
     return _mems(eng, call, "sfx_mems_dev", n, query, text, min_len, unique, max_pairs, capacity, workspace)
 
 
+def inverse_table_workspace(n, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_inverse_table_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def inverse_table(sa, out=None, workspace=None, engine=None):
+    """isa[sa[r]] = r (uint32 in int32 storage): sfx_inverse_table_dev.  Raises for a table that is no permutation of
+    [0, n); reading that verdict synchronises the current stream."""
+    eng = engine or default_engine()
+    _check_u32(sa, "sa")
+    n = sa.numel()
+    if sa.is_cuda:
+        eng.require_device()
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=sa.device)
+    _check_u32(out, "out", n)
+    if workspace is None:
+        workspace = inverse_table_workspace(n, sa.device, eng)
+    with _on(sa):
+        eng.check(eng.lib.sfx_inverse_table_dev(_p(sa), n, _p(out), _p(workspace), workspace.numel(), _stream_ptr(sa)),
+                  "sfx_inverse_table_dev")
+    return out
+
+
+class LceDeviceIndex:
+    """Longest common extensions between positions of the indexed text, from the device tensors (sa, lcp) of `build_sa_lcp`
+    -- or of `build_gsa` with its `doc_starts` (int64), where no extension passes a document end (sfx_lce_create_dev).
+    The handle holds the inverse table and a 32-ary min-tree over lcp; lcp and doc_starts are borrowed (kept alive here),
+    sa is free again after creation, which synchronises the current stream once.  `lce`, `range_min` and `rank_of` queue
+    on the current stream without a synchronisation."""
+
+    def __init__(self, sa, lcp, doc_starts=None, engine=None):
+        self._eng = engine or default_engine()
+        _check_u32(sa, "sa")
+        _check_u32(lcp, "lcp", sa.numel())
+        if lcp.device != sa.device:
+            raise ValueError(f"lcp must be on the table's device ({sa.device})")
+        if doc_starts is not None:
+            if doc_starts.dtype != torch.int64 or doc_starts.dim() != 1 or not doc_starts.is_contiguous() or not doc_starts.numel():
+                raise TypeError("doc_starts must be a contiguous 1-D int64 tensor with one entry per document")
+            if doc_starts.device != sa.device:
+                raise ValueError(f"doc_starts must be on the table's device ({sa.device})")
+        if sa.is_cuda:
+            self._eng.require_device()
+        self._dev, self.n = sa.device, sa.numel()
+        self._lcp, self._starts = lcp, doc_starts                       # (borrowed by the index: keep them alive)
+        self._on = torch.empty(0, dtype=torch.uint8, device=sa.device)
+        h = ctypes.c_void_p()
+        with _on(sa):
+            self._eng.check(self._eng.lib.sfx_lce_create_dev(_p(sa), _p(lcp), self.n, _p(doc_starts),
+                                                             0 if doc_starts is None else doc_starts.numel(), _stream_ptr(sa),
+                                                             ctypes.byref(h)), "sfx_lce_create_dev")
+        self._h = h
+        self.nbytes = int(self._eng.lib.sfx_lce_bytes(self.n))
+
+    def _arg(self, t, name, n=None):
+        _check_u32(t, name, n)
+        if t.device != self._dev:
+            raise ValueError(f"{name} must be on the index's device ({self._dev})")
+
+    def lce(self, a, b, mismatches=0):
+        """len[q] = how far the suffixes at a[q] and b[q] agree with at most `mismatches` differing bytes (the same budget
+        for the whole batch); 0 for a position equal to n, 0xFFFFFFFF for one above."""
+        self._arg(a, "a")
+        self._arg(b, "b", a.numel())
+        if not 0 <= int(mismatches) <= 0xFFFFFFFF:
+            raise ValueError("mismatches must be in 0 .. 2^32 - 1")
+        out = torch.empty(a.numel(), dtype=torch.int32, device=self._dev)
+        with _on(self._on):
+            self._eng.check(self._eng.lib.sfx_lce_query_dev(self._h, _p(a), _p(b), a.numel(), int(mismatches), _p(out),
+                                                            _stream_ptr(self._on)), "sfx_lce_query_dev")
+        return out
+
+    def range_min(self, lo, hi):
+        """min lcp[lo[q] : hi[q]]; 0xFFFFFFFF for an empty range or hi > n."""
+        self._arg(lo, "lo")
+        self._arg(hi, "hi", lo.numel())
+        out = torch.empty(lo.numel(), dtype=torch.int32, device=self._dev)
+        with _on(self._on):
+            self._eng.check(self._eng.lib.sfx_lce_range_min_dev(self._h, _p(lo), _p(hi), lo.numel(), _p(out), _stream_ptr(self._on)),
+                            "sfx_lce_range_min_dev")
+        return out
+
+    def rank_of(self, pos):
+        """The table rank of every position; 0xFFFFFFFF for a position >= n."""
+        self._arg(pos, "pos")
+        out = torch.empty(pos.numel(), dtype=torch.int32, device=self._dev)
+        with _on(self._on):
+            self._eng.check(self._eng.lib.sfx_lce_ranks_dev(self._h, _p(pos), pos.numel(), _p(out), _stream_ptr(self._on)),
+                            "sfx_lce_ranks_dev")
+        return out
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._eng.lib.sfx_lce_destroy(h)
+
+    __del__ = close
+
+
 class GeneralizedDeviceIndex:
     """Resident generalized index over device tensors (text, doc_starts, GSA, DA) -- borrowed, keep them alive;
     `query` = per query (start, end, found, any, ndocs): matches inside one document only, ndocs = the number of

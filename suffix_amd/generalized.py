@@ -15,6 +15,7 @@ no match spans two documents.
     match_stats(query, max_len)   longest match of every suffix of a NEW text inside one document of the collection
     shared_spans(query, min_len)  [(begin, end)] of the query bytes inside such matches of at least min_len bytes
     mems(query, min_len, unique)  the maximal exact matches of a NEW text, each inside one document
+    lce((doc, off), (doc, off), mismatches)   how far two suffixes of the collection agree, never past a document end
 
 Construction and queries run on the GPU through the C ABI (sfx_build_gsa_u32, sfx_gindex_*); there is no CPU
 path except `new_naive`, the definition itself.
@@ -24,7 +25,7 @@ import ctypes
 import numpy as np
 
 from ._lib import default_engine
-from .table import Mems, _as_bytes, _match_stats, _mems, _ptr, _repeat_lens, _repeat_spans, _shared_spans
+from .table import Mems, _LceHandle, _as_bytes, _match_stats, _mems, _ptr, _repeat_lens, _repeat_spans, _shared_spans
 
 _NONE = 0xFFFFFFFF
 
@@ -42,6 +43,7 @@ class GeneralizedSuffixTable:
             starts[1:] = np.cumsum([len(d) for d in self._docs[:-1]], dtype=np.uint64)
         self._starts = starts
         self._index = None
+        self._lce = _LceHandle(self._eng)
         n = self._tarr.size
         if n > 0xFFFFFFFF:
             raise OverflowError("GeneralizedSuffixTable: more than u32::MAX bytes in all")
@@ -92,6 +94,9 @@ class GeneralizedSuffixTable:
                 self._eng.lib.sfx_gindex_destroy(ix)
             except Exception:
                 pass
+        lx = getattr(self, "_lce", None)
+        if lx:
+            lx.close()
 
     # -- accessors --------------------------------------------------------------------------
     def table(self):
@@ -248,3 +253,23 @@ class GeneralizedSuffixTable:
         d = np.searchsorted(self._starts, tpos.astype(np.uint64), side="right").astype(np.int64) - 1
         off = (tpos.astype(np.int64) - self._starts[d].astype(np.int64)).astype(np.uint32) if tpos.size else tpos.copy()
         return Mems(qpos, tpos, ln, pairs, doc=d.astype(np.uint32), offset=off)
+
+    # -- longest common extensions ----------------------------------------------------------------
+    def _lce_index(self):
+        return self._lce.get(self._table, self._lcp, self._starts)
+
+    def lce_batch(self, a, b, mismatches=0):
+        """len (uint32) for pairs of TEXT positions (doc_starts[doc] + offset): how far the two truncated suffixes agree
+        with at most `mismatches` differing bytes; no extension passes the end of either position's document.  A
+        position equal to len() gives 0, one above 0xFFFFFFFF."""
+        return self._lce.lce(self._lce_index, a, b, mismatches)
+
+    def lce(self, a, b, mismatches=0):
+        """As lce_batch for one pair of (document, offset) positions inside their documents."""
+        pos = []
+        for d, o in (a, b):
+            d, o = int(d), int(o)
+            if not 0 <= d < len(self._docs) or not 0 <= o < len(self._docs[d]):
+                raise IndexError(f"({d}, {o}) is no position of the collection")
+            pos.append(int(self._starts[d]) + o)
+        return int(self.lce_batch([pos[0]], [pos[1]], mismatches)[0])

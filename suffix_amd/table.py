@@ -21,6 +21,7 @@ Same method names, argument meaning and error behaviour as the Rust API:
     (none)                                   .mems(query, min_len, unique): the maximal exact matches of a new text
     (none)                                   .bwt(sample_step) / suffix_amd.unbwt(bwt, samples, sample_step)
     (none)                                   .fm_index(sample_step) / suffix_amd.FmIndex: the same queries from the transform alone
+    (none)                                   .inverse_table() / .lce(i, j, mismatches) / .lce_batch / .lcp_range_min[_batch]
 
 Text is indexed by BYTES (every UTF-8 byte offset has a suffix, :29-31 of the
 crate docs and :379); `str` input is encoded as UTF-8.  Construction, LCP and
@@ -112,6 +113,64 @@ def _shared_spans(eng, match_stats, query, min_len):
         raise ValueError("min_len must be in 1 .. 2^32 - 1")
     b, e = _repeat_spans(eng, match_stats(query, max_len=min_len), min_len, None)
     return list(zip(b.tolist(), e.tolist()))
+
+
+def _u32_arg(x, name):
+    a = np.asarray(x)
+    if a.ndim != 1:
+        raise ValueError(f"{name} must be one-dimensional")
+    if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > _NONE):
+        raise ValueError(f"{name} must hold integers in 0 .. 2^32 - 1")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+class _LceHandle:
+    """The lazily made sfx_lce handle of a table (SuffixTable, GeneralizedSuffixTable): sfx_lce_create over host arrays,
+    which copies them; freed with its owner."""
+
+    def __init__(self, eng):
+        self._eng, self._h = eng, None
+
+    def get(self, table, lcp, starts=None):
+        """lcp: the array, or a callable that makes it -- called only when the handle does not exist yet."""
+        if self._h is None:
+            self._eng.require_device()
+            if callable(lcp):
+                lcp = lcp()
+            h = ctypes.c_void_p()
+            self._eng.check(self._eng.lib.sfx_lce_create(_ptr(table), _ptr(lcp), int(table.size), _ptr(starts) if starts is not None else None,
+                                                         int(starts.size) if starts is not None else 0, ctypes.byref(h)), "sfx_lce_create")
+            self._h = h
+        return self._h
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            try:
+                self._eng.lib.sfx_lce_destroy(h)
+            except Exception:
+                pass
+
+    def lce(self, h, a, b, mismatches):
+        a, b = _u32_arg(a, "a"), _u32_arg(b, "b")
+        if a.size != b.size:
+            raise ValueError("a and b must hold one position per pair")
+        k = int(mismatches)
+        if k < 0 or k > _NONE:
+            raise ValueError("mismatches must be in 0 .. 2^32 - 1")
+        out = np.zeros(a.size, dtype=np.uint32)
+        if a.size:
+            self._eng.check(self._eng.lib.sfx_lce_query(h(), _ptr(a), _ptr(b), int(a.size), k, _ptr(out)), "sfx_lce_query")
+        return out
+
+    def range_min(self, h, lo, hi):
+        lo, hi = _u32_arg(lo, "lo"), _u32_arg(hi, "hi")
+        if lo.size != hi.size:
+            raise ValueError("lo and hi must hold one bound per range")
+        out = np.zeros(lo.size, dtype=np.uint32)
+        if lo.size:
+            self._eng.check(self._eng.lib.sfx_lce_range_min(h(), _ptr(lo), _ptr(hi), int(lo.size), _ptr(out)), "sfx_lce_range_min")
+        return out
 
 
 class Mems:
@@ -236,6 +295,7 @@ class SuffixTable:
         self._text = _as_bytes(text)
         self._tarr = np.frombuffer(self._text, dtype=np.uint8)
         self._index = None
+        self._lce = _LceHandle(self._eng)
         if _table is None:
             # sais_table (:378-386): assert len <= u32::MAX, allocate, fill
             n = self._tarr.size
@@ -298,6 +358,9 @@ class SuffixTable:
                 self._eng.lib.sfx_index_destroy(ix)
             except Exception:
                 pass
+        lx = getattr(self, "_lce", None)
+        if lx:
+            lx.close()
 
     # -- accessors ----------------------------------------------------------------------
     def table(self):
@@ -410,6 +473,37 @@ class SuffixTable:
         bytes (scope as for repeat_lens; "earlier" keeps the first copy of everything out of the report)."""
         b, e = _repeat_spans(self._eng, self.repeat_lens(scope), min_len, None)
         return list(zip(b.tolist(), e.tolist()))
+
+    # -- longest common extensions -----------------------------------------------------------------
+    def inverse_table(self):
+        """isa (uint32): isa[table()[r]] = r, the rank of the suffix at every text position (sfx_inverse_table_u32).
+        Raises SuffixHipError for a table (from_parts) that is no permutation of the positions."""
+        n = self.len()
+        isa = np.zeros(n, dtype=np.uint32)
+        if n:
+            self._eng.require_device()
+        self._eng.check(self._eng.lib.sfx_inverse_table_u32(_ptr(self._table), n, _ptr(isa)), "sfx_inverse_table_u32")
+        return isa
+
+    def _lce_index(self):
+        return self._lce.get(self._table, self.lcp_lens)             # (the LCP array is built for the first call only)
+
+    def lce_batch(self, a, b, mismatches=0):
+        """len (uint32): how far the suffixes at byte positions a[q] and b[q] agree when up to `mismatches` bytes may
+        differ (one budget for the batch) -- the largest l with at most that many differing places among the first l
+        bytes, never past the end of the text.  A position equal to len() gives 0, one above 0xFFFFFFFF; a[q] == b[q]
+        gives the rest of the text.  The handle (inverse table + min-tree over lcp_lens()) is made on the first call."""
+        return self._lce.lce(self._lce_index, a, b, mismatches)
+
+    def lce(self, i, j, mismatches=0):
+        return int(self.lce_batch([int(i)], [int(j)], mismatches)[0])
+
+    def lcp_range_min_batch(self, lo, hi):
+        """min lcp_lens()[lo[q]:hi[q]] (uint32); 0xFFFFFFFF for an empty range or hi > len()."""
+        return self._lce.range_min(self._lce_index, lo, hi)
+
+    def lcp_range_min(self, lo, hi):
+        return int(self.lcp_range_min_batch([int(lo)], [int(hi)])[0])
 
     # -- Burrows-Wheeler transform ----------------------------------------------------------------
     def bwt(self, sample_step=256):

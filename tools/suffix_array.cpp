@@ -3,7 +3,7 @@
 // over the MI355X engine's C++ host mirror (include/suffix_table.hpp -> libsuffix_hip.so),
 // extended into the large-file driver SURVEY.md 8(f) asks for:
 //
-//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]
+//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--lce I,J[,I,J...] [--mismatches K]] [--isa] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]
 //
 //   --dump PREFIX   write PREFIX.sa (and PREFIX.lcp with --lcp) as raw little-endian u32
 //                   arrays -- the on-disk form SuffixTable::from_parts (:111-119) reloads
@@ -22,6 +22,10 @@
 //                   == FILE[tpos .. tpos+len), extendable in neither direction -- ascending by qpos, then by the table rank
 //                   of tpos; --unique keeps the matches whose bytes occur once in FILE; more than P candidate pairs
 //                   (default 2^30) end with status 2 and a message naming the count
+//   --lce I,J[,I,J...] [--mismatches K]
+//                   one line "i j len" per pair: how far the suffixes at byte positions i and j agree when up to K bytes
+//                   (default 0) may differ; 0 for a position equal to the file's length, 4294967295 for one above
+//   --isa           the inverse table: "ISA: rank of the whole text R, of its last byte R"; with --dump also PREFIX.isa
 //   --bwt PREFIX    write the Burrows-Wheeler transform: PREFIX.bwt (n raw bytes) and PREFIX.bwi (little-endian u32: the
 //                   sample step S, then the sampled rows; --step S, 0 or a power of two, default 256)
 //   suffix-array PREFIX.bwt --unbwt PREFIX.bwi --out OUT
@@ -87,7 +91,9 @@ int main(int argc, char** argv)
     long long min_len = 32, step = 256, occ_step = 0, mems = -1, max_pairs = 1ll << 30;
     std::vector<std::string> queries;
     bool want_lcp = false, timing = false, earlier = false, unlz = false, min_len_given = false, unique = false, max_pairs_given = false;
-    long long repeats = -1;
+    long long repeats = -1, mismatches = 0;
+    bool want_isa = false, mismatches_given = false;
+    std::vector<uint32_t> lce_pos;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto need = [&](const char* opt) -> const char* {
@@ -111,6 +117,28 @@ int main(int argc, char** argv)
             if (mems < 1 || mems > 0xFFFFFFFFll) { fprintf(stderr, "--mems needs a length of at least 1\n"); return 1; }
         }
         else if (a == "--unique") unique = true;
+        else if (a == "--isa") want_isa = true;
+        else if (a == "--lce") {
+            // I,J[,I,J...]: an even number of positions
+            const std::string v = need("--lce");
+            size_t p = 0;
+            while (p <= v.size()) {
+                size_t e = v.find(',', p);
+                if (e == std::string::npos) e = v.size();
+                char* end = nullptr;
+                const std::string tok = v.substr(p, e - p);
+                const unsigned long long x = strtoull(tok.c_str(), &end, 10);
+                if (tok.empty() || *end || tok[0] == '-' || x > 0xFFFFFFFFull) { fprintf(stderr, "--lce needs positions I,J[,I,J...]\n"); return 1; }
+                lce_pos.push_back((uint32_t)x);
+                p = e + 1;
+            }
+            if (lce_pos.size() % 2) { fprintf(stderr, "--lce needs an even number of positions\n"); return 1; }
+        }
+        else if (a == "--mismatches") {
+            mismatches = atoll(need("--mismatches"));
+            mismatches_given = true;
+            if (mismatches < 0 || mismatches > 0xFFFFFFFFll) { fprintf(stderr, "--mismatches needs a count of at least 0\n"); return 1; }
+        }
         else if (a == "--max-pairs") {
             max_pairs = atoll(need("--max-pairs"));
             max_pairs_given = true;
@@ -138,10 +166,11 @@ int main(int argc, char** argv)
         else file = a;
     }
     if (mems > 0 && match.empty()) { fprintf(stderr, "--mems needs --match FILE2\n"); return 1; }
+    if (mismatches_given && lce_pos.empty()) { fprintf(stderr, "--mismatches needs --lce I,J\n"); return 1; }
     if (mems > 0 && min_len_given && lz.empty()) { fprintf(stderr, "--mems L takes its length itself: --min-len belongs to the span report of --match alone\n"); return 1; }
     if (mems < 0 && (unique || max_pairs_given)) { fprintf(stderr, "--unique and --max-pairs need --mems L\n"); return 1; }
     if (file.empty()) {
-        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]\n       suffix-array PREFIX.lz --unlz --out OUT\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
+        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--lce I,J[,I,J...] [--mismatches K]] [--isa] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]\n       suffix-array PREFIX.lz --unlz --out OUT\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
         return 1;
     }
     std::string text;
@@ -252,8 +281,15 @@ int main(int argc, char** argv)
             for (uint32_t v : lcp) { sum += v; if (v > mx) mx = v; }
             std::cout << "LCP: max " << mx << " mean " << (lcp.empty() ? 0.0 : (double)sum / (double)lcp.size()) << "\n";
         }
+        std::vector<uint32_t> isa;
+        if (want_isa) {
+            t0 = std::chrono::steady_clock::now();
+            isa = st.inverse_table();
+            if (timing) std::cout << "isa ms: " << ms_since(t0) << "\n";
+            std::cout << "ISA: rank of the whole text " << (isa.empty() ? 0u : isa[0]) << ", of its last byte " << (isa.empty() ? 0u : isa.back()) << "\n";
+        }
         if (!dump.empty()) {
-            if (!write_u32(dump + ".sa", st.table()) || (want_lcp && !write_u32(dump + ".lcp", lcp))) {
+            if (!write_u32(dump + ".sa", st.table()) || (want_lcp && !write_u32(dump + ".lcp", lcp)) || (want_isa && !write_u32(dump + ".isa", isa))) {
                 fprintf(stderr, "cannot write %s.*\n", dump.c_str());
                 return 1;
             }
@@ -268,6 +304,14 @@ int main(int argc, char** argv)
                 if (e > s) std::cout << (e - s > 8 ? ", ...]" : "]");
                 std::cout << "\n";
             }
+        }
+        if (!lce_pos.empty()) {
+            std::vector<uint32_t> a, b;
+            for (size_t k = 0; k < lce_pos.size(); k += 2) { a.push_back(lce_pos[k]); b.push_back(lce_pos[k + 1]); }
+            t0 = std::chrono::steady_clock::now();
+            const auto len = st.lce_batch(a, b, (uint32_t)mismatches);
+            if (timing) std::cout << "lce ms: " << ms_since(t0) << "\n";
+            for (size_t k = 0; k < len.size(); k++) std::cout << a[k] << " " << b[k] << " " << len[k] << "\n";
         }
         if (repeats > 0) {
             t0 = std::chrono::steady_clock::now();
