@@ -529,8 +529,8 @@ int sfx_unlz(const uint32_t* len, const uint32_t* src, const uint8_t* lit, uint6
  *   text's suffix array is unspecified.  The index entries rely on the check made when the index was created;
  *   sfx_index_mems_dev starts the search in the bucket directory, sfx_gindex_mems_dev uses the collection's search.
  * sfx_index_mems / sfx_gindex_mems: the same with host buffers, staged through HBM.
- * Not covered: matches unique in the query too (MUMmer's -mum), MEMs over the FM-index, approximate matches,
- * chaining of seeds, the multi-GPU path. */
+ * Not covered: matches unique in the query too (MUMmer's -mum), MEMs over the FM-index, chaining of seeds, the
+ * multi-GPU path.  (Approximate matches of whole patterns: the k-mismatch search below.) */
 enum { SFX_MEM_UNIQUE = 1 };
 uint64_t sfx_mems_workspace_bytes(uint64_t m, uint64_t pair_limit);
 int sfx_mems_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint8_t* d_query, uint64_t m,
@@ -554,6 +554,83 @@ int sfx_index_mems(const sfx_index* ix, const uint8_t* query, uint64_t m, uint32
 int sfx_gindex_mems(const sfx_gindex* gx, const uint8_t* query, uint64_t m, uint32_t min_len, uint32_t flags,
                     uint64_t pair_limit, uint32_t* qpos_out, uint32_t* tpos_out, uint32_t* len_out, uint64_t capacity,
                     uint64_t* pairs_out, uint64_t* count_out);
+
+/* ---- k-mismatch pattern search against the table -------------------------------------------
+ * Where does a pattern occur if up to k bytes may differ (Hamming distance; no insertions or deletions)?
+ * T = the indexed text of n bytes with table sa.  Patterns P_0 .. P_(nq-1) arrive as qbytes / qoff, exactly as for
+ * sfx_index_query_dev; m_j = the length of pattern j, k = max_mismatches <= 255.
+ *   occurrence   of pattern j: a position p with m_j >= 1 and p + m_j <= end(p) such that fewer than k + 1 indices
+ *                i < m_j have P_j[i] != T[p+i].  end(p) = n for a plain index, the end of p's document for a
+ *                collection (the truncated-suffix model): a window never leaves the document in which it starts.
+ *                mism = the number of differing bytes, 0 <= mism <= k.  An empty pattern has no occurrence; a pattern
+ *                with 0 < m_j <= k occurs at every window that has room.
+ *   pieces       pattern j is cut at b_t = floor(t * m_j / (k + 1)), t = 0 .. k + 1; piece t = P_j[b_t .. b_(t+1)), empty
+ *                now and then when m_j < k + 1.  By the pigeonhole principle every occurrence has a piece that matches
+ *                exactly at p + b_t (an empty piece matches everywhere); the first such t is its OWNING piece -- a
+ *                property of (T, P_j, k, p), not of the implementation.
+ *   candidates   triples (j, t, r), r a rank in the exact interval of piece t (the interval of the collection's search
+ *                for a collection; all of [0, n) for an empty piece of a non-empty pattern; none for an empty pattern),
+ *                numbered ascending by j, then t, then r; C of them.  With q = sa[r] and p = q - b_t a candidate yields
+ *                an occurrence iff q >= b_t, p is not before the start of q's document, p + m_j <= end(q), every earlier
+ *                piece has at least one mismatch at p, and the whole window has at most k.  Every occurrence is thus
+ *                produced by exactly one candidate, that of its owning piece.
+ *   output       the triples (pattern, tpos, mism) of the surviving candidates, in candidate order: ascending by
+ *                pattern, then by owning piece, then by the table rank of tpos + b_owner.  first[0 .. nq] (u64): the
+ *                occurrences of pattern j are out[first[j] .. first[j+1]); first[nq] = Z even when Z exceeds
+ *                `capacity` (first counts occurrences, not written triples).  The whole result is determined bit for
+ *                bit by (T, sa, doc_starts, patterns, k).  At k = 0 the triples of pattern j are exactly
+ *                sa[start_j .. end_j) of the exact search, in that order, with mism = 0.
+ * Work is proportional to C plus the bytes compared (a window is abandoned at mismatch k + 1): short pieces of a
+ * repetitive text have wide intervals, so the caller gives a cand_limit, the same duty as pair_limit above.
+ *
+ * sfx_hamming_dev / sfx_index_hamming_dev / sfx_gindex_hamming_dev: everything is queued on the caller's stream, which
+ *   is synchronised ONCE, at the end, to read (C, Z) back.  The calls keep no state in the index and take their memory
+ *   from the workspace (the piece search of sfx_index_hamming_dev is sfx_index_query_dev, whose large batches use that
+ *   call's scratch, kept per calling thread): any number of threads may call on one index at once, each with its own
+ *   workspace.
+ *   *cands_out = C always.  C <= cand_limit: *count_out = Z, the first min(Z, capacity) triples are written and nothing
+ *   past them, and first (when given) is complete whatever capacity is.  C > cand_limit: SFX_OK, nothing is written to
+ *   the triple arrays or to first, and *count_out = 0 -- the refusal is recognised by *cands_out > cand_limit.
+ *   SFX_ERR_ARG: cand_limit == 0, max_mismatches > 255, cands_out / count_out NULL, a triple array NULL while
+ *   capacity > 0, a NULL input of a non-empty call, a qoff that is not monotone (found on the device, reported
+ *   through the same single read-back), a workspace off SFX_WORKSPACE_ALIGN.  SFX_ERR_TOO_LARGE: n > u32::MAX, a
+ *   pattern longer than u32::MAX (found on the device likewise), nq * (k + 1) >= 2^32.  A workspace below
+ *   sfx_hamming_workspace_bytes(nq, max_mismatches, cand_limit) is SFX_ERR_WORKSPACE.
+ *   nq == 0 or n == 0: SFX_OK with C = Z = 0, first all zero if given.
+ *   Workspace <= 32 (nq (k + 1) + 1) + cand_limit / 4 + 64 KiB bytes (a cand_limit above nq (k + 1) * u32::MAX counts
+ *   as that).
+ *   d_text and d_qbytes may have any alignment, d_pattern / d_tpos need 4 bytes, d_qoff / d_first 8.  Outside the
+ *   caller's buffers nothing is written; outside T, sa (da and doc_starts of a collection), the patterns and the
+ *   workspace nothing is read; no load of the compare touches a byte outside the window [p, p + m_j).
+ *   sfx_hamming_dev takes text and table as they are, like sfx_mems_dev: for any table whose entries are all < n
+ *   nothing is read or written out of bounds and every loop ends; what is reported for a table that is not the
+ *   text's suffix array is unspecified.  sfx_index_hamming_dev searches the pieces through the bucket directory and
+ *   the key tree, sfx_gindex_hamming_dev with the collection's search.
+ * sfx_index_hamming / sfx_gindex_hamming: the same with host buffers, staged through HBM.
+ * Not covered: edit distance (insertions and deletions), search over the FM-index, wildcards, per-pattern k, the
+ * multi-GPU path. */
+uint64_t sfx_hamming_workspace_bytes(uint64_t nq, uint32_t max_mismatches, uint64_t cand_limit);
+int sfx_hamming_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
+                    const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq, uint32_t max_mismatches, uint64_t cand_limit,
+                    uint32_t* d_pattern, uint32_t* d_tpos, uint8_t* d_mism, uint64_t capacity, uint64_t* d_first /* nq + 1, may be NULL */,
+                    uint64_t* cands_out /* host */, uint64_t* count_out /* host */,
+                    void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_index_hamming_dev(const sfx_index* ix,
+                          const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq, uint32_t max_mismatches, uint64_t cand_limit,
+                          uint32_t* d_pattern, uint32_t* d_tpos, uint8_t* d_mism, uint64_t capacity, uint64_t* d_first,
+                          uint64_t* cands_out /* host */, uint64_t* count_out /* host */,
+                          void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_gindex_hamming_dev(const sfx_gindex* gx,
+                           const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq, uint32_t max_mismatches, uint64_t cand_limit,
+                           uint32_t* d_pattern, uint32_t* d_tpos, uint8_t* d_mism, uint64_t capacity, uint64_t* d_first,
+                           uint64_t* cands_out /* host */, uint64_t* count_out /* host */,
+                           void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_index_hamming(const sfx_index* ix, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq, uint32_t max_mismatches,
+                      uint64_t cand_limit, uint32_t* pattern_out, uint32_t* tpos_out, uint8_t* mism_out, uint64_t capacity,
+                      uint64_t* first_out, uint64_t* cands_out, uint64_t* count_out);
+int sfx_gindex_hamming(const sfx_gindex* gx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq, uint32_t max_mismatches,
+                       uint64_t cand_limit, uint32_t* pattern_out, uint32_t* tpos_out, uint8_t* mism_out, uint64_t capacity,
+                       uint64_t* first_out, uint64_t* cands_out, uint64_t* count_out);
 
 /* ---- LCE index: inverse table, LCP range minima, k-mismatch extension -------- */
 /* How far do the suffixes at two positions of the indexed text agree?  T has n bytes, with table sa and lcp as

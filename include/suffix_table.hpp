@@ -8,7 +8,7 @@
 //   new_ / new_naive (doc-hidden upstream, :93-100: the definition, sorted on the host -- the reference's own test oracle,
 //   tests/tests.rs:18-20; never a fallback of new_) / from_parts / into_parts / lcp_lens / table / text / len / is_empty /
 //   suffix / suffix_bytes / contains / positions / any_position,
-// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans, bwt / unbwt, lz77 / unlz, mems,
+// plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans, bwt / unbwt, lz77 / unlz, mems, approx_positions,
 // inverse_table / lce / lcp_range_min and fm_index (class FmIndex below: the same queries from the transform alone).  Errors that are panics
 // in the reference (assert! :380, assert_eq! :117) are std::runtime_error /
 // std::length_error here.  Text is indexed by BYTES (:379).
@@ -202,6 +202,38 @@ public:
         r.tpos.resize((size_t)z);
         r.len.resize((size_t)z);
         return r;
+    }
+    // additive: where does a pattern occur if up to `mismatches` (<= 255) bytes may differ -- Hamming distance, no
+    // insertions or deletions (suffix_hip.h, sfx_index_hamming)?  (position, differing bytes) per occurrence, ascending by
+    // position; an empty pattern has none, a pattern of at most `mismatches` bytes occurs wherever it has room.  The work
+    // grows with the exact hits of the pattern's mismatches + 1 pieces: more than max_candidates of them throw
+    // std::runtime_error naming the count.
+    std::vector<std::pair<uint32_t, uint8_t>> approx_positions(std::string_view query, uint32_t mismatches,
+                                                               uint64_t max_candidates = 1ull << 30) const
+    {
+        if (mismatches > 255 || max_candidates == 0) throw std::invalid_argument("approx_positions: mismatches must be at most 255, max_candidates at least 1");
+        std::vector<std::pair<uint32_t, uint8_t>> out;
+        if (query.empty() || text_.empty()) return out;
+        const uint64_t off[2] = {0, query.size()};
+        std::vector<uint32_t> pat, tpos;
+        std::vector<uint8_t> mism;
+        uint64_t cap = 1024, cands = 0, z = 0;
+        for (int round = 0; round < 2; round++) {                                    // the room is a guess: once more when there were more
+            pat.resize((size_t)cap);
+            tpos.resize((size_t)cap);
+            mism.resize((size_t)cap);
+            check(sfx_index_hamming(index(), reinterpret_cast<const uint8_t*>(query.data()), off, 1, mismatches, max_candidates, pat.data(),
+                                    tpos.data(), mism.data(), cap, nullptr, &cands, &z), "approx_positions");
+            if (cands > max_candidates)
+                throw std::runtime_error("approx_positions: " + std::to_string(cands) + " candidates exceed max_candidates = " +
+                                         std::to_string(max_candidates));
+            if (z <= cap) break;
+            cap = z;
+        }
+        out.resize((size_t)z);
+        for (size_t i = 0; i < out.size(); i++) out[i] = {tpos[i], mism[i]};
+        std::sort(out.begin(), out.end());
+        return out;
     }
     // additive: longest common extensions between two positions of this text (suffix_hip.h, sfx_lce_*).  inverse_table():
     // isa[table()[r]] = r; throws std::runtime_error for a table (from_parts) that is no permutation.  lce(i, j, k): how

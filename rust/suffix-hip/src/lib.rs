@@ -107,6 +107,23 @@ extern "C" {
     fn sfx_mems_dev(d_text: *const u8, n: u64, d_sa: *const u32, d_query: *const u8, m: u64, min_len: u32, flags: u32,
                     pair_limit: u64, d_qpos: *mut u32, d_tpos: *mut u32, d_len: *mut u32, capacity: u64, pairs_out: *mut u64,
                     count_out: *mut u64, d_workspace: *mut c_void, workspace_bytes: u64, stream: *mut c_void) -> c_int;
+    // k-mismatch pattern search (Hamming distance) of a batch of patterns; DeviceIndex::approx_positions below goes through
+    // sfx_index_hamming (host buffers; the outputs may be null at capacity 0, first_out may be null)
+    fn sfx_index_hamming(ix: *const SfxIndex, qbytes: *const u8, qoff: *const u64, nq: u64, max_mismatches: u32,
+                         cand_limit: u64, pattern_out: *mut u32, tpos_out: *mut u32, mism_out: *mut u8, capacity: u64,
+                         first_out: *mut u64, cands_out: *mut u64, count_out: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_hamming_workspace_bytes(nq: u64, max_mismatches: u32, cand_limit: u64) -> u64;
+    #[allow(dead_code)]
+    fn sfx_hamming_dev(d_text: *const u8, n: u64, d_sa: *const u32, d_qbytes: *const u8, d_qoff: *const u64, nq: u64,
+                       max_mismatches: u32, cand_limit: u64, d_pattern: *mut u32, d_tpos: *mut u32, d_mism: *mut u8,
+                       capacity: u64, d_first: *mut u64, cands_out: *mut u64, count_out: *mut u64,
+                       d_workspace: *mut c_void, workspace_bytes: u64, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_index_hamming_dev(ix: *const SfxIndex, d_qbytes: *const u8, d_qoff: *const u64, nq: u64, max_mismatches: u32,
+                             cand_limit: u64, d_pattern: *mut u32, d_tpos: *mut u32, d_mism: *mut u8, capacity: u64,
+                             d_first: *mut u64, cands_out: *mut u64, count_out: *mut u64, d_workspace: *mut c_void,
+                             workspace_bytes: u64, stream: *mut c_void) -> c_int;
     // FM-index over that pair (sfx_fm_*): the size bound; the handle functions take `sfx_fm*`, a type the signature check
     // of this block (tests/test_rust_crate.py) has no mapping for yet, so they are not bound here
     fn sfx_fm_bytes(n: u64, sample_step: u32, occ_step: u32) -> u64;
@@ -408,6 +425,55 @@ impl DeviceIndex {
         r.pairs = pairs;
         Ok(r)
     }
+    /// Additive API: where do `queries` occur in the indexed text if up to `mismatches` (<= 255) bytes may differ?  No
+    /// insertions or deletions.  Per query, in order: `first[j] .. first[j + 1]` are its entries of `tpos` (the window's
+    /// start) and `mism` (the differing bytes of that window, 0 ..= mismatches), ordered by the owning piece of the
+    /// pigeonhole cut and then by table rank -- sort a slice by position if that is what is wanted.  An empty query has
+    /// no occurrence.  `Err(cands)`: the exact hits of the query pieces add up to `cands` > `max_candidates` and nothing
+    /// was compared; use longer queries, fewer mismatches or a larger limit.
+    pub fn approx_positions(&self, queries: &[&[u8]], mismatches: u32, max_candidates: u64) -> Result<ApproxPositions, u64> {
+        assert!(mismatches <= 255 && max_candidates >= 1);
+        let mut off = vec![0u64];
+        let mut blob = Vec::new();
+        for q in queries {
+            blob.extend_from_slice(q);
+            off.push(blob.len() as u64);
+        }
+        let nq = queries.len();
+        let mut cap = (4 * nq).max(1024);
+        let (mut cands, mut count) = (0u64, 0u64);
+        let mut r = ApproxPositions { first: vec![0u64; nq + 1], tpos: Vec::new(), mism: Vec::new(), candidates: 0 };
+        let mut pattern: Vec<u32> = Vec::new();
+        for _ in 0..2 {                                        // the room is a guess: once more when there were more
+            pattern.resize(cap, 0);
+            r.tpos.resize(cap, 0);
+            r.mism.resize(cap, 0);
+            check(unsafe {
+                sfx_index_hamming(self.0, blob.as_ptr(), off.as_ptr(), nq as u64, mismatches, max_candidates,
+                                  pattern.as_mut_ptr(), r.tpos.as_mut_ptr(), r.mism.as_mut_ptr(), cap as u64,
+                                  r.first.as_mut_ptr(), &mut cands, &mut count)
+            }, "sfx_index_hamming");
+            if cands > max_candidates {
+                return Err(cands);
+            }
+            if count as usize <= cap {
+                break;
+            }
+            cap = count as usize;
+        }
+        r.tpos.truncate(count as usize);
+        r.mism.truncate(count as usize);
+        r.candidates = cands;
+        Ok(r)
+    }
+}
+/// The k-mismatch occurrences of a batch of queries (`DeviceIndex::approx_positions`), in CSR form: the occurrences of
+/// query j are the entries `first[j] .. first[j + 1]` of `tpos` / `mism`; `candidates` = the exact piece hits looked at.
+pub struct ApproxPositions {
+    pub first: Vec<u64>,
+    pub tpos: Vec<u32>,
+    pub mism: Vec<u8>,
+    pub candidates: u64,
 }
 /// The maximal exact matches of a query text (`DeviceIndex::mems`): one entry per match, and the number of candidate
 /// pairs the call looked at.

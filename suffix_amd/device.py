@@ -359,6 +359,13 @@ class DeviceIndex:
         return _mems(self._eng, call, "sfx_index_mems_dev", self._text.numel(), query, self._text, min_len, unique, max_pairs,
                      capacity, workspace)
 
+    def hamming(self, qbytes, qoff, mismatches, max_candidates=1 << 30, capacity=None, workspace=None):
+        """As the module's hamming, against the index's text and (checked) table; the pieces are searched through the
+        directory and the key tree (sfx_index_hamming_dev).  Keeps no state in the index: threads may call at once."""
+        call = lambda *tail: self._eng.lib.sfx_index_hamming_dev(self._h, *tail)
+        return _hamming(self._eng, call, "sfx_index_hamming_dev", self._text.numel(), qbytes, qoff, self._text, mismatches,
+                        max_candidates, capacity, workspace)
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
@@ -693,6 +700,71 @@ def mems(text, sa, query, min_len, unique=False, max_pairs=1 << 30, capacity=Non
     return _mems(eng, call, "sfx_mems_dev", n, query, text, min_len, unique, max_pairs, capacity, workspace)
 
 
+def hamming_workspace(nq, mismatches, max_candidates, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_hamming_workspace_bytes(int(nq), int(mismatches), int(max_candidates))), dtype=torch.uint8,
+                       device=device)
+
+
+def _hamming(eng, call, name, n, qbytes, qoff, anchor, mismatches, max_candidates, capacity, workspace):
+    """The checks, buffers and the repeated call every hamming entry shares; call(tail...) -> status."""
+    if qbytes.dtype != torch.uint8 or qbytes.dim() != 1 or not qbytes.is_contiguous():
+        raise TypeError("qbytes must be a contiguous 1-D uint8 tensor")
+    if qoff.dtype != torch.int64 or qoff.dim() != 1 or not qoff.is_contiguous() or qoff.numel() < 1:
+        raise TypeError("qoff must be a contiguous 1-D int64 tensor of nq + 1 offsets")
+    dev = anchor.device
+    if qbytes.device != dev or qoff.device != dev:
+        raise ValueError(f"qbytes and qoff must be on the text's device ({dev})")
+    k, max_candidates = int(mismatches), int(max_candidates)
+    if not 0 <= k <= 255:
+        raise ValueError("mismatches must be in 0 .. 255")
+    if max_candidates < 1:
+        raise ValueError("max_candidates must be at least 1")
+    nq = qoff.numel() - 1
+    max_candidates = min(max_candidates, max(nq * (k + 1) * n, 1))   # (there are no more: keeps the workspace small)
+    if anchor.is_cuda:
+        eng.require_device()
+    if workspace is None:
+        workspace = hamming_workspace(nq, k, max_candidates, dev, eng)
+    first = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    cap = min(max(4 * nq, 1024), max_candidates) if capacity is None else int(capacity)
+    cands, count = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    for _ in range(2):
+        pat, tpos = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(2))
+        mism = torch.empty(cap, dtype=torch.uint8, device=dev)
+        with _on(anchor):
+            eng.check(call(_p(qbytes), _p(qoff), nq, k, max_candidates, _p(pat), _p(tpos), _p(mism), cap, _p(first),
+                           ctypes.byref(cands), ctypes.byref(count), _p(workspace), workspace.numel(), _stream_ptr(anchor)), name)
+        if cands.value > max_candidates:
+            raise SuffixHipError(f"{name}: {cands.value} candidates exceed max_candidates = {max_candidates}; use longer patterns, "
+                                 "fewer mismatches or raise max_candidates")
+        if count.value <= cap or capacity is not None:
+            break
+        cap = int(count.value)
+    z = min(int(count.value), cap)
+    return first, pat[:z].clone(), tpos[:z].clone(), mism[:z].clone(), int(cands.value)
+
+
+def hamming(text, sa, qbytes, qoff, mismatches, max_candidates=1 << 30, capacity=None, workspace=None, engine=None):
+    """Where do the patterns (qbytes uint8, qoff int64 of nq + 1 offsets, as for DeviceIndex.query) occur in (text, sa)
+    if up to `mismatches` (0 .. 255) bytes may differ -- Hamming distance, no insertions or deletions; all tensors on
+    one device.  -> (first, pattern, tpos, mism, candidates): the occurrences of pattern j are the entries
+    first[j] .. first[j + 1] of pattern (uint32 in int32 storage, = j), tpos (likewise: the window's start) and mism
+    (uint8: the differing bytes of the window), ordered by the owning piece of the pigeonhole cut and then by table
+    rank; candidates = the exact piece hits looked at.  More than max_candidates raise SuffixHipError naming the count.
+    The room is guessed and the call repeated once when there were more; with `capacity` it runs once and returns the
+    first `capacity` occurrences (first stays complete).  Runs on the current stream and synchronises it once per call;
+    the table is not checked (sfx_hamming_dev)."""
+    eng = engine or default_engine()
+    _check_u8(text)
+    _check_u32(sa, "sa", text.numel())
+    if sa.device != text.device:
+        raise ValueError(f"sa must be on the text's device ({text.device})")
+    n = text.numel()
+    call = lambda *tail: eng.lib.sfx_hamming_dev(_p(text), n, _p(sa), *tail)
+    return _hamming(eng, call, "sfx_hamming_dev", n, qbytes, qoff, text, mismatches, max_candidates, capacity, workspace)
+
+
 def inverse_table_workspace(n, device, engine=None):
     eng = engine or default_engine()
     return torch.empty(int(eng.lib.sfx_inverse_table_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
@@ -844,6 +916,13 @@ class GeneralizedDeviceIndex:
         call = lambda *tail: self._eng.lib.sfx_gindex_mems_dev(self._h, *tail)
         return _mems(self._eng, call, "sfx_gindex_mems_dev", self._text.numel(), query, self._text, min_len, unique, max_pairs,
                      capacity, workspace)
+
+    def hamming(self, qbytes, qoff, mismatches, max_candidates=1 << 30, capacity=None, workspace=None):
+        """As the module's hamming, against the collection: a window lies inside one document, tpos is a text position
+        (sfx_gindex_hamming_dev)."""
+        call = lambda *tail: self._eng.lib.sfx_gindex_hamming_dev(self._h, *tail)
+        return _hamming(self._eng, call, "sfx_gindex_hamming_dev", self._text.numel(), qbytes, qoff, self._text, mismatches,
+                        max_candidates, capacity, workspace)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

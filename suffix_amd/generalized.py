@@ -15,6 +15,7 @@ no match spans two documents.
     match_stats(query, max_len)   longest match of every suffix of a NEW text inside one document of the collection
     shared_spans(query, min_len)  [(begin, end)] of the query bytes inside such matches of at least min_len bytes
     mems(query, min_len, unique)  the maximal exact matches of a NEW text, each inside one document
+    approx_positions(query, k)    the occurrences with up to k differing bytes, each inside one document
     lce((doc, off), (doc, off), mismatches)   how far two suffixes of the collection agree, never past a document end
 
 Construction and queries run on the GPU through the C ABI (sfx_build_gsa_u32, sfx_gindex_*); there is no CPU
@@ -25,7 +26,7 @@ import ctypes
 import numpy as np
 
 from ._lib import default_engine
-from .table import Mems, _LceHandle, _as_bytes, _match_stats, _mems, _ptr, _repeat_lens, _repeat_spans, _shared_spans
+from .table import Mems, _LceHandle, _approx_positions, _as_bytes, _match_stats, _mems, _ptr, _repeat_lens, _repeat_spans, _shared_spans
 
 _NONE = 0xFFFFFFFF
 
@@ -253,6 +254,18 @@ class GeneralizedSuffixTable:
         d = np.searchsorted(self._starts, tpos.astype(np.uint64), side="right").astype(np.int64) - 1
         off = (tpos.astype(np.int64) - self._starts[d].astype(np.int64)).astype(np.uint32) if tpos.size else tpos.copy()
         return Mems(qpos, tpos, ln, pairs, doc=d.astype(np.uint32), offset=off)
+
+    # -- k-mismatch pattern search ------------------------------------------------------------------
+    def approx_positions_batch(self, queries, mismatches, max_candidates=1 << 30, sort=False):
+        """As SuffixTable.approx_positions_batch, against the collection: a window lies inside ONE document; tpos is a
+        text position doc_starts[doc] + offset."""
+        return _approx_positions(self._eng, self._eng.lib.sfx_gindex_hamming, "sfx_gindex_hamming", self._ensure_index, self.len(),
+                                 queries, mismatches, max_candidates, sort)
+
+    def approx_positions(self, query, mismatches):
+        """(positions, mismatches): text positions ascending and the differing bytes of each window."""
+        _, tpos, mism = self.approx_positions_batch([query], mismatches, sort=True)
+        return tpos, mism
 
     # -- longest common extensions ----------------------------------------------------------------
     def _lce_index(self):

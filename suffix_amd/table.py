@@ -19,6 +19,7 @@ Same method names, argument meaning and error behaviour as the Rust API:
     (none)                                   .repeat_lens(scope) / .repeated_spans(min_len, scope)
     (none)                                   .match_stats(query, max_len) / .shared_spans(query, min_len)
     (none)                                   .mems(query, min_len, unique): the maximal exact matches of a new text
+    (none)                                   .approx_positions(query, mismatches) / .approx_positions_batch: k-mismatch occurrences
     (none)                                   .bwt(sample_step) / suffix_amd.unbwt(bwt, samples, sample_step)
     (none)                                   .fm_index(sample_step) / suffix_amd.FmIndex: the same queries from the transform alone
     (none)                                   .inverse_table() / .lce(i, j, mismatches) / .lce_batch / .lcp_range_min[_batch]
@@ -225,6 +226,44 @@ def _mems(eng, fn, name, index, n, query, min_len, unique, max_pairs):
         cap = int(count.value)
     z = int(count.value)
     return out[0][:z].copy(), out[1][:z].copy(), out[2][:z].copy(), int(pairs.value)
+
+
+def _approx_positions(eng, fn, name, index, n, queries, mismatches, max_candidates, sort):
+    """sfx_index_hamming / sfx_gindex_hamming on host arrays -> (first uint64, tpos uint32, mism uint8).  The first call
+    guesses the room; a second one follows when there were more.  sort: every pattern's slice by position, on the host."""
+    qs = [_as_bytes(q) for q in queries]
+    k, max_candidates = int(mismatches), int(max_candidates)
+    if not 0 <= k <= 255:
+        raise ValueError("mismatches must be in 0 .. 255")
+    if max_candidates < 1:
+        raise ValueError("max_candidates must be at least 1")
+    nq = len(qs)
+    first = np.zeros(nq + 1, dtype=np.uint64)
+    if not nq or not n:
+        return first, np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+    off = np.zeros(nq + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(q) for q in qs], dtype=np.uint64)
+    blob = np.frombuffer(b"".join(qs) or b"\0", dtype=np.uint8)
+    max_candidates = min(max_candidates, nq * (k + 1) * n)          # (there are no more candidates)
+    eng.require_device()
+    cands, count = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    cap = min(max(4 * nq, 1024), max_candidates)
+    for _ in range(2):
+        pat, tpos, mism = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint8)
+        eng.check(fn(index(), _ptr(blob), _ptr(off), nq, k, max_candidates, _ptr(pat), _ptr(tpos), _ptr(mism), cap, _ptr(first),
+                     ctypes.byref(cands), ctypes.byref(count)), name)
+        if cands.value > max_candidates:
+            raise SuffixHipError(f"{name}: {cands.value} candidates exceed max_candidates = {max_candidates}; use longer patterns, "
+                                 "fewer mismatches or raise max_candidates")
+        if count.value <= cap:
+            break
+        cap = int(count.value)
+    z = int(count.value)
+    tpos, mism = tpos[:z].copy(), mism[:z].copy()
+    if sort and z:
+        order = np.lexsort((tpos, pat[:z]))                         # (the patterns ascend already: slices stay in place)
+        tpos, mism = tpos[order], mism[order]
+    return first, tpos, mism
 
 
 def _bwt_step(sample_step):
@@ -571,6 +610,24 @@ class SuffixTable:
         about 25 ms of it, and a buffer of up to 12 bytes per pair for the matches."""
         return Mems(*_mems(self._eng, self._eng.lib.sfx_index_mems, "sfx_index_mems", self._ensure_index, self.len(), query,
                            min_len, unique, max_pairs))
+
+    # -- k-mismatch pattern search ------------------------------------------------------------------
+    def approx_positions_batch(self, queries, mismatches, max_candidates=1 << 30, sort=False):
+        """Where do the queries occur if up to `mismatches` (0 .. 255) bytes may differ (Hamming distance: no insertions
+        or deletions)?  -> (first, tpos, mism): the occurrences of queries[j] are tpos[first[j]:first[j + 1]] (uint32
+        window starts) with mism[...] differing bytes each (uint8).  A slice is ordered by the owning piece of the
+        pigeonhole cut, then by table rank -- at mismatches = 0 it is positions(q) exactly; sort=True orders every slice
+        by position, on the host.  An empty query has no occurrence.
+        The work grows with the exact hits of the k + 1 pieces of every query, the candidates: a call that would look
+        at more than max_candidates raises SuffixHipError naming the count."""
+        return _approx_positions(self._eng, self._eng.lib.sfx_index_hamming, "sfx_index_hamming", self._ensure_index, self.len(),
+                                 queries, mismatches, max_candidates, sort)
+
+    def approx_positions(self, query, mismatches):
+        """(positions, mismatches) of `query` with up to `mismatches` differing bytes: uint32 window starts ascending
+        and the uint8 number of differing bytes of each."""
+        _, tpos, mism = self.approx_positions_batch([query], mismatches, sort=True)
+        return tpos, mism
 
     def __repr__(self):                                              # Debug, :296-312
         lines = ["", "-----------------------------------------", "SUFFIX TABLE",

@@ -3,12 +3,16 @@
 // over the MI355X engine's C++ host mirror (include/suffix_table.hpp -> libsuffix_hip.so),
 // extended into the large-file driver SURVEY.md 8(f) asks for:
 //
-//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--lce I,J[,I,J...] [--mismatches K]] [--isa] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]
+//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q [--mismatches K]]... [--repeats L [--earlier]] [--lce I,J[,I,J...] [--mismatches K]] [--isa] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]
 //
 //   --dump PREFIX   write PREFIX.sa (and PREFIX.lcp with --lcp) as raw little-endian u32
 //                   arrays -- the on-disk form SuffixTable::from_parts (:111-119) reloads
 //   --load PREFIX   skip construction: from_parts(text, PREFIX.sa)
 //   --query Q       positions(Q) (:223-259): prints count and the first few positions
+//   --query Q --mismatches K
+//                   (without --lce) the occurrences of Q with up to K <= 255 differing bytes (Hamming distance) instead of
+//                   the exact ones: "approx_positions("Q", K): Z", then one "position<TAB>mismatches" line per occurrence,
+//                   sorted by position
 //   --repeats L     one "begin end" line per maximal run of bytes that lie inside a repeat of at least L bytes;
 //                   with --earlier only repeats of something EARLIER in the file count (the first copy of everything
 //                   stays out of the report: what a deduplication would keep)
@@ -166,11 +170,13 @@ int main(int argc, char** argv)
         else file = a;
     }
     if (mems > 0 && match.empty()) { fprintf(stderr, "--mems needs --match FILE2\n"); return 1; }
-    if (mismatches_given && lce_pos.empty()) { fprintf(stderr, "--mismatches needs --lce I,J\n"); return 1; }
+    if (mismatches_given && lce_pos.empty() && queries.empty()) { fprintf(stderr, "--mismatches needs --lce I,J or --query Q\n"); return 1; }
+    const bool approx = mismatches_given && lce_pos.empty();            // (with --lce the count belongs to it, and queries stay exact)
+    if (approx && (mismatches > 255 || !fm.empty())) { fprintf(stderr, "--query Q --mismatches K needs K <= 255 and a text, not a transform (--fm)\n"); return 1; }
     if (mems > 0 && min_len_given && lz.empty()) { fprintf(stderr, "--mems L takes its length itself: --min-len belongs to the span report of --match alone\n"); return 1; }
     if (mems < 0 && (unique || max_pairs_given)) { fprintf(stderr, "--unique and --max-pairs need --mems L\n"); return 1; }
     if (file.empty()) {
-        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q]... [--repeats L [--earlier]] [--lce I,J[,I,J...] [--mismatches K]] [--isa] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]\n       suffix-array PREFIX.lz --unlz --out OUT\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
+        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q [--mismatches K]]... [--repeats L [--earlier]] [--lce I,J[,I,J...] [--mismatches K]] [--isa] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]\n       suffix-array PREFIX.lz --unlz --out OUT\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
         return 1;
     }
     std::string text;
@@ -294,7 +300,15 @@ int main(int argc, char** argv)
                 return 1;
             }
         }
-        if (!queries.empty()) {
+        if (approx) {
+            for (const std::string& q : queries) {
+                t0 = std::chrono::steady_clock::now();
+                const auto occ = st.approx_positions(q, (uint32_t)mismatches);
+                if (timing) std::cout << "approx ms: " << ms_since(t0) << "\n";
+                std::cout << "approx_positions(\"" << q << "\", " << mismatches << "): " << occ.size() << "\n";
+                for (const auto& pm : occ) std::cout << pm.first << "\t" << (unsigned)pm.second << "\n";
+            }
+        } else if (!queries.empty()) {
             std::vector<std::string_view> qs(queries.begin(), queries.end());
             auto se = st.positions_batch(qs);
             for (size_t k = 0; k < qs.size(); k++) {
