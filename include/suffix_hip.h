@@ -696,6 +696,56 @@ int sfx_lce_ranks(const sfx_lce* lx, const uint32_t* pos, uint64_t nq, uint32_t*
 int sfx_lce_u32(const uint32_t* sa, const uint32_t* lcp, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs,
                 const uint32_t* a, const uint32_t* b, uint64_t nq, uint32_t max_mismatches, uint32_t* len_out);
 
+/* ---- document counts of every lcp-interval, k-common substrings of a collection ----------
+ * Which strings are shared by many documents?  da, lcp, n, ndocs are a collection's arrays as sfx_build_gsa_u32* writes
+ * them (lcp the in-document one; lcp[0] counts as 0 whatever it holds).  One document is a valid collection.
+ *
+ *   PREV[r]        the largest rank q < r with da[q] == da[r], or none.
+ *   p(r)           for a rank with a PREV: the LARGEST boundary p in (PREV[r], r] with lcp[p] = min lcp(PREV[r], r].
+ *   dup_prefix[x]  the number of ranks r with p(r) <= x (an inclusive prefix sum; it fits 32 bits: at most n - 1).
+ *   For a rank interval [lb, rb] whose inner boundaries (lb, rb] all have lcp >= h while lcp[lb] < h and lcp[rb + 1] < h
+ *   (boundary 0 and boundary n count as below) -- every lcp-interval, and the interval [start, end - 1] of every pattern
+ *   that sfx_gindex_query* reports -- the number of distinct documents among da[lb .. rb] is
+ *       (rb - lb + 1) - (dup_prefix[rb] - dup_prefix[lb]).
+ *   df[p]          that number for the interval boundary p belongs to, [lb[p], rb[p]] of sfx_lcp_intervals_dev; boundary 0
+ *                  and every boundary with lcp[p] == 0 belong to the root: df = the number of non-empty documents.
+ *
+ * sfx_doc_counts_dev writes d_dup_prefix and d_df, n entries each; either may be NULL.  Both are determined bit for bit
+ * by (da, lcp).  It queues on the caller's stream and synchronises it once at the end, for one flag: a da entry >= ndocs
+ * is SFX_ERR_ARG (nothing is read or written out of bounds on the way).  n == 0 succeeds; ndocs == 0 with n > 0 is
+ * SFX_ERR_ARG; n > u32::MAX SFX_ERR_TOO_LARGE.  lcp is not verified: no address depends on a value read from it, so a
+ * foreign lcp gives unspecified values and nothing else.  The workspace may hold anything on entry;
+ * sfx_doc_counts_workspace_bytes(n) <= 34 n + 9 MiB bytes (PREV 4n, two (u64 key, u32 value) arrays 24n, the counts 4n,
+ * the levels of the min-tree n/7, the interval search n/2 + n/15, the radix sort's scratch of 8 MiB + about n/2 and
+ * the scan's partials); a shorter one is SFX_ERR_WORKSPACE.
+ *
+ * k-common substrings: for d in 1 .. ndocs,
+ *   len[d - 1]  the length of the longest string that occurs in at least d distinct documents, 0 if there is none; it
+ *               does not increase with d.  For d >= 2 the maximum of lcp[p] over the boundaries p >= 1 with df[p] >= d;
+ *               for d == 1 the whole documents count too, so it is the longest document's length.
+ *   pos[d - 1]  a text position where that string stands, UINT32_MAX where len is 0: sa[p*] for the smallest boundary
+ *               p* with df[p*] >= d and lcp[p*] == len[d - 1]; for d == 1, if no boundary attains the length, the start
+ *               of the first longest document.
+ * sfx_common_substrings_dev reads sa, lcp, df (n entries, df as sfx_doc_counts_dev writes it; an entry of 0 or above
+ * ndocs is passed over) and doc_starts, and writes ndocs entries of d_len and d_pos.  It synchronises the stream once,
+ * for the check of doc_starts (first 0, never decreasing, none past n: else SFX_ERR_ARG), and returns with its last
+ * kernel queued.  ndocs == 0 is SFX_ERR_ARG unless n == 0; n or ndocs above u32::MAX is SFX_ERR_TOO_LARGE.  The workspace
+ * is sfx_common_substrings_workspace_bytes(ndocs) = 8 ndocs + 1 KiB at most.
+ *
+ * sfx_doc_counts_u32 / sfx_common_substrings_u32: the same over host buffers.
+ *
+ * Not covered: sfx_gindex_query* still counts documents by its linear pass over PREV; the node table of
+ * sfx_suffix_tree_dev for collections; the multi-GPU path. */
+uint64_t sfx_doc_counts_workspace_bytes(uint64_t n);
+int sfx_doc_counts_dev(const uint32_t* d_da, const uint32_t* d_lcp, uint64_t n, uint64_t ndocs, uint32_t* d_dup_prefix /* may be NULL */,
+                       uint32_t* d_df /* may be NULL */, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_doc_counts_u32(const uint32_t* da, const uint32_t* lcp, uint64_t n, uint64_t ndocs, uint32_t* dup_prefix_out, uint32_t* df_out);
+uint64_t sfx_common_substrings_workspace_bytes(uint64_t ndocs);
+int sfx_common_substrings_dev(const uint32_t* d_sa, const uint32_t* d_lcp, const uint32_t* d_df, uint64_t n, const uint64_t* d_doc_starts,
+                              uint64_t ndocs, uint32_t* d_len, uint32_t* d_pos, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_common_substrings_u32(const uint32_t* sa, const uint32_t* lcp, const uint32_t* df, uint64_t n, const uint64_t* doc_starts,
+                              uint64_t ndocs, uint32_t* len_out, uint32_t* pos_out);
+
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the
  * text shard [shard_begin, shard_end).

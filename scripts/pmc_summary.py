@@ -90,6 +90,8 @@ NAMES = [
     ("k_fm_count", "fm_count"), ("k_fm_lookup", "fm_lookup"), ("k_fm_", "fm_build"),
     ("k_lce_check", "lce_check"), ("k_lce_scatter", "lce_scatter"), ("k_lce_verify", "lce_verify"), ("k_lce_levels", "lce_levels"),
     ("k_lce_query", "lce_query"), ("k_lce_range_min", "lce_range_min"), ("k_lce_ranks", "lce_ranks"),
+    ("k_docs_check", "docs_check"), ("k_docs_argmin", "docs_argmin"), ("k_docs_runs", "docs_runs"), ("k_docs_counts", "docs_counts"),
+    ("k_docs_longest", "docs_longest"), ("k_docs_best", "docs_best"), ("k_docs_suffix_max", "docs_suffix_max"),
     ("k_ms_search_dir", "ms_search_dir"), ("k_ms_search", "ms_search"), ("k_ms_gsa_search", "ms_gsa_search"),
     # -- not part of a build's profile: the polled read-back and the memory-system probes
     ("detail::k_post_words", "post_words"), ("k_mb_copy", "mb_copy"), ("k_mb_gather", "mb_gather"), ("k_mb_scatter", "mb_scatter"),

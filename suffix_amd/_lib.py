@@ -153,6 +153,12 @@ ABI = [
     ("sfx_lce_ranks_dev", _int, [_vp, _vp, _u64, _vp, _vp]),
     ("sfx_lce_ranks", _int, [_vp, _vp, _u64, _vp]),
     ("sfx_lce_u32", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u32, _vp]),
+    ("sfx_doc_counts_workspace_bytes", _u64, [_u64]),
+    ("sfx_doc_counts_dev", _int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp]),
+    ("sfx_doc_counts_u32", _int, [_vp, _vp, _u64, _u64, _vp, _vp]),
+    ("sfx_common_substrings_workspace_bytes", _u64, [_u64]),
+    ("sfx_common_substrings_dev", _int, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp]),
+    ("sfx_common_substrings_u32", _int, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),

@@ -14,6 +14,7 @@
 #include "sfx_mem.hip"  // maximal exact matches, likewise
 #include "sfx_hamming.hip"  // k-mismatch pattern search, likewise (over sfx_mem.hip's expansion)
 #include "sfx_lce.hip"  // longest common extensions (inverse table + LCP min-tree), likewise
+#include "sfx_docs.hip"  // document counts per lcp-interval and k-common substrings, likewise (over sfx_lce.hip's levels)
 
 namespace sfx {
 
@@ -1008,6 +1009,79 @@ int sfx_lce_u32(const uint32_t* sa, const uint32_t* lcp, uint64_t n, const uint6
     const int rc = sfx_lce_query(lx, a, b, nq, max_mismatches, len_out);
     sfx_lce_destroy(lx);
     return rc;
+}
+
+// ---- document counts of every lcp-interval, k-common substrings of a collection (include/suffix_hip.h) -------------
+uint64_t sfx_doc_counts_workspace_bytes(uint64_t n) { return doc_counts_workspace_bytes(n); }
+int sfx_doc_counts_dev(const uint32_t* d_da, const uint32_t* d_lcp, uint64_t n, uint64_t ndocs, uint32_t* d_dup_prefix, uint32_t* d_df,
+                       void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    SFX_NEED_U32(d_da, d_lcp, d_dup_prefix, d_df);
+    SFX_NEED_WS(d_workspace, workspace_bytes, doc_counts_workspace_bytes(n));
+    return doc_counts_dev(d_da, d_lcp, n, ndocs, d_dup_prefix, d_df, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sfx_doc_counts_u32(const uint32_t* da, const uint32_t* lcp, uint64_t n, uint64_t ndocs, uint32_t* dup_prefix_out, uint32_t* df_out)
+{
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (ndocs == 0 || !da || !lcp) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    const uint64_t wsb = doc_counts_workspace_bytes(n), bytes = n * sizeof(uint32_t);
+    DevBuf dd, dl, dp, df, dw;
+    SFX_TRY(dd.alloc(bytes));
+    SFX_TRY(dl.alloc(bytes));
+    if (dup_prefix_out) SFX_TRY(dp.alloc(bytes));
+    if (df_out) SFX_TRY(df.alloc(bytes));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    SFX_HIP(hipMemcpyAsync(dd.p, da, bytes, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dl.p, lcp, bytes, hipMemcpyHostToDevice, st));
+    SFX_TRY(doc_counts_dev((const uint32_t*)dd.p, (const uint32_t*)dl.p, n, ndocs, (uint32_t*)dp.p, (uint32_t*)df.p, dw.p, wsb, st));
+    if (dup_prefix_out) SFX_HIP(hipMemcpyAsync(dup_prefix_out, dp.p, bytes, hipMemcpyDeviceToHost, st));
+    if (df_out) SFX_HIP(hipMemcpyAsync(df_out, df.p, bytes, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+uint64_t sfx_common_substrings_workspace_bytes(uint64_t ndocs) { return common_substrings_workspace_bytes(ndocs); }
+int sfx_common_substrings_dev(const uint32_t* d_sa, const uint32_t* d_lcp, const uint32_t* d_df, uint64_t n, const uint64_t* d_doc_starts,
+                              uint64_t ndocs, uint32_t* d_len, uint32_t* d_pos, void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    SFX_NEED_U32(d_sa, d_lcp, d_df, d_len, d_pos);
+    SFX_NEED_U64(d_doc_starts);
+    SFX_NEED_WS(d_workspace, workspace_bytes, common_substrings_workspace_bytes(ndocs));
+    return common_substrings_dev(d_sa, d_lcp, d_df, n, d_doc_starts, ndocs, d_len, d_pos, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sfx_common_substrings_u32(const uint32_t* sa, const uint32_t* lcp, const uint32_t* df, uint64_t n, const uint64_t* doc_starts,
+                              uint64_t ndocs, uint32_t* len_out, uint32_t* pos_out)
+{
+    if (n > 0xFFFFFFFFull || ndocs > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (ndocs == 0) return n ? SFX_ERR_ARG : SFX_OK;
+    if (!doc_starts || !len_out || !pos_out || (n && (!sa || !lcp || !df))) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    const uint64_t wsb = common_substrings_workspace_bytes(ndocs), bytes = n * sizeof(uint32_t);
+    DevBuf ds, dl, dd, dt, dn, dp, dw;
+    SFX_TRY(ds.alloc(bytes));
+    SFX_TRY(dl.alloc(bytes));
+    SFX_TRY(dd.alloc(bytes));
+    SFX_TRY(dt.alloc(ndocs * sizeof(uint64_t)));
+    SFX_TRY(dn.alloc(ndocs * sizeof(uint32_t)));
+    SFX_TRY(dp.alloc(ndocs * sizeof(uint32_t)));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    if (n) {
+        SFX_HIP(hipMemcpyAsync(ds.p, sa, bytes, hipMemcpyHostToDevice, st));
+        SFX_HIP(hipMemcpyAsync(dl.p, lcp, bytes, hipMemcpyHostToDevice, st));
+        SFX_HIP(hipMemcpyAsync(dd.p, df, bytes, hipMemcpyHostToDevice, st));
+    }
+    SFX_HIP(hipMemcpyAsync(dt.p, doc_starts, ndocs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(common_substrings_dev((const uint32_t*)ds.p, (const uint32_t*)dl.p, (const uint32_t*)dd.p, n, (const uint64_t*)dt.p, ndocs,
+                                  (uint32_t*)dn.p, (uint32_t*)dp.p, dw.p, wsb, st));
+    SFX_HIP(hipMemcpyAsync(len_out, dn.p, ndocs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipMemcpyAsync(pos_out, dp.p, ndocs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
 }
 
 // ---- LZ77 factorization from the EARLIER repeat lengths, and its decoder (include/suffix_hip.h) -----------------

@@ -506,6 +506,14 @@ void lce_destroy(sfx_lce* lx);
 int lce_query_dev(const sfx_lce* lx, const uint32_t* d_a, const uint32_t* d_b, uint64_t nq, uint32_t k, uint32_t* d_len, hipStream_t st);
 int lce_range_min_dev(const sfx_lce* lx, const uint32_t* d_lo, const uint32_t* d_hi, uint64_t nq, uint32_t* d_min, hipStream_t st);
 int lce_ranks_dev(const sfx_lce* lx, const uint32_t* d_pos, uint64_t nq, uint32_t* d_rank, hipStream_t st);
+// document counts of every lcp-interval and the k-common substrings of a collection (sfx_docs.hip); both synchronise the
+// stream once, for their flag
+uint64_t doc_counts_workspace_bytes(uint64_t n);
+int doc_counts_dev(const uint32_t* d_da, const uint32_t* d_lcp, uint64_t n, uint64_t ndocs, uint32_t* d_dup, uint32_t* d_df, void* ws,
+                   uint64_t ws_bytes, hipStream_t st);
+uint64_t common_substrings_workspace_bytes(uint64_t ndocs);
+int common_substrings_dev(const uint32_t* d_sa, const uint32_t* d_lcp, const uint32_t* d_df, uint64_t n, const uint64_t* d_starts,
+                          uint64_t ndocs, uint32_t* d_len, uint32_t* d_pos, void* ws, uint64_t ws_bytes, hipStream_t st);
 // bucket directory of the resident index (sfx_query.hip)
 int dir_shape(uint64_t n, int bits, int* k_out, int* dbits_out, uint64_t* entries_out);
 uint64_t dir_scratch_words(uint64_t entries);
@@ -547,6 +555,9 @@ int lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_
                       uint32_t* d_leaf_parent, void* ws, uint64_t ws_bytes, hipStream_t st);
 int doc_lookup_dev(const uint32_t* d_pos, uint64_t count, const uint64_t* d_starts, uint64_t ndocs, uint32_t* d_doc,
                    uint32_t* d_offset, hipStream_t st);
+// lb, rb and node of lcp_intervals_dev without the parents: the same workspace
+int lcp_interval_bounds_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_t* d_rb, uint32_t* d_node, void* ws,
+                            uint64_t ws_bytes, hipStream_t st);
 // node table with ordered children (sfx_tree.hip); synchronises the stream once for the counts
 uint64_t suffix_tree_workspace_bytes(uint64_t n);
 int suffix_tree_dev(const uint8_t* d_text, const uint32_t* d_sa, const uint32_t* d_lcp, uint64_t n, uint64_t node_capacity,
@@ -562,6 +573,9 @@ uint64_t gindex_workspace_bytes(uint64_t n);
 // checks doc_starts and every (table, DA) entry (*bad_out), then PREV[r] = the previous rank of the same document
 int gindex_build_dev(const uint64_t* d_starts, uint64_t ndocs, uint64_t n, const uint32_t* d_sa, const uint32_t* d_da,
                      uint32_t* d_prev, void* ws, uint64_t ws_bytes, hipStream_t st, bool* bad_out);
+// PREV alone (no checks): (K0, V0) / (K1, V1) are n entries each of scratch, radix_scratch as for the sorts
+int gsa_prev_dev(const uint32_t* d_da, uint64_t n, uint64_t ndocs, uint32_t* d_prev, uint64_t* K0, uint32_t* V0, uint64_t* K1, uint32_t* V1,
+                 uint32_t* radix_scratch, hipStream_t st);
 uint64_t gindex_query_scratch_bytes(uint64_t nq);
 int gindex_query_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, const uint32_t* d_sa,
                      const uint32_t* d_da, const uint32_t* d_prev, const uint8_t* d_q, const uint64_t* d_qoff, uint64_t nq,

@@ -305,12 +305,13 @@ uint64_t lcp_intervals_workspace_bytes(uint64_t n)
     return ((pyramid_words(n) * sizeof(uint32_t) + 255) & ~uint64_t(255)) + 256 + open_list_cap(n) * sizeof(uint64_t) + 256;
 }
 
-int lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_t* d_rb, uint32_t* d_node, uint32_t* d_parent,
-                      uint32_t* d_leaf_parent, void* ws, uint64_t ws_bytes, hipStream_t st)
+// lb, rb and node alone (the document counts of sfx_docs.hip need no parents): the same workspace, the same launches
+int lcp_interval_bounds_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_t* d_rb, uint32_t* d_node, void* ws,
+                            uint64_t ws_bytes, hipStream_t st)
 {
     if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
     if (n == 0) return SFX_OK;
-    if (!d_lcp || !d_lb || !d_rb || !d_node || !d_parent || !d_leaf_parent) return SFX_ERR_ARG;
+    if (!d_lcp || !d_lb || !d_rb || !d_node) return SFX_ERR_ARG;
     if (!ws || ws_bytes < lcp_intervals_workspace_bytes(n)) return SFX_ERR_WORKSPACE;
     Pyramid py;
     SFX_TRY(pyramid_build(d_lcp, n, reinterpret_cast<uint32_t*>(ws), "tree_pyramid", st, &py));
@@ -327,6 +328,16 @@ int lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_
         SFX_LAUNCH("tree_intervals_open", 0.0, k_lcp_intervals_open, grid, kBlock, st, py, n, (const uint64_t*)open_list, cap,
                    (const unsigned long long*)open_count, d_lb, d_rb, d_node);
     }
+    return SFX_OK;
+}
+int lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uint32_t* d_rb, uint32_t* d_node, uint32_t* d_parent,
+                      uint32_t* d_leaf_parent, void* ws, uint64_t ws_bytes, hipStream_t st)
+{
+    if (n > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!d_lcp || !d_lb || !d_rb || !d_node || !d_parent || !d_leaf_parent) return SFX_ERR_ARG;
+    SFX_TRY(lcp_interval_bounds_dev(d_lcp, n, d_lb, d_rb, d_node, ws, ws_bytes, st));
+    const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
     SFX_LAUNCH("tree_parents", (double)n * 28, k_tree_parents, grid, kBlock, st, d_lcp, n, (const uint32_t*)d_lb,
                (const uint32_t*)d_rb, (const uint32_t*)d_node, d_parent, d_leaf_parent);
     return SFX_OK;
@@ -855,6 +866,13 @@ int gindex_build_dev(const uint64_t* d_starts, uint64_t ndocs, uint64_t n, const
     }
     *bad_out = bad;
     if (bad) return SFX_OK;
+    return gsa_prev_dev(d_da, n, ndocs, d_prev, K0, V0, K1, V1, scratch, st);
+}
+// PREV alone, for sfx_docs.hip too: (K0, V0) / (K1, V1) n entries each, scratch radix_scratch_words(n).  Only the low
+// bits_for(ndocs - 1) bits of an entry are sorted on, and V holds ranks: an entry >= ndocs (the caller's check) costs nothing
+int gsa_prev_dev(const uint32_t* d_da, uint64_t n, uint64_t ndocs, uint32_t* d_prev, uint64_t* K0, uint32_t* V0, uint64_t* K1, uint32_t* V1,
+                 uint32_t* scratch, hipStream_t st)
+{
     const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
     SFX_LAUNCH("gsa_prev", (double)n * 16, k_gsa_prev_keys, grid, kBlock, st, d_da, n, K0, V0);
     int in1 = 0;

@@ -789,6 +789,63 @@ def inverse_table(sa, out=None, workspace=None, engine=None):
     return out
 
 
+def doc_counts_workspace(n, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_doc_counts_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def doc_counts(da, lcp, ndocs, want_df=True, want_prefix=False, workspace=None, engine=None):
+    """Distinct documents under every lcp-interval of a collection, from the da and lcp of build_gsa (uint32 in int32
+    storage, on one device): df[p] = the document count of the interval boundary p belongs to; dup_prefix, from which
+    the count of any interval [lb, rb] is (rb - lb + 1) - (dup_prefix[rb] - dup_prefix[lb]).  -> df, dup_prefix, or
+    (df, dup_prefix) when both are wanted.  Raises for a da entry >= ndocs; reading that verdict synchronises the
+    current stream.  See include/suffix_hip.h."""
+    eng = engine or default_engine()
+    if not (want_df or want_prefix):
+        raise ValueError("doc_counts: nothing wanted")
+    _check_u32(da, "da")
+    n = da.numel()
+    _check_u32(lcp, "lcp", n)
+    if lcp.device != da.device:
+        raise ValueError(f"all arrays must be on one device ({da.device})")
+    if da.is_cuda:
+        eng.require_device()
+    df = torch.empty(n, dtype=torch.int32, device=da.device) if want_df else None
+    dup = torch.empty(n, dtype=torch.int32, device=da.device) if want_prefix else None
+    if workspace is None:
+        workspace = doc_counts_workspace(n, da.device, eng)
+    with _on(da):
+        eng.check(eng.lib.sfx_doc_counts_dev(_p(da), _p(lcp), n, int(ndocs), _p(dup), _p(df), _p(workspace), workspace.numel(),
+                                             _stream_ptr(da)), "sfx_doc_counts_dev")
+    return (df, dup) if want_df and want_prefix else df if want_df else dup
+
+
+def common_substrings(sa, lcp, df, doc_starts, engine=None):
+    """The longest strings common to at least d documents, d = 1 .. ndocs, from the sa and lcp of build_gsa, the df of
+    doc_counts and doc_starts (int64): -> (len, pos), ndocs entries each (uint32 in int32 storage); pos is a text
+    position, 0xFFFFFFFF where len is 0.  Synchronises the current stream once.  See include/suffix_hip.h."""
+    eng = engine or default_engine()
+    _check_u32(sa, "sa")
+    n = sa.numel()
+    _check_u32(lcp, "lcp", n)
+    _check_u32(df, "df", n)
+    if doc_starts.dtype != torch.int64 or doc_starts.dim() != 1 or not doc_starts.is_contiguous():
+        raise TypeError("doc_starts must be a contiguous 1-D int64 tensor")
+    for t in (lcp, df, doc_starts):
+        if t.device != sa.device:
+            raise ValueError(f"all arrays must be on one device ({sa.device})")
+    nd = doc_starts.numel()
+    if sa.is_cuda:
+        eng.require_device()
+    ln = torch.empty(nd, dtype=torch.int32, device=sa.device)
+    pos = torch.empty(nd, dtype=torch.int32, device=sa.device)
+    ws = torch.empty(int(eng.lib.sfx_common_substrings_workspace_bytes(nd)), dtype=torch.uint8, device=sa.device)
+    with _on(sa):
+        eng.check(eng.lib.sfx_common_substrings_dev(_p(sa), _p(lcp), _p(df), n, _p(doc_starts), nd, _p(ln), _p(pos), _p(ws), ws.numel(),
+                                                    _stream_ptr(sa)), "sfx_common_substrings_dev")
+    return ln, pos
+
+
 class LceDeviceIndex:
     """Longest common extensions between positions of the indexed text, from the device tensors (sa, lcp) of `build_sa_lcp`
     -- or of `build_gsa` with its `doc_starts` (int64), where no extension passes a document end (sfx_lce_create_dev).

@@ -10,6 +10,10 @@ no match spans two documents.
     lcp_lens()       common prefix of neighbouring truncated suffixes (0 first)
     positions(q)     [(doc, offset)] of every occurrence of q, in table order
     documents(q)     sorted distinct documents containing q; document_frequency(q) = their number
+    document_counts()             distinct documents under every lcp-interval (per boundary of the table)
+    interval_document_frequency(start, end)   the same for any pattern's rank interval, from two prefix sums
+    common_substring_lengths()    the longest string common to at least d documents, for every d
+    longest_common_substring(min_docs)        the bytes of one, and in how many documents they occur
     repeat_lens(scope)            longest repeat starting at every position: anywhere, earlier, or in another document
     repeated_spans(min_len, ...)  [(document, begin_offset, end_offset)] of the bytes inside such repeats
     match_stats(query, max_len)   longest match of every suffix of a NEW text inside one document of the collection
@@ -45,6 +49,7 @@ class GeneralizedSuffixTable:
         self._starts = starts
         self._index = None
         self._lce = _LceHandle(self._eng)
+        self._counts = self._common_arrays = None        # (df, dup_prefix) / (len, pos): made on first use
         n = self._tarr.size
         if n > 0xFFFFFFFF:
             raise OverflowError("GeneralizedSuffixTable: more than u32::MAX bytes in all")
@@ -216,6 +221,69 @@ class GeneralizedSuffixTable:
 
     def document_frequency(self, query):
         return int(self.document_frequency_batch([query])[0])
+
+    # -- what the documents share ---------------------------------------------------------------
+    def _doc_counts(self):
+        """(df, dup_prefix), made by the first call that needs them (sfx_doc_counts_u32) and kept."""
+        if self._counts is None:
+            n = self.len()
+            df, dup = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+            if n:
+                self._eng.require_device()
+                self._eng.check(self._eng.lib.sfx_doc_counts_u32(_ptr(self._da), _ptr(self._lcp), n, self._starts.size, _ptr(dup), _ptr(df)),
+                                "sfx_doc_counts_u32")
+            self._counts = (df, dup)
+        return self._counts
+
+    def _common(self):
+        """(len, pos) of sfx_common_substrings_u32, likewise."""
+        if self._common_arrays is None:
+            nd = self._starts.size
+            ln, pos = np.zeros(nd, dtype=np.uint32), np.full(nd, _NONE, dtype=np.uint32)
+            if nd and self.len():
+                df = self.document_counts()
+                self._eng.check(self._eng.lib.sfx_common_substrings_u32(_ptr(self._table), _ptr(self._lcp), _ptr(df), self.len(), _ptr(self._starts),
+                                                                        nd, _ptr(ln), _ptr(pos)), "sfx_common_substrings_u32")
+            self._common_arrays = (ln, pos)
+        return self._common_arrays
+
+    def document_counts(self):
+        """df[p] (uint32, per boundary p between ranks p - 1 and p) = the number of distinct documents among the ranks of
+        the lcp-interval that boundary belongs to; boundary 0 and every boundary of depth 0 give the number of non-empty
+        documents."""
+        return self._doc_counts()[0]
+
+    def interval_document_frequency(self, start, end):
+        """Distinct documents among table()[start:end] for a rank interval as query_batch returns it (all occurrences of
+        one string): two reads of the prefix sums kept with the table.  Scalars or arrays; an empty interval gives 0."""
+        dup = self._doc_counts()[1].astype(np.int64)
+        s, e = np.asarray(start, dtype=np.int64), np.asarray(end, dtype=np.int64)
+        if ((s < 0) | (e > self.len()) | (s > e)).any():
+            raise IndexError("interval_document_frequency: not a rank interval of the table")
+        ok = e > s
+        last, first = np.where(ok, e - 1, 0), np.where(ok, s, 0)
+        out = np.where(ok, (e - s) - (dup[last] - dup[first]) if dup.size else 0, 0)
+        return int(out) if out.ndim == 0 else out.astype(np.uint32)
+
+    def common_substring_lengths(self):
+        """len[d - 1] (uint32, d = 1 .. num_docs()) = the length of the longest string that occurs in at least d distinct
+        documents; 0 where there is none."""
+        return self._common()[0]
+
+    def longest_common_substring(self, min_docs=None):
+        """(bytes, document count) of the longest string that occurs in at least min_docs distinct documents -- None:
+        in every non-empty one.  The count is that of the string itself (>= min_docs).  More documents than there are
+        non-empty ones, or nothing in common: (b"", 0)."""
+        nonempty = sum(1 for d in self._docs if d)
+        k = nonempty if min_docs is None else int(min_docs)
+        if k < 1:
+            raise ValueError("min_docs must be at least 1")
+        ln, pos = self._common()
+        if k > nonempty or not ln[k - 1]:
+            return b"", 0
+        s = self._text[int(pos[k - 1]):int(pos[k - 1]) + int(ln[k - 1])]
+        res = self.query_batch([s])
+        return s, self.interval_document_frequency(int(res["start"][0]), int(res["end"][0]))
 
     # -- repeats --------------------------------------------------------------------------------
     def repeat_lens(self, scope="any", with_source=False):
