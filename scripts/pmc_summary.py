@@ -25,6 +25,7 @@ from collections import defaultdict
 NAMES = [
     # -- device-wide passes (sfx_radix.hip)
     ("k_partition<sfx::SrcText32", "radix_scatter_text_u32"), ("k_partition<sfx::SrcText36", "radix_scatter_text_u32"), ("k_partition<sfx::SrcE64", "radix_scatter_u32"),
+    ("k_partition_text<sfx::SrcText32", "radix_scatter_text_u32"), ("k_partition_text<sfx::SrcText36", "radix_scatter_text_u32"),
     ("k_radix_sweep<sfx::SrcE64", "radix_scatter_u32"), ("k_radix_sweep<sfx::SrcText32", "radix_scatter_text_u32"),
     ("k_radix_sweep<sfx::SrcKV", "radix_scatter_u64"), ("k_radix_sweep<sfx::SrcKeyIota", "radix_scatter_u64"),
     ("k_radix_sweep<sfx::SrcText64", "radix_scatter_text_u64"),

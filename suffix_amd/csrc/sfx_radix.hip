@@ -110,12 +110,12 @@ struct SrcText36 {
         return ((k64 >> (32 - extra)) << (32 - extra)) | (uint64_t)(uint32_t)i;
     }
 };
-// A full tile of a text-fed partition pass without a load per element (round 7).  With SPW = 32 / bits symbols in a packed word
-// (1, 2, 4, 8 bits: kbits == 32) and tiles that begin on word boundaries, thread t takes the tile's positions [KPT t, KPT t + KPT):
-// they start in max(KPT / SPW, 1) consecutive words, and with the word behind those every one of the KPT windows is a shift of two
-// neighbouring registers.  One load of TextTileWords::kCount words per thread and tile -- DNA at KPT = 16: two -- where key()
-// issues KPT eight-byte loads, each a word-index division, and a wave's 64 lanes ask for the same 16 - 24 bytes 64 times.  Which
-// lane ranks which element is free in an unstable pass.
+// A tile of a text-fed partition pass without a load per element (round 7; k_partition_text, round 8).  With SPW = 32 / bits symbols
+// in a packed word (1, 2, 4, 8 bits: kbits == 32) and tiles that begin on word boundaries, thread t takes the tile's positions
+// [KPT t, KPT t + KPT): they start in max(KPT / SPW, 1) consecutive words, and with the word behind those every one of the KPT
+// windows is a shift of two neighbouring registers.  One load of TextTileWords::kCount words per thread and tile -- DNA at
+// KPT = 32: three -- where key() issues KPT eight-byte loads, each a word-index division, and a wave's 64 lanes ask for the same
+// 16 - 24 bytes 64 times.  Which lane ranks which element is free in an unstable pass.
 template <int SPW, int KPT>
 struct TextTileWords {
     static_assert(SPW >= KPT ? SPW % KPT == 0 : KPT % SPW == 0, "a thread's positions begin on a word boundary or stay inside one word");
@@ -128,19 +128,38 @@ struct TextTileWords {
     {
         __builtin_memcpy(w, t.words + (begin / (unsigned)SPW + ((uint64_t)tid * KPT) / (unsigned)SPW), sizeof(w));
     }
-    template <class Src>
-    __device__ __forceinline__ void keys(const Src& src, uint64_t begin, unsigned tid, uint64_t (&key)[KPT]) const
+    // the same for a tile of nvalid < KPT * threads positions (the last of a stretch): word by word, none behind the word that
+    // follows the tile's last position -- at the end of the text that is the first of the spare words; what is not read is 0
+    __device__ __forceinline__ void load_short(const PackedText& t, uint64_t begin, unsigned tid, unsigned nvalid)
+    {
+        const uint64_t q0 = begin / (unsigned)SPW + ((uint64_t)tid * KPT) / (unsigned)SPW;
+        const uint64_t qend = (begin + nvalid - 1u) / (unsigned)SPW + 1u;
+#pragma unroll
+        for (int j = 0; j < kCount; j++) w[j] = q0 + (unsigned)j <= qend ? t.words[q0 + (unsigned)j] : 0u;
+    }
+    // the thread's share of the tile's packed words -> `text` (KPT * threads / SPW words and the one behind them)
+    __device__ __forceinline__ void publish(uint32_t* text, unsigned tid, unsigned threads) const
+    {
+        if (SPW <= KPT || (tid * KPT) % (unsigned)SPW == 0u) {
+#pragma unroll
+            for (int j = 0; j < kOwn; j++) text[(tid * KPT) / (unsigned)SPW + (unsigned)j] = w[j];
+        }
+        if (tid == threads - 1u) text[(threads * KPT) / (unsigned)SPW] = w[kOwn];
+    }
+    // the top 32 bits of the window of the thread's position r: the 32-bit key of its suffix
+    __device__ __forceinline__ uint32_t hi(unsigned tid, int r) const
     {
         constexpr unsigned kBits = 32u / SPW;
-        const unsigned off0 = SPW > KPT ? (tid * KPT) % (unsigned)SPW : 0u;
-#pragma unroll
-        for (int r = 0; r < KPT; r++) {
-            const int j = SPW > KPT ? 0 : r / SPW;
-            const unsigned off = SPW > KPT ? off0 + (unsigned)r : (unsigned)(r % SPW);
-            const uint64_t both = ((uint64_t)w[j] << 32) | (uint64_t)w[j + 1];
-            key[r] = src.from_window(both << (off * kBits), begin + (uint64_t)tid * KPT + (unsigned)r);
-        }
+        const int j = SPW > KPT ? 0 : r / SPW;
+        const unsigned off = SPW > KPT ? (tid * KPT) % (unsigned)SPW + (unsigned)r : (unsigned)(r % SPW);
+        return window_hi(w[j], w[j + 1], off * kBits);
     }
+    // the window of 64 bits of symbols that starts `sh` < 32 bits into word a (b = the word behind it), and its top half
+    static __device__ __forceinline__ uint64_t window(uint32_t a, uint32_t b, unsigned sh)
+    {
+        return (((uint64_t)a << 32) | (uint64_t)b) << sh;
+    }
+    static __device__ __forceinline__ uint32_t window_hi(uint32_t a, uint32_t b, unsigned sh) { return (uint32_t)(window(a, b, sh) >> 32); }
 };
 struct SrcKV {
     static constexpr bool kHasVal = true;
@@ -996,17 +1015,14 @@ struct PartSmem {
 //              bucket = bits [shift, shift + 8) inside top-8 bucket b, cursor[(b << 8) | d].
 // (Ranking: the match masks of the one-sweep pass.  One returning LDS atomic per element was the first version -- the LDS
 // retires about one of them per clock and CU: 8.4 us per 16384-element tile against 4.6 for the masks, lab/partition_lab.hip.)
-// SPW > 0:     (text-fed, SUB = false, 32 / SPW bits per symbol, class_len a multiple of SPW) the full tiles take their elements
-//              through TextTileWords, the words of the workgroup's next tile requested before this one is ranked; a short tile
-//              (the last of a stretch) keeps src.key().
-template <class Src, int KPT, int NW, bool SUB, int SPW = 0>
+// (A text-fed first pass over whole packed words of 1, 2, 4 or 8-bit symbols has a kernel of its own: k_partition_text below.)
+template <class Src, int KPT, int NW, bool SUB>
 __global__ void __launch_bounds__(NW * kWave) SFX_WAVES_PER_EU(4, 4)      // (16 waves per CU: one workgroup of 16, two of 8 or four of 4)
 k_partition(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t* __restrict__ cursor,
             const uint32_t* __restrict__ bstart16, uint64_t class_len)
 {
     constexpr int kThreads = NW * kWave;
     constexpr uint32_t kTile = kThreads * KPT;
-    static_assert(SPW == 0 || (Src::kFromText && !SUB), "the tile loader reads packed text");
     static_assert(kThreads >= kRadix, "thread d owns bucket d");
     static_assert(kWave * KPT >= kRadix, "the match masks must fit the staging buffer");
     static_assert(kTile < 65536, "16-bit tile positions");
@@ -1079,45 +1095,20 @@ k_partition(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t
     };
     // (wave-striped loads, 64 consecutive elements per round; the padding of a short tile carries the largest digit and is
     // ranked behind the real elements of its wave's last rounds: it stays out of the counts and is never stored.  Requesting
-    // the next tile's elements before this one leaves was measured: the 32 registers it takes spill into the ranking loop.
-    // The tile loader's words are another matter: two registers for DNA.  A short tile does not use it: its padding is ranked
-    // behind the real elements only in the wave-striped order.)
-    TextTileWords<SPW ? SPW : KPT, KPT> words = {};
-    auto request = [&](uint64_t v) {                                 // the words of tile v, when it is a full one
-        if constexpr (SPW > 0) {
-            uint64_t begin;
-            unsigned nvalid, top;
-            locate(v, begin, nvalid, top);
-            if (nvalid == kTile) words.load(src.t, begin, tid);
-        }
-    };
-    request(blockIdx.x);
+    // the next tile's elements before this one leaves was measured: the 32 registers it takes spill into the ranking loop.)
     for (uint64_t v = blockIdx.x; v < ntiles; v += gridDim.x) {
         uint64_t begin;
         unsigned nvalid, top;
         locate(v, begin, nvalid, top);
-        if (nvalid == 0u) {                                          // (a stretch or a class with fewer tiles than the largest)
-            request(v + gridDim.x);
-            continue;
-        }
+        if (nvalid == 0u) continue;                                  // (a stretch or a class with fewer tiles than the largest)
         uint64_t key[KPT];
         uint32_t pos[KPT];
-        bool striped = true;
-        if constexpr (SPW > 0) {
-            if (nvalid == kTile) {
-                words.keys(src, begin, tid, key);
-                striped = false;
-            }
-            request(v + gridDim.x);                                  // (in flight while this tile is ranked, staged and stored)
-        }
-        if (striped) {
-            unsigned first = w * (kWave * KPT) + lane;               // (opaque, like t below)
-            SFX_OPAQUE_VGPR(first);
+        unsigned first = w * (kWave * KPT) + lane;                   // (opaque, like t below)
+        SFX_OPAQUE_VGPR(first);
 #pragma unroll
-            for (int r = 0; r < KPT; r++) {
-                const unsigned idx = first + r * kWave;
-                key[r] = idx < nvalid ? src.key(begin + idx) : ~0ull;
-            }
+        for (int r = 0; r < KPT; r++) {
+            const unsigned idx = first + r * kWave;
+            key[r] = idx < nvalid ? src.key(begin + idx) : ~0ull;
         }
 #pragma unroll
         for (int k = 0; k < kRadix / kWave; k++) my_flags[k * kWave + lane] = 0ull;
@@ -1172,6 +1163,206 @@ k_partition(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t
             for (int k = 0; k < NW; k++) s.cnt[k][tid] = 0;
         }
         __syncthreads();
+    }
+}
+
+// ---- the text-fed first partition pass, compact staging (round 8) ------------------------------------------------------------
+// k_partition<text source, .., false> for packed words of 1, 2, 4 or 8-bit symbols (SPW = 32, 16, 8, 4 symbols per word, kbits == 32,
+// stretches that begin on word boundaries, the element's key = the top 32 + extra bits of its window).  An element of such a tile is
+// a pure function of two neighbouring packed words and its position, so it need not exist before it is stored: thread t holds
+// the words of its KPT consecutive positions in registers (TextTileWords) and copies them to LDS once; the ranking takes its
+// digits out of the registers; what is staged at an element's sorted place is its 16-bit tile-local index, and the output loop
+// rebuilds the element from the index and the two words of the LDS copy.  2 bytes of stage per element instead of 8, no
+// uint64_t key[KPT] across the ranking: same output as k_partition -- the same multiset per top-8 bucket and class at the same
+// cursors -- with a stage a quarter the size and 86 - 96 registers for 32 positions.  The short last tile of a stretch takes the same path with
+// its positions >= nvalid kept out of masks, counts and stage (rank_round16_live), its words read one by one (load_short).
+// shift >= 32: the digit is read out of the top half of the window.
+// Geometry, measured on the headline (100 MB of DNA, MI355X; profiles/r8_compact_geometry.jsonl, NOTES_r8.md), positions per thread x
+// workgroups of 8 waves per CU -> kernel time, step: k_partition 16 x 2 (round 7) 289 us, 1.275 ms; this kernel 16 x 2 271, 1.254;
+// 16 x 4 (64 registers) 266, 1.255; 32 x 3 (80 registers) 250, 1.244; 32 x 2 251, 1.238.  Twice the run length pays, more
+// workgroups per CU do not; 32 x 2 needs no scratch at any symbol width (86 - 96 registers, 40 - 54 KiB of LDS), 32 x 3 and
+// 16 x 4 keep up to 56 bytes of loop invariants there.  64 per thread (1 KiB runs) was compiled only: scratch for 1- and 2-bit
+// symbols under 128 registers, 156 - 168 registers (one workgroup per CU) for 4- and 8-bit ones.
+constexpr int kCompactKPT = 32, kCompactPerCU = 2;
+template <int KPT, int NW, int SPW>
+struct CompactSmem {
+    static constexpr int kTile = NW * kWave * KPT;
+    static constexpr int kWords = kTile / SPW + 1;                   // the tile's packed words and the one behind them
+    alignas(8) uint16_t idx[kTile];                                  // (the match masks of the ranking alias its first NW x 2 KiB)
+    uint32_t text[(kWords + 1) & ~1];
+    uint16_t cnt[NW][kRadix];
+    uint32_t off[kRadix];
+    uint32_t part[2][NW];
+};
+// rank_round16 with lanes that take no part (the positions behind a short tile's end)
+__device__ __forceinline__ uint32_t rank_round16_live(unsigned d, bool live, unsigned long long* flags_w, uint16_t* cnt_w, unsigned long long mybit)
+{
+    if (live) atomicOr(&flags_w[d], mybit);
+    wave_sync();
+    const unsigned long long peers = live ? flags_w[d] : 0ull;
+    const uint32_t pre = live ? cnt_w[d] : 0u;
+    wave_sync();
+    const unsigned below = lanes_below(peers);
+    if (live && below == 0) {
+        flags_w[d] = 0ull;
+        cnt_w[d] = (uint16_t)(pre + (uint32_t)__popcll(peers));
+    }
+    wave_sync();
+    return pre + below;
+}
+template <class Src, int KPT, int NW, int SPW, int PER_CU>
+__global__ void __launch_bounds__(NW * kWave) SFX_WAVES_PER_EU(PER_CU * NW / 4, PER_CU * NW / 4)
+k_partition_text(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uint32_t* __restrict__ cursor, uint64_t class_len)
+{
+    constexpr int kThreads = NW * kWave;
+    constexpr uint32_t kTile = kThreads * KPT;
+    constexpr unsigned kBits = 32u / SPW;
+    using Words = TextTileWords<SPW, KPT>;
+    static_assert(Src::kFromText && SPW * kBits == 32u, "whole words of 1, 2, 4 or 8-bit symbols");
+    static_assert(kThreads >= kRadix, "thread d owns bucket d");
+    static_assert(kTile * sizeof(uint16_t) >= NW * kRadix * sizeof(unsigned long long), "the match masks must fit the staging buffer");
+    static_assert(kTile < 65536 && KPT % 4 == 0, "16-bit tile positions, output rounds in fours");
+    __shared__ CompactSmem<KPT, NW, SPW> s;
+    const unsigned tid = threadIdx.x, lane = lane_id(), w = wave_id();
+    const unsigned long long mybit = 1ull << lane;
+    const bool owner = tid < (unsigned)kRadix;
+    const unsigned sh = (unsigned)shift - 32u;
+    unsigned par = 0;
+    unsigned long long* const my_flags = reinterpret_cast<unsigned long long*>(s.idx) + w * kRadix;
+    // (the longest stretch is the first; the last may be short or empty)
+    const uint32_t ntiles = (uint32_t)((dmin<uint64_t>(m, class_len) + kTile - 1) / kTile) * kPartClasses;
+    if (owner) {
+#pragma unroll
+        for (int k = 0; k < NW; k++) s.cnt[k][tid] = 0;
+    }
+    __syncthreads();
+    // tile v = 8 u + x is tile u of stretch x (k_partition, SUB = false)
+    auto locate = [&](uint32_t v, uint64_t& begin, unsigned& nvalid, unsigned& top) {
+        begin = 0;
+        nvalid = 0;
+        top = (unsigned)(v % kPartClasses);
+        if (v >= ntiles) return;
+        const uint64_t p0 = dmin<uint64_t>(m, (uint64_t)top * class_len), p1 = dmin<uint64_t>(m, p0 + class_len);
+        begin = p0 + (uint64_t)(v / kPartClasses) * kTile;
+        if (begin < p1) nvalid = (unsigned)dmin<uint64_t>(kTile, p1 - begin);
+    };
+    // (the words of the workgroup's next tile are requested before this one is ranked: kCount registers)
+    Words cur = {}, nxt = {};
+    auto request = [&](uint32_t v) {
+        uint64_t begin;
+        unsigned nvalid, top;
+        locate(v, begin, nvalid, top);
+        if (nvalid == kTile) nxt.load(src.t, begin, tid);
+        else if (nvalid) nxt.load_short(src.t, begin, tid, nvalid);
+    };
+    request(blockIdx.x);
+    for (uint32_t v = blockIdx.x; v < ntiles; v += gridDim.x) {
+        uint64_t begin;
+        unsigned nvalid, top;
+        locate(v, begin, nvalid, top);
+        cur = nxt;
+        request(v + gridDim.x);                                      // (in flight while this tile is ranked, staged and stored)
+        if (nvalid == 0u) continue;                                  // (a stretch with fewer tiles than the first)
+        auto tile = [&](auto full_tile) {
+            constexpr bool FULL = decltype(full_tile)::value;
+            // (the thread's first position in the tile; opaque, like t below: KPT places and KPT comparisons that do not change
+            // from tile to tile would otherwise be computed before the tile loop and kept)
+            unsigned mine0 = tid * KPT;
+            SFX_OPAQUE_VGPR(mine0);
+            cur.publish(s.text, tid, kThreads);
+#pragma unroll
+            for (int k = 0; k < kRadix / kWave; k++) my_flags[k * kWave + lane] = 0ull;
+            wave_sync();
+            uint32_t pos2[KPT / 2];                                  // ranks, then sorted places: two 16-bit values per register
+#pragma unroll
+            for (int r = 0; r < KPT; r += 2) {
+                uint32_t a, b;
+                if (FULL) {
+                    a = rank_round16((cur.hi(tid, r) >> sh) & 255u, my_flags, s.cnt[w], mybit);
+                    b = rank_round16((cur.hi(tid, r + 1) >> sh) & 255u, my_flags, s.cnt[w], mybit);
+                } else {
+                    a = rank_round16_live((cur.hi(tid, r) >> sh) & 255u, mine0 + (unsigned)r < nvalid, my_flags, s.cnt[w], mybit);
+                    b = rank_round16_live((cur.hi(tid, r + 1) >> sh) & 255u, mine0 + (unsigned)r + 1u < nvalid, my_flags, s.cnt[w], mybit);
+                }
+                // (opaque: the sum and the pair are formed here, not kept apart in four registers until the staging)
+                uint32_t ab = a | (b << 16);
+                SFX_OPAQUE_VGPR(ab);
+                pos2[r / 2] = ab;
+            }
+            __syncthreads();
+            uint32_t tile_ex = 0, mine = 0;
+            {
+                unsigned col = tid;                                  // (opaque: see k_radix_sweep_duo)
+                SFX_OPAQUE_VGPR(col);
+                uint32_t c[NW], tile_count = 0;
+#pragma unroll
+                for (int k = 0; k < NW; k++) {
+                    c[k] = owner ? s.cnt[k][col] : 0u;
+                    tile_count += c[k];
+                }
+                const uint32_t ex = block_scan_excl_1b<NW>(tile_count, s.part, par);
+                if (owner) {
+                    uint32_t run = ex;
+#pragma unroll
+                    for (int k = 0; k < NW; k++) {
+                        s.cnt[k][col] = (uint16_t)run;
+                        run += c[k];
+                    }
+                    tile_ex = ex;
+                    // (the reservation is in flight while the tile is staged)
+                    if (tile_count) mine = atomicAdd(&cursor[(top * kRadix + tid) * kCursorPad], tile_count);
+                }
+            }
+            __syncthreads();
+            SFX_OPAQUE_VGPR(mine0);
+#pragma unroll
+            for (int r = 0; r < KPT; r++) {
+                const unsigned rank = (r & 1) ? (pos2[r / 2] >> 16) : (pos2[r / 2] & 0xFFFFu);
+                const unsigned p = rank + s.cnt[w][(cur.hi(tid, r) >> sh) & 255u];
+                if (FULL || mine0 + (unsigned)r < nvalid) s.idx[p] = (uint16_t)(mine0 + (unsigned)r);
+            }
+            if (owner) s.off[tid] = mine - tile_ex;
+            __syncthreads();
+            // (the thread index, made opaque: see k_partition)
+            unsigned t = tid;
+            SFX_OPAQUE_VGPR(t);
+            constexpr int kOut = 4;
+#pragma unroll
+            for (int r0 = 0; r0 < KPT; r0 += kOut) {
+                unsigned i[kOut];
+                uint32_t a[kOut], b[kOut], dst[kOut];
+#pragma unroll
+                for (int j = 0; j < kOut; j++) {
+                    const unsigned p = (unsigned)(r0 + j) * kThreads + t;
+                    i[j] = (FULL || p < nvalid) ? (unsigned)s.idx[p] : 0u;       // (behind a short tile's end: stale places)
+                }
+#pragma unroll
+                for (int j = 0; j < kOut; j++) {
+                    a[j] = s.text[i[j] / (unsigned)SPW];
+                    b[j] = s.text[i[j] / (unsigned)SPW + 1u];
+                }
+#pragma unroll
+                for (int j = 0; j < kOut; j++) {
+                    const unsigned bit = (i[j] % (unsigned)SPW) * kBits;
+                    dst[j] = s.off[(Words::window_hi(a[j], b[j], bit) >> sh) & 255u] + ((unsigned)(r0 + j) * kThreads + t);
+                }
+#pragma unroll
+                for (int j = 0; j < kOut; j++) {
+                    const unsigned bit = (i[j] % (unsigned)SPW) * kBits;
+                    if (FULL || (unsigned)(r0 + j) * kThreads + t < nvalid)
+                        out[dst[j]] = src.from_window(Words::window(a[j], b[j], bit), begin + i[j]);
+                }
+            }
+            if (owner) {
+                unsigned col = tid;
+                SFX_OPAQUE_VGPR(col);
+#pragma unroll
+                for (int k = 0; k < NW; k++) s.cnt[k][col] = 0;
+            }
+            __syncthreads();
+        };
+        if (nvalid == kTile) tile(std::true_type{});
+        else tile(std::false_type{});
     }
 }
 // ---- hybrid initial sort: two device-wide passes on the top 16 key bits, the rest in LDS ----------
@@ -2025,13 +2216,27 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
                 uint64_t* t = e0; e0 = e1; e1 = t;             // (from here on: e1 = the array grouped by its top 16 bits, e0 = free)
             } else {
                 // (whole words of 1, 2, 4 or 8-bit symbols and stretches that begin on word boundaries -- class_len is a multiple of
-                // 1024 spw by construction: the tile loader; anything else, and the 16- and 4-wave geometries of the tests: src.key())
+                // 1024 spw by construction: k_partition_text; anything else -- 3-bit symbols, the two-symbol key of the tests -- and
+                // the 16- and 4-wave geometries of the tests: k_partition and src.key())
                 const int loader_spw = (kPNw == 8 && text.bits * text.spw == 32 && text.kbits == 32 && !wide_key &&
                                         class_len % (uint64_t)text.spw == 0) ? text.spw : 0;
                 auto text_pass = [&](auto tsrc, auto spw) -> int {
-                    SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0),
-                               (k_partition<decltype(tsrc), kPKpt, kPNw, false, (kPNw == 8 ? decltype(spw)::value : 0)>), g1, kPNw * kWave, st,
-                               tsrc, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
+                    constexpr int kSpw = decltype(spw)::value;
+                    if constexpr (kPNw == 8 && kSpw != 0) {
+                        // (the compact-staging kernel: its own tile and workgroups per CU; a grid that is a multiple of 8 keeps a
+                        // workgroup's tiles in one stretch and on one XCD)
+                        const uint64_t ctile = (uint64_t)kCompactKPT * kPNw * kWave;
+                        const uint64_t tiles = ((dmin<uint64_t>(m, class_len) + ctile - 1) / ctile) * kPartClasses;
+                        unsigned gc = (unsigned)dmin<uint64_t>(tiles, dmin((unsigned)kCompactPerCU * cus, grid_cap()));
+                        if (gc >= kPartClasses) gc -= gc % kPartClasses;
+                        SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0),
+                                   (k_partition_text<decltype(tsrc), kCompactKPT, kPNw, kSpw, kCompactPerCU>), gc, kPNw * kWave, st,
+                                   tsrc, e0, m, top_hi - 8, cursor8, class_len);
+                    } else {
+                        SFX_LAUNCH("radix_scatter_text_u32", (double)m * (text.bits / 8.0 + 8.0),
+                                   (k_partition<decltype(tsrc), kPKpt, kPNw, false>), g1, kPNw * kWave, st,
+                                   tsrc, e0, m, top_hi - 8, cursor8, (const uint32_t*)bins, class_len);
+                    }
                     return SFX_OK;
                 };
                 auto text_pass_of = [&](auto tsrc) -> int {
