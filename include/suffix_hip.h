@@ -82,9 +82,28 @@ int sfx_build_sa_u32_dev(const uint8_t* d_text, uint64_t n, uint32_t* d_sa,
 int sfx_build_sa_u64(const uint8_t* text, uint64_t n, uint64_t* sa_out);
 int sfx_widen_u32_to_u64_dev(const uint32_t* d_in, uint64_t count, uint64_t* d_out, void* stream);
 
-/* The host-pointer entry points keep a few released device buffers in a mutex-guarded pool
- * so that repeated calls on similar sizes skip hipMalloc/hipFree; this returns them. */
+/* The host-pointer entry points keep a few released device buffers (at most 8) in a mutex-guarded pool
+ * so that repeated calls on similar sizes skip hipMalloc/hipFree -- a loop at one size allocates once; this
+ * returns them, and with them the CALLING thread's query scratch (sfx_index_query_dev), after waiting for the
+ * last batch that used it.  What else a thread holds between calls -- one non-blocking stream per device and one
+ * pinned page of 4608 bytes for the small read-backs -- stays until the thread ends: everything a thread holds is
+ * given back when it returns (not at process exit: the library never calls into HIP from exit()). */
 void sfx_release_cached_buffers(void);
+
+/* What the library holds at this moment, process-wide: every device allocation, pinned page, stream and event it
+ * makes is counted where it is made and where it is given back.  Pure host code: works without a device.
+ * device_* / pinned_*: live allocations and their requested sizes (the pool's idle buffers included, reported
+ * again as pooled_*); device_allocs_total only grows: a *_dev call over a caller workspace leaves it unchanged.
+ * The counters are read one by one, not as a snapshot: read them while no other thread is inside the library. */
+typedef struct {
+    uint64_t device_bytes, device_allocs;
+    uint64_t pinned_bytes, pinned_allocs;
+    uint64_t streams, events;
+    uint64_t pooled_bytes, pooled_buffers;   /* the idle part of the pool */
+    uint64_t device_allocs_total;            /* device allocations ever made */
+    uint64_t reserved[7];                    /* zero */
+} sfx_resource_stats_t;
+int sfx_resource_stats(sfx_resource_stats_t* out);
 
 /* ---- lcp_lens (:130-138 -> lcp_lens_quadratic :348-361): LCP array ---------- */
 /* lcp_out[0] = 0, lcp_out[r] = |lcp(text[sa[r-1]..], text[sa[r]..])| in bytes.
@@ -120,7 +139,9 @@ typedef struct sfx_index sfx_index;
  * looks its own first dbits bits up and searches only inside that bucket -- and, memory permitting (17 n
  * bytes), a static 16-ary B+TREE over the first 16 bytes of every suffix in table order: a query of <= 16
  * bytes is answered from its nodes alone, a longer one bisects the ranks that share its first 16 bytes.
- * Batches of >= 4096 queries keep a per-thread scratch list (12 bytes per query) between calls. */
+ * Batches of >= 4096 queries keep a per-thread scratch list (256 + 12 bytes per query of the thread's largest batch,
+ * and one event) between calls: sfx_index_query_dev makes or grows it on the calling thread, and it is given back when
+ * that thread ends or calls sfx_release_cached_buffers() -- the next large batch then allocates it again. */
 int sfx_index_create(const uint8_t* text, uint64_t n, const uint32_t* sa, sfx_index** out);
 /* the same over text and suffix array that already live in HBM (borrowed, not copied: keep them alive and
  * unchanged while the index exists); only the directory and the tree are built.  Queries with device buffers: */

@@ -47,6 +47,14 @@ class FmInfo(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class ResourceStats(ctypes.Structure):
+    _fields_ = [("device_bytes", _u64), ("device_allocs", _u64), ("pinned_bytes", _u64), ("pinned_allocs", _u64), ("streams", _u64),
+                ("events", _u64), ("pooled_bytes", _u64), ("pooled_buffers", _u64), ("device_allocs_total", _u64), ("reserved", _u64 * 7)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
 # every symbol include/suffix_hip.h declares: (name, restype, argtypes)
 ABI = [
     ("sfx_strerror", ctypes.c_char_p, [_int]),
@@ -54,6 +62,7 @@ ABI = [
     ("sfx_last_hip_error", ctypes.c_char_p, []),
     ("sfx_build_sa_u32", _int, [_vp, _u64, _vp]),
     ("sfx_release_cached_buffers", None, []),
+    ("sfx_resource_stats", _int, [ctypes.POINTER(ResourceStats)]),
     ("sfx_build_sa_u64", _int, [_vp, _u64, _vp]),
     ("sfx_widen_u32_to_u64_dev", _int, [_vp, _u64, _vp, _vp]),
     ("sfx_sa_workspace_bytes", _u64, [_u64]),
@@ -244,8 +253,16 @@ class Engine:
         return float(g.value)
 
     def release_cached_buffers(self):
-        """Return the pooled device buffers of the host-pointer entry points to the driver."""
+        """Return the pooled device buffers of the host-pointer entry points, and the calling thread's query scratch, to
+        the driver."""
         self.lib.sfx_release_cached_buffers()
+
+    def resource_stats(self):
+        """What the library holds right now, process-wide (sfx_resource_stats): live device / pinned bytes and allocations,
+        streams, events, the idle part of the pool and the number of device allocations ever made."""
+        s = ResourceStats()
+        self.check(self.lib.sfx_resource_stats(ctypes.byref(s)), "sfx_resource_stats")
+        return s.as_dict()
 
     def profile(self, on):
         self.lib.sfx_profile_enable(1 if on else 0)

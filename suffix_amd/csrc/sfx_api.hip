@@ -4,8 +4,12 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <pthread.h>
+
+#include <atomic>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "sfx_host.hpp"
@@ -52,7 +56,7 @@ void profile_begin(const char* name, hipStream_t st, double algo_bytes)
     ProfRecord r;
     r.name = name;
     r.bytes = algo_bytes;
-    if (hipEventCreate(&r.a) != hipSuccess || hipEventCreate(&r.b) != hipSuccess) return;
+    if (event_create(&r.a) != hipSuccess || event_create(&r.b) != hipSuccess) return;
     (void)hipEventRecord(r.a, st);
     std::lock_guard<std::mutex> lk(g_prof_mu);
     g_prof_open.push_back(r);
@@ -69,8 +73,8 @@ static void profile_fold()
         float ms = 0.f;
         (void)hipEventSynchronize(r.b);
         (void)hipEventElapsedTime(&ms, r.a, r.b);
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
+        (void)event_destroy(r.a);
+        (void)event_destroy(r.b);
         ProfStat* s = nullptr;
         for (ProfStat& t : g_prof_stats) if (t.name == r.name) { s = &t; break; }
         if (!s) { g_prof_stats.push_back(ProfStat{r.name, 0, 0.0, 0.0}); s = &g_prof_stats.back(); }
@@ -79,6 +83,72 @@ static void profile_fold()
         s->bytes += r.bytes;
     }
     g_prof_open.clear();
+}
+
+// ---- resource ledger (sfx_host.hpp's wrappers; sfx_resource_stats) ---------------------------------
+struct ResCounters {
+    std::atomic<uint64_t> device_bytes{0}, device_allocs{0}, pinned_bytes{0}, pinned_allocs{0}, streams{0}, events{0}, device_allocs_total{0};
+};
+static ResCounters g_res;
+// pointer -> bytes of what is live (device and pinned alike: their addresses never coincide).  Never destroyed: a thread
+// that ends while the process exits may still return its buffers.
+static std::mutex& res_mu() { static std::mutex* m = new std::mutex; return *m; }
+static std::unordered_map<void*, uint64_t>& res_sizes() { static auto* t = new std::unordered_map<void*, uint64_t>; return *t; }
+namespace res {
+void note_alloc(void* p, uint64_t bytes, bool pinned)
+{
+    { std::lock_guard<std::mutex> lk(res_mu()); res_sizes()[p] = bytes; }
+    (pinned ? g_res.pinned_bytes : g_res.device_bytes).fetch_add(bytes, std::memory_order_relaxed);
+    (pinned ? g_res.pinned_allocs : g_res.device_allocs).fetch_add(1, std::memory_order_relaxed);
+    if (!pinned) g_res.device_allocs_total.fetch_add(1, std::memory_order_relaxed);
+}
+void note_free(void* p, bool pinned)
+{
+    uint64_t bytes = 0;
+    {
+        std::lock_guard<std::mutex> lk(res_mu());
+        auto it = res_sizes().find(p);
+        if (it == res_sizes().end()) return;          // (not ours: nothing to take off)
+        bytes = it->second;
+        res_sizes().erase(it);
+    }
+    (pinned ? g_res.pinned_bytes : g_res.device_bytes).fetch_sub(bytes, std::memory_order_relaxed);
+    (pinned ? g_res.pinned_allocs : g_res.device_allocs).fetch_sub(1, std::memory_order_relaxed);
+}
+void note_stream(int delta) { g_res.streams.fetch_add((uint64_t)(int64_t)delta, std::memory_order_relaxed); }
+void note_event(int delta) { g_res.events.fetch_add((uint64_t)(int64_t)delta, std::memory_order_relaxed); }
+}  // namespace res
+
+// ---- per-thread state (sfx_host.hpp: ThreadRes) -----------------------------------------------------
+void ThreadRes::release_scratch()
+{
+    for (QueryScratch& sc : scratch) {
+        if (sc.p) {
+            if (sc.used) (void)hipEventSynchronize(sc.done);
+            (void)dev_free(sc.p);
+        }
+        if (sc.done) (void)event_destroy(sc.done);
+        sc = QueryScratch();
+    }
+}
+ThreadRes::~ThreadRes()
+{
+    release_scratch();
+    // (every host-pointer call drains its stream before it returns: nothing is queued on these)
+    for (hipStream_t st : stream) if (st) (void)stream_destroy(st);
+    if (stage) (void)pinned_free(stage);
+}
+static pthread_key_t g_thread_res_key;
+static std::once_flag g_thread_res_once;
+ThreadRes& thread_res()
+{
+    thread_local ThreadRes* t = nullptr;             // (a plain pointer: no destructor of its own, the key's gives the record back)
+    if (!t) {
+        std::call_once(g_thread_res_once, [] { (void)pthread_key_create(&g_thread_res_key, [](void* v) { delete static_cast<ThreadRes*>(v); }); });
+        t = new ThreadRes();
+        (void)pthread_setspecific(g_thread_res_key, t);
+    }
+    return *t;
 }
 
 // ---- device buffers of the host-pointer entry points ----------------------------------
@@ -119,7 +189,7 @@ static void pool_give(void* p, uint64_t bytes, int device)
             g_pool.erase(g_pool.begin());
         }
     }
-    if (evict) (void)hipFree(evict);
+    if (evict) (void)dev_free(evict);
 }
 
 struct DevBuf {
@@ -133,11 +203,11 @@ struct DevBuf {
         (void)hipGetDevice(&device);
         p = pool_take(want, device, &bytes);
         if (p) return SFX_OK;
-        hipError_t e = hipMalloc(&p, want);
+        hipError_t e = dev_malloc(&p, want);
         if (e != hipSuccess) {
             // the pool may be what is in the way: give everything back and retry once
             sfx_release_cached_buffers();
-            e = hipMalloc(&p, want);
+            e = dev_malloc(&p, want);
         }
         if (e != hipSuccess) { note_hip_error(e, "hipMalloc", __FILE__, __LINE__); p = nullptr; return SFX_ERR_HIP; }
         bytes = want;
@@ -155,7 +225,6 @@ struct DevBuf {
 // serialising on the NULL stream ("per-call stream").  nullptr if creation fails.
 // A stream belongs to the device that was current when it was made: one per (thread, device), looked up by the
 // device current NOW (suffix_amd/device.py switches devices per call).
-constexpr int kMaxDevices = 16;
 // -1: the ordinal does not fit the per-device tables (or cannot be told): such a call runs on the NULL stream and without
 // cached scratch -- never on a stream, event or buffer that was made on another device
 static int current_device()
@@ -166,18 +235,17 @@ static int current_device()
 }
 static hipStream_t call_stream()
 {
-    thread_local hipStream_t st[kMaxDevices] = {};
-    thread_local bool tried[kMaxDevices] = {};
     const int d = current_device();
     if (d < 0) return nullptr;
-    if (!tried[d]) {
-        tried[d] = true;
-        if (hipStreamCreateWithFlags(&st[d], hipStreamNonBlocking) != hipSuccess) {
-            st[d] = nullptr;
+    ThreadRes& t = thread_res();
+    if (!t.stream_tried[d]) {
+        t.stream_tried[d] = true;
+        if (stream_create(&t.stream[d], hipStreamNonBlocking) != hipSuccess) {
+            t.stream[d] = nullptr;
             (void)hipGetLastError();
         }
     }
-    return st[d];
+    return t.stream[d];
 }
 // pooled device buffers must not go back to the pool while work that uses them may still be queued
 struct StreamDrain {
@@ -256,28 +324,28 @@ static int index_build_directory(sfx_index* ix, hipStream_t st)
 {
     if (ix->n == 0) return SFX_OK;
     void* small = nullptr;
-    SFX_HIP(hipMalloc(&small, 4096));
+    SFX_HIP(dev_malloc(&small, 4096));
     unsigned long long bins[256];
     int rc = byte_presence_host(ix->d_text, ix->n, small, bins, st);
-    (void)hipFree(small);
+    (void)dev_free(small);
     if (rc != SFX_OK) return rc;
     uint16_t lut[256];
     unsigned sigma = 0;
     for (int c = 0; c < 256; c++) lut[c] = bins[c] ? (uint16_t)(++sigma) : (uint16_t)0;
     ix->bits = bits_for(sigma > 1 ? sigma - 1 : 1);
     SFX_TRY(dir_shape(ix->n, ix->bits, &ix->k, &ix->dbits, &ix->entries));
-    SFX_HIP(hipMalloc((void**)&ix->d_dir, ix->entries * sizeof(uint32_t)));
-    SFX_HIP(hipMalloc((void**)&ix->d_lut, 256 * sizeof(uint16_t)));
+    SFX_HIP(dev_malloc((void**)&ix->d_dir, ix->entries * sizeof(uint32_t)));
+    SFX_HIP(dev_malloc((void**)&ix->d_lut, 256 * sizeof(uint16_t)));
     uint32_t* scratch = nullptr;
-    SFX_HIP(hipMalloc((void**)&scratch, (dir_scratch_words(ix->entries) + 2) * sizeof(uint32_t)));
+    SFX_HIP(dev_malloc((void**)&scratch, (dir_scratch_words(ix->entries) + 2) * sizeof(uint32_t)));
     uint64_t bad = 0;
     rc = dir_build_dev(ix->d_text, ix->n, ix->d_sa, lut, ix->bits, ix->k, ix->dbits, ix->entries, ix->d_lut, ix->d_dir, scratch, st, &bad);
-    (void)hipFree(scratch);
+    (void)dev_free(scratch);
     if (rc != SFX_OK) return rc;
     if (bad) return SFX_ERR_ARG;
     // SFX_INDEX_TREE=0 (development): directory only
     static const bool want_tree = [] { const char* e = dev_env("SFX_INDEX_TREE"); return !e || atoi(e) != 0; }();
-    if (want_tree && hipMalloc((void**)&ix->d_tree, key_tree_words(ix->n) * sizeof(uint64_t)) == hipSuccess) {
+    if (want_tree && dev_malloc((void**)&ix->d_tree, key_tree_words(ix->n) * sizeof(uint64_t)) == hipSuccess) {
         rc = key_tree_build_dev(ix->d_text, ix->n, ix->d_sa, ix->d_tree, ix->tree_off, &ix->tree_levels, st);
         if (rc != SFX_OK) return rc;
         // the index is handed to callers who will query it on OTHER streams: the tree must be complete, not queued
@@ -462,8 +530,8 @@ int sfx_index_create(const uint8_t* text, uint64_t n, const uint32_t* sa, sfx_in
             return false;
         };
         do {
-            if (!hip_ok(hipMalloc((void**)&ix->d_text, n), "hipMalloc(text)") ||
-                !hip_ok(hipMalloc((void**)&ix->d_sa, n * sizeof(uint32_t)), "hipMalloc(sa)")) break;
+            if (!hip_ok(dev_malloc((void**)&ix->d_text, n), "text buffer") ||
+                !hip_ok(dev_malloc((void**)&ix->d_sa, n * sizeof(uint32_t)), "table buffer")) break;
             if (!hip_ok(hipMemcpyAsync(ix->d_text, text, n, hipMemcpyHostToDevice, st), "H2D text")) break;
             if (sa) {
                 if (!hip_ok(hipMemcpyAsync(ix->d_sa, sa, n * sizeof(uint32_t), hipMemcpyHostToDevice, st), "H2D sa")) break;
@@ -521,23 +589,22 @@ int sfx_index_query_dev(const sfx_index* ix, const uint8_t* d_qbytes, const uint
         // (Answering large batches in the order of their first 8 bytes, so that neighbouring lanes share tree nodes and probes,
         // was measured on config 5's 10^6 queries: the search kernel 1.39 -> 1.23 ms, the 8-pass sort of the (key, query) pairs
         // 0.24 ms -- not worth it.)
-        // scratch of phase 2 (the list of queries that go on), kept across calls per (thread, device): no
+        // scratch of phase 2 (the list of queries that go on), kept across calls per (thread, device) in the thread's
+        // ThreadRes -- given back when the thread ends or calls sfx_release_cached_buffers(): no
         // allocation and no host synchronisation on the hot path.  The previous batch may still be using it on another
         // stream (whose handle may be gone by now): it left an EVENT behind, and this batch's stream waits on that -- on
         // the device.  Without scratch the batch is answered in one phase.
-        struct QueryScratch { void* p = nullptr; uint64_t bytes = 0; hipEvent_t done = nullptr; bool used = false; };
-        thread_local QueryScratch scs[kMaxDevices];
         const int dev = current_device();
         QueryScratch none;
-        QueryScratch& sc = dev >= 0 ? scs[dev] : none;
+        QueryScratch& sc = dev >= 0 ? thread_res().scratch[dev] : none;
         void* os = nullptr;
         if (dev >= 0 && nq >= query_two_phase_min()) {
             const uint64_t need = query_scratch_bytes(nq);
-            if (!sc.done && hipEventCreateWithFlags(&sc.done, hipEventDisableTiming) != hipSuccess) { sc.done = nullptr; (void)hipGetLastError(); }
+            if (!sc.done && event_create(&sc.done, hipEventDisableTiming) != hipSuccess) { sc.done = nullptr; (void)hipGetLastError(); }
             if (sc.done) {
                 if (sc.bytes < need) {
-                    if (sc.p) { if (sc.used) (void)hipEventSynchronize(sc.done); (void)hipFree(sc.p); sc.p = nullptr; sc.bytes = 0; sc.used = false; }
-                    if (hipMalloc(&sc.p, need) == hipSuccess) sc.bytes = need; else { sc.p = nullptr; (void)hipGetLastError(); }
+                    if (sc.p) { if (sc.used) (void)hipEventSynchronize(sc.done); (void)dev_free(sc.p); sc.p = nullptr; sc.bytes = 0; sc.used = false; }
+                    if (dev_malloc(&sc.p, need) == hipSuccess) sc.bytes = need; else { sc.p = nullptr; (void)hipGetLastError(); }
                 }
                 if (sc.p) {
                     if (sc.used) (void)hipStreamWaitEvent((hipStream_t)stream, sc.done, 0);
@@ -559,12 +626,12 @@ void sfx_index_destroy(sfx_index* ix)
 {
     if (!ix) return;
     if (ix->owns_arrays) {
-        if (ix->d_text) (void)hipFree(ix->d_text);
-        if (ix->d_sa) (void)hipFree(ix->d_sa);
+        if (ix->d_text) (void)dev_free(ix->d_text);
+        if (ix->d_sa) (void)dev_free(ix->d_sa);
     }
-    if (ix->d_dir) (void)hipFree(ix->d_dir);
-    if (ix->d_tree) (void)hipFree(ix->d_tree);
-    if (ix->d_lut) (void)hipFree(ix->d_lut);
+    if (ix->d_dir) (void)dev_free(ix->d_dir);
+    if (ix->d_tree) (void)dev_free(ix->d_tree);
+    if (ix->d_lut) (void)dev_free(ix->d_lut);
     delete ix;
 }
 
@@ -929,8 +996,8 @@ int sfx_lce_create(const uint32_t* sa, const uint32_t* lcp, uint64_t n, const ui
     {
         StreamDrain drain{st};
         rc = [&]() -> int {
-            SFX_HIP(hipMalloc(&d_lcp, n * sizeof(uint32_t)));                                               // the handle's own level 0
-            if (doc_starts) SFX_HIP(hipMalloc(&d_starts, ndocs * sizeof(uint64_t)));
+            SFX_HIP(dev_malloc(&d_lcp, n * sizeof(uint32_t)));                                               // the handle's own level 0
+            if (doc_starts) SFX_HIP(dev_malloc(&d_starts, ndocs * sizeof(uint64_t)));
             SFX_HIP(hipMemcpyAsync(ds.p, sa, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             SFX_HIP(hipMemcpyAsync(d_lcp, lcp, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             if (doc_starts) SFX_HIP(hipMemcpyAsync(d_starts, doc_starts, ndocs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -938,8 +1005,8 @@ int sfx_lce_create(const uint32_t* sa, const uint32_t* lcp, uint64_t n, const ui
         }();
     }
     if (rc != SFX_OK) {
-        if (d_lcp) (void)hipFree(d_lcp);
-        if (d_starts) (void)hipFree(d_starts);
+        if (d_lcp) (void)dev_free(d_lcp);
+        if (d_starts) (void)dev_free(d_starts);
     }
     return rc;
 }
@@ -1113,19 +1180,28 @@ int sfx_lz77_u32(const uint8_t* text, uint64_t n, const uint32_t* sa, const uint
     if (!text || (capacity && (!len_out || !src_out || !lit_out))) return SFX_ERR_ARG;
     SFX_TRY(check_device());
     if (capacity > n) capacity = n;                                      // (no parse is longer)
-    const uint64_t bytes = n * sizeof(uint32_t), cb = capacity * sizeof(uint32_t);
+    const uint64_t bytes = n * sizeof(uint32_t);
     const uint64_t wsb = dmax(dmax(sa ? (lcp ? 0 : lcp_workspace_bytes(n)) : sa_lcp_workspace_bytes(n),
                                    repeat_lens_workspace_bytes(n, SFX_REP_EARLIER)), lz_parse_workspace_bytes(n));
-    DevBuf dt, ds, dl, dr, dq, db, dn, dp, dc, dw;
+    // (seven buffers, not ten: the pool keeps kPoolMaxBuffers, and a loop at one size is to allocate once -- the phrase
+    // arrays are carved from one)
+    struct Carved { void* p = nullptr; } db, dn, dp, dc;
+    DevBuf dt, ds, dl, dr, dq, dout, dw;
     SFX_TRY(dt.alloc(n));
     SFX_TRY(ds.alloc(bytes));
     SFX_TRY(dl.alloc(bytes));
     SFX_TRY(dr.alloc(bytes));
     SFX_TRY(dq.alloc(bytes));
-    if (begin_out) SFX_TRY(db.alloc(cb));
-    SFX_TRY(dn.alloc(cb));
-    SFX_TRY(dp.alloc(cb));
-    SFX_TRY(dc.alloc(capacity));
+    ArenaSizer osz;
+    for (int i = 0; i < 3; i++) osz.take<uint32_t>(capacity);
+    osz.take<uint8_t>(capacity);
+    SFX_TRY(dout.alloc(osz.used));
+    Arena oa(dout.p, dmax<uint64_t>(osz.used, 1));
+    db.p = oa.take<uint32_t>(capacity);
+    dn.p = oa.take<uint32_t>(capacity);
+    dp.p = oa.take<uint32_t>(capacity);
+    dc.p = oa.take<uint8_t>(capacity);
+    if (oa.overflow) return SFX_ERR_INTERNAL;
     SFX_TRY(dw.alloc(wsb));
     hipStream_t st = call_stream();
     StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
@@ -1620,8 +1696,8 @@ int sfx_gindex_create_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_d
     if (n) {
         hipStream_t st = (hipStream_t)stream;
         do {
-            hipError_t e = hipMalloc((void**)&gx->d_prev, n * sizeof(uint32_t));
-            if (e != hipSuccess) { note_hip_error(e, "hipMalloc(prev)", __FILE__, __LINE__); gx->d_prev = nullptr; rc = SFX_ERR_HIP; break; }
+            hipError_t e = dev_malloc((void**)&gx->d_prev, n * sizeof(uint32_t));
+            if (e != hipSuccess) { note_hip_error(e, "prev buffer", __FILE__, __LINE__); gx->d_prev = nullptr; rc = SFX_ERR_HIP; break; }
             DevBuf dw;
             const uint64_t wsb = gindex_workspace_bytes(n);
             rc = dw.alloc(wsb);
@@ -1654,7 +1730,7 @@ int sfx_gindex_create(const uint8_t* text, uint64_t n, const uint64_t* doc_start
     hipStream_t st = call_stream();
     for (int i = 0; i < 4 && rc == SFX_OK; i++) {
         if (!bytes[i]) continue;
-        hipError_t e = hipMalloc(&p[i], bytes[i]);
+        hipError_t e = dev_malloc(&p[i], bytes[i]);
         if (e == hipSuccess) e = hipMemcpyAsync(p[i], src[i], bytes[i], hipMemcpyHostToDevice, st);
         if (e != hipSuccess) { note_hip_error(e, "gindex copy", __FILE__, __LINE__); rc = SFX_ERR_HIP; }
     }
@@ -1664,7 +1740,7 @@ int sfx_gindex_create(const uint8_t* text, uint64_t n, const uint64_t* doc_start
                                    st, &gx);
     if (rc != SFX_OK) {
         (void)hipStreamSynchronize(st);
-        for (void* q : p) if (q) (void)hipFree(q);
+        for (void* q : p) if (q) (void)dev_free(q);
         return rc;
     }
     for (int i = 0; i < 4; i++) gx->own[i] = p[i];
@@ -1686,16 +1762,16 @@ int sfx_gindex_query_dev(const sfx_gindex* gx, const uint8_t* d_qbytes, const ui
     sfx_gindex* g = const_cast<sfx_gindex*>(gx);
     std::lock_guard<std::mutex> lk(g->mu);
     const uint64_t need = gindex_query_scratch_bytes(nq);
-    if (!g->done) SFX_HIP(hipEventCreateWithFlags(&g->done, hipEventDisableTiming));
+    if (!g->done) SFX_HIP(event_create(&g->done, hipEventDisableTiming));
     if (g->scratch_bytes < need) {
         if (g->scratch) {
             if (g->used) SFX_HIP(hipEventSynchronize(g->done));
-            (void)hipFree(g->scratch);
+            (void)dev_free(g->scratch);
             g->scratch = nullptr;
             g->scratch_bytes = 0;
             g->used = false;
         }
-        SFX_HIP(hipMalloc(&g->scratch, need));
+        SFX_HIP(dev_malloc(&g->scratch, need));
         g->scratch_bytes = need;
     }
     if (g->used) SFX_HIP(hipStreamWaitEvent(st, g->done, 0));
@@ -1741,10 +1817,10 @@ void sfx_gindex_destroy(sfx_gindex* gx)
 {
     if (!gx) return;
     if (gx->used) (void)hipEventSynchronize(gx->done);
-    if (gx->done) (void)hipEventDestroy(gx->done);
-    if (gx->scratch) (void)hipFree(gx->scratch);
-    if (gx->d_prev) (void)hipFree(gx->d_prev);
-    for (void* p : gx->own) if (p) (void)hipFree(p);
+    if (gx->done) (void)event_destroy(gx->done);
+    if (gx->scratch) (void)dev_free(gx->scratch);
+    if (gx->d_prev) (void)dev_free(gx->d_prev);
+    for (void* p : gx->own) if (p) (void)dev_free(p);
     delete gx;
 }
 
@@ -1806,7 +1882,26 @@ void sfx_release_cached_buffers(void)
         std::lock_guard<std::mutex> lk(g_pool_mu);
         take.swap(g_pool);
     }
-    for (PooledBuf& b : take) (void)hipFree(b.p);
+    for (PooledBuf& b : take) (void)dev_free(b.p);
+    thread_res().release_scratch();                  // the calling thread's phase-2 scratch: the next large batch makes it again
+}
+
+int sfx_resource_stats(sfx_resource_stats_t* out)
+{
+    if (!out) return SFX_ERR_ARG;
+    memset(out, 0, sizeof(*out));
+    const auto rd = [](const std::atomic<uint64_t>& a) { return a.load(std::memory_order_relaxed); };
+    out->device_bytes = rd(g_res.device_bytes);
+    out->device_allocs = rd(g_res.device_allocs);
+    out->pinned_bytes = rd(g_res.pinned_bytes);
+    out->pinned_allocs = rd(g_res.pinned_allocs);
+    out->streams = rd(g_res.streams);
+    out->events = rd(g_res.events);
+    out->device_allocs_total = rd(g_res.device_allocs_total);
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    for (const PooledBuf& b : g_pool) out->pooled_bytes += b.bytes;
+    out->pooled_buffers = g_pool.size();
+    return SFX_OK;
 }
 
 // ---- profiling --------------------------------------------------------------------------------

@@ -500,7 +500,7 @@ static FmView fm_view(const sfx_fm* fm)
 void fm_destroy(sfx_fm* fm)
 {
     if (!fm) return;
-    if (fm->mem) (void)hipFree(fm->mem);
+    if (fm->mem) (void)dev_free(fm->mem);
     delete fm;
 }
 static int fm_build(sfx_fm* fm, const uint8_t* d_bwt, const uint32_t* d_samples, uint32_t occ_step, hipStream_t st, void** tmp_out)
@@ -508,7 +508,7 @@ static int fm_build(sfx_fm* fm, const uint8_t* d_bwt, const uint32_t* d_samples,
     const uint64_t n = fm->n;
     // the alphabet: exact byte counts, read back once (creation needs sigma before it can size the blocks)
     void* tmp = nullptr;
-    SFX_HIP(hipMalloc(&tmp, 4096 + (uint64_t)kMaxGrid * kRadixDev * 4));
+    SFX_HIP(dev_malloc(&tmp, 4096 + (uint64_t)kMaxGrid * kRadixDev * 4));
     *tmp_out = tmp;
     uint64_t* d_bins = (uint64_t*)tmp;
     uint32_t* d_err = (uint32_t*)((char*)tmp + 2048);
@@ -541,7 +541,7 @@ static int fm_build(sfx_fm* fm, const uint8_t* d_bwt, const uint32_t* d_samples,
     fm->T = half >= 1024 ? 64 : half >= 256 ? 16 : half >= 64 ? 4 : 1;
     fm->nload = half / fm->T / 16;
     const FmLayout L = fm_layout(n, fm->nsamples, fm->B, fm->sigp);
-    SFX_HIP(hipMalloc(&fm->mem, L.bytes));
+    SFX_HIP(dev_malloc(&fm->mem, L.bytes));
     fm->bytes = L.bytes;
     char* base = (char*)fm->mem;
     uint32_t* d_hdr = (uint32_t*)(base + L.hdr_off);
@@ -599,7 +599,7 @@ int fm_create_dev(const uint8_t* d_bwt, uint64_t n, const uint32_t* d_samples, u
         rc = fm_build(fm, d_bwt, d_samples, occ_step, st, &tmp);
         if (tmp) {
             (void)hipStreamSynchronize(st);
-            (void)hipFree(tmp);
+            (void)dev_free(tmp);
         }
     }
     if (rc != SFX_OK) {

@@ -30,6 +30,85 @@ void note_hip_error(hipError_t e, const char* what, const char* file, int line);
         if (s_ != SFX_OK) return s_;        \
     } while (0)
 
+// ---- resource ledger -------------------------------------------------------------
+// Every device allocation, pinned page, stream and event of the library is made and given back through these wrappers and
+// nowhere else (tests/test_lifetime_emu.py reads the sources for a raw call).  They keep the counters that
+// sfx_resource_stats() reports: relaxed atomics plus a mutex-guarded pointer -> size table, on allocation paths only --
+// nothing is added to a launch or a read-back, and a *_dev call over a caller workspace still allocates nothing.
+namespace res {
+void note_alloc(void* p, uint64_t bytes, bool pinned);   // (sfx_api.hip)
+void note_free(void* p, bool pinned);
+void note_stream(int delta);
+void note_event(int delta);
+}  // namespace res
+inline hipError_t dev_malloc(void** p, uint64_t bytes)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) res::note_alloc(*p, bytes, false);
+    return e;
+}
+inline hipError_t dev_free(void* p)
+{
+    if (p) res::note_free(p, false);
+    return hipFree(p);
+}
+inline hipError_t pinned_malloc(void** p, uint64_t bytes, unsigned flags)
+{
+    const hipError_t e = hipHostMalloc(p, bytes, flags);
+    if (e == hipSuccess) res::note_alloc(*p, bytes, true);
+    return e;
+}
+inline hipError_t pinned_free(void* p)
+{
+    if (p) res::note_free(p, true);
+    return hipHostFree(p);
+}
+inline hipError_t stream_create(hipStream_t* st, unsigned flags)
+{
+    const hipError_t e = hipStreamCreateWithFlags(st, flags);
+    if (e == hipSuccess) res::note_stream(+1);
+    return e;
+}
+inline hipError_t stream_destroy(hipStream_t st)
+{
+    res::note_stream(-1);
+    return hipStreamDestroy(st);
+}
+inline hipError_t event_create(hipEvent_t* ev)
+{
+    const hipError_t e = hipEventCreate(ev);
+    if (e == hipSuccess) res::note_event(+1);
+    return e;
+}
+inline hipError_t event_create(hipEvent_t* ev, unsigned flags)
+{
+    const hipError_t e = hipEventCreateWithFlags(ev, flags);
+    if (e == hipSuccess) res::note_event(+1);
+    return e;
+}
+inline hipError_t event_destroy(hipEvent_t ev)
+{
+    res::note_event(-1);
+    return hipEventDestroy(ev);
+}
+
+// ---- what a calling thread keeps between calls -------------------------------------
+// One record per thread, made on the thread's first use and given back when the thread ends (a pthread key's destructor:
+// it runs when a thread returns, not when the process exits, so nothing calls into HIP from exit()).
+constexpr int kMaxDevices = 16;
+// phase-2 scratch of sfx_index_query_dev's large batches; `done` is recorded behind the last batch that used it
+struct QueryScratch { void* p = nullptr; uint64_t bytes = 0; hipEvent_t done = nullptr; bool used = false; };
+struct ThreadRes {
+    hipStream_t stream[kMaxDevices] = {};       // call_stream(): the host-pointer entry points' stream, per device
+    bool stream_tried[kMaxDevices] = {};
+    void* stage = nullptr;                      // detail::post_stage(): the pinned page of the read-backs
+    bool stage_tried = false;
+    QueryScratch scratch[kMaxDevices];
+    void release_scratch();                     // waits on `done` first: a batch queued on the caller's stream may still use it
+    ~ThreadRes();
+};
+ThreadRes& thread_res();                        // (sfx_api.hip)
+
 // ---- device workspace carving --------------------------------------------------
 // All device scratch comes from one caller-provided allocation (torch tensor in
 // bench.py, hipMalloc in the host-pointer entry points): nothing is allocated
@@ -161,17 +240,16 @@ constexpr size_t kStage = 4096, kPostArea = 512;
 // without a flush.
 inline void* post_stage()
 {
-    thread_local void* stage = nullptr;
-    thread_local bool tried = false;
-    if (!tried) {
-        tried = true;
-        if (hipHostMalloc(&stage, kStage + kPostArea, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-            stage = nullptr;
+    ThreadRes& t = thread_res();
+    if (!t.stage_tried) {
+        t.stage_tried = true;
+        if (pinned_malloc(&t.stage, kStage + kPostArea, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+            t.stage = nullptr;
             (void)hipGetLastError();
         }
-        if (stage) std::memset(stage, 0, kStage + kPostArea);
+        if (t.stage) std::memset(t.stage, 0, kStage + kPostArea);
     }
-    return stage;
+    return t.stage;
 }
 }  // namespace detail
 inline PostTicket post_ticket()

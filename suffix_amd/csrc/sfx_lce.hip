@@ -454,11 +454,11 @@ static int lce_variant(const sfx_lce* lx)
 void lce_destroy(sfx_lce* lx)
 {
     if (!lx) return;
-    if (lx->mem) (void)hipFree(lx->mem);
-    if (lx->own_lcp) (void)hipFree(lx->own_lcp);
-    if (lx->own_starts) (void)hipFree(lx->own_starts);
+    if (lx->mem) (void)dev_free(lx->mem);
+    if (lx->own_lcp) (void)dev_free(lx->own_lcp);
+    if (lx->own_starts) (void)dev_free(lx->own_starts);
 #ifdef SFX_DEV_HOOKS
-    if (lx->pyr_mem) (void)hipFree(lx->pyr_mem);
+    if (lx->pyr_mem) (void)dev_free(lx->pyr_mem);
 #endif
     delete lx;
 }
@@ -469,7 +469,7 @@ static int lce_build(sfx_lce* lx, const uint32_t* d_sa, hipStream_t st, void* sc
     const uint64_t n = lx->n;
     const LceLayout L = lce_layout(n, lx->fan_log);
     if (!scratch || scratch_bytes < inverse_table_workspace_bytes(n)) return SFX_ERR_WORKSPACE;
-    SFX_HIP(hipMalloc(&lx->mem, L.bytes));
+    SFX_HIP(dev_malloc(&lx->mem, L.bytes));
     lx->bytes = L.bytes;
     lx->levels = L.levels;
     uint32_t* isa = (uint32_t*)lx->mem;
@@ -496,7 +496,7 @@ static int lce_build(sfx_lce* lx, const uint32_t* d_sa, hipStream_t st, void* sc
     }
 #ifdef SFX_DEV_HOOKS
     if (lce_variant_hook() == kLcePyramid) {
-        SFX_HIP(hipMalloc(&lx->pyr_mem, (lcp_pyramid_words(n) + 64) * sizeof(uint32_t)));
+        SFX_HIP(dev_malloc(&lx->pyr_mem, (lcp_pyramid_words(n) + 64) * sizeof(uint32_t)));
         SFX_TRY(lcp_pyramid_build_dev(lx->lcp, n, (uint32_t*)lx->pyr_mem, st, &lx->py));
     }
 #endif

@@ -85,11 +85,11 @@ int microbench(int kind, uint64_t bytes, int param, int param2, int reps, double
     double algo = 0.0;
     const unsigned grid = kMaxGrid;
     do {
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { rc = SFX_ERR_HIP; break; }
+        if (event_create(&e0) != hipSuccess || event_create(&e1) != hipSuccess) { rc = SFX_ERR_HIP; break; }
         // power-of-two element counts so that mb_perm is a bijection
         if (kind == SFX_MB_COPY) {
             const uint64_t n16 = bytes / 16;
-            if (hipMalloc(&a, n16 * 16) != hipSuccess || hipMalloc(&b, n16 * 16) != hipSuccess) { rc = SFX_ERR_HIP; break; }
+            if (dev_malloc(&a, n16 * 16) != hipSuccess || dev_malloc(&b, n16 * 16) != hipSuccess) { rc = SFX_ERR_HIP; break; }
             (void)hipMemsetAsync(a, 1, n16 * 16, st);
             algo = 2.0 * n16 * 16;
             for (int r = -1; r < reps; r++) {
@@ -98,7 +98,7 @@ int microbench(int kind, uint64_t bytes, int param, int param2, int reps, double
             }
         } else if (kind == SFX_MB_SCATTER4) {
             const uint64_t n = 1ull << floor_log2(bytes / 4);
-            if (hipMalloc(&a, n * 4) != hipSuccess) { rc = SFX_ERR_HIP; break; }
+            if (dev_malloc(&a, n * 4) != hipSuccess) { rc = SFX_ERR_HIP; break; }
             algo = 4.0 * n;
             for (int r = -1; r < reps; r++) {
                 if (r == 0) (void)hipEventRecord(e0, st);
@@ -107,7 +107,7 @@ int microbench(int kind, uint64_t bytes, int param, int param2, int reps, double
         } else if (kind == SFX_MB_GATHER1 || kind == SFX_MB_GATHER4) {
             const uint64_t esz = kind == SFX_MB_GATHER1 ? 1 : 4;
             const uint64_t n = 1ull << floor_log2(bytes / esz);
-            if (hipMalloc(&a, n * esz) != hipSuccess || hipMalloc(&b, 256) != hipSuccess) { rc = SFX_ERR_HIP; break; }
+            if (dev_malloc(&a, n * esz) != hipSuccess || dev_malloc(&b, 256) != hipSuccess) { rc = SFX_ERR_HIP; break; }
             (void)hipMemsetAsync(a, 1, n * esz, st);
             algo = (double)esz * n;
             for (int r = -1; r < reps; r++) {
@@ -123,7 +123,7 @@ int microbench(int kind, uint64_t bytes, int param, int param2, int reps, double
             const uint64_t n8 = 1ull << floor_log2(bytes / 8);
             const uint64_t runs = n8 >> log2_L;
             if (runs < 2) { rc = SFX_ERR_ARG; break; }
-            if (hipMalloc(&a, n8 * 8) != hipSuccess || hipMalloc(&b, n8 * 8 + 64) != hipSuccess) { rc = SFX_ERR_HIP; break; }
+            if (dev_malloc(&a, n8 * 8) != hipSuccess || dev_malloc(&b, n8 * 8 + 64) != hipSuccess) { rc = SFX_ERR_HIP; break; }
             (void)hipMemsetAsync(a, 1, n8 * 8, st);
             algo = 16.0 * n8;                                                          // read + write
             for (int r = -1; r < reps; r++) {
@@ -141,10 +141,10 @@ int microbench(int kind, uint64_t bytes, int param, int param2, int reps, double
         if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess || ms <= 0.f) { rc = SFX_ERR_HIP; break; }
         *gbps_out = algo * reps / (ms * 1e-3) / 1e9;
     } while (0);
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    if (a) (void)dev_free(a);
+    if (b) (void)dev_free(b);
+    if (e0) (void)event_destroy(e0);
+    if (e1) (void)event_destroy(e1);
     return rc;
 }
 

@@ -6,6 +6,9 @@
 #include <stdio.h>
 
 #include <chrono>
+#include <mutex>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 dim3 threadIdx, blockIdx, blockDim, gridDim;
@@ -168,14 +171,80 @@ void emu_launch(dim3 grid, dim3 block, const std::function<void()>& body)
 
 // ---- host API --------------------------------------------------------------
 struct emu_event_s { std::chrono::steady_clock::time_point t; };
+struct emu_stream_s { int unused; };
 
-hipError_t hipMalloc(void** p, size_t bytes)
+// The shim's own ledger of what it has handed out (tests/_lifetime.py compares the library's counters with it): every
+// pointer with its size, every stream and event token, and the frees / destroys of something it never gave out.
+namespace {
+struct Ledger {
+    std::mutex mu;
+    std::unordered_map<void*, size_t> device, pinned;
+    std::unordered_set<void*> streams, events;
+    uint64_t device_bytes = 0, pinned_bytes = 0, bad_frees = 0, device_allocs_total = 0;
+};
+Ledger& ledger() { static Ledger* l = new Ledger; return *l; }        // (never destroyed: threads may end during exit)
+
+hipError_t ledger_alloc(void** p, size_t bytes, bool pinned)
 {
     *p = malloc(bytes ? bytes : 1);
-    if (*p) memset(*p, 0xCD, bytes);               // poison: catch reads of uninitialised memory
-    return *p ? hipSuccess : hipErrorOutOfMemory;
+    if (!*p) return hipErrorOutOfMemory;
+    memset(*p, 0xCD, bytes);                       // poison: catch reads of uninitialised memory
+    Ledger& l = ledger();
+    std::lock_guard<std::mutex> lk(l.mu);
+    (pinned ? l.pinned : l.device)[*p] = bytes;
+    (pinned ? l.pinned_bytes : l.device_bytes) += bytes;
+    if (!pinned) l.device_allocs_total++;
+    return hipSuccess;
 }
-hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+hipError_t ledger_free(void* p, bool pinned)
+{
+    if (!p) return hipSuccess;
+    Ledger& l = ledger();
+    {
+        std::lock_guard<std::mutex> lk(l.mu);
+        auto& m = pinned ? l.pinned : l.device;
+        auto it = m.find(p);
+        if (it == m.end()) { l.bad_frees++; return hipErrorInvalidValue; }      // (not freed: it is not ours)
+        (pinned ? l.pinned_bytes : l.device_bytes) -= it->second;
+        m.erase(it);
+    }
+    free(p);
+    return hipSuccess;
+}
+template <class T> hipError_t ledger_make(T** out, std::unordered_set<void*> Ledger::*set)
+{
+    *out = new T();
+    Ledger& l = ledger();
+    std::lock_guard<std::mutex> lk(l.mu);
+    (l.*set).insert(*out);
+    return hipSuccess;
+}
+template <class T> hipError_t ledger_drop(T* tok, std::unordered_set<void*> Ledger::*set)
+{
+    Ledger& l = ledger();
+    {
+        std::lock_guard<std::mutex> lk(l.mu);
+        if (!(l.*set).erase(tok)) { l.bad_frees++; return hipErrorInvalidValue; }
+    }
+    delete tok;
+    return hipSuccess;
+}
+}  // namespace
+
+// out[8]: live device bytes, device allocations, pinned bytes, pinned allocations, streams, events; bad frees and device
+// allocations ever made
+extern "C" void emu_resource_stats(uint64_t* out)
+{
+    Ledger& l = ledger();
+    std::lock_guard<std::mutex> lk(l.mu);
+    out[0] = l.device_bytes; out[1] = l.device.size(); out[2] = l.pinned_bytes; out[3] = l.pinned.size();
+    out[4] = l.streams.size(); out[5] = l.events.size(); out[6] = l.bad_frees; out[7] = l.device_allocs_total;
+}
+
+hipError_t hipMalloc(void** p, size_t bytes) { return ledger_alloc(p, bytes, false); }
+hipError_t hipFree(void* p) { return ledger_free(p, false); }
+hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { return ledger_alloc(p, bytes, true); }
+hipError_t hipHostFree(void* p) { return ledger_free(p, true); }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memmove(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t) { return hipMemcpy(d, s, n, k); }
 hipError_t hipMemset(void* d, int v, size_t n) { if (n) memset(d, v, n); return hipSuccess; }
@@ -187,10 +256,11 @@ const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "hipSucce
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
-hipError_t hipStreamCreate(hipStream_t* st) { *st = nullptr; return hipSuccess; }
-hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = new emu_event_s(); return hipSuccess; }
-hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+// distinct tokens that nothing here dereferences (work on any stream runs at once, on the calling thread)
+hipError_t hipStreamCreate(hipStream_t* st) { return ledger_make(st, &Ledger::streams); }
+hipError_t hipStreamDestroy(hipStream_t st) { return ledger_drop(st, &Ledger::streams); }
+hipError_t hipEventCreate(hipEvent_t* e) { return ledger_make(e, &Ledger::events); }
+hipError_t hipEventDestroy(hipEvent_t e) { return ledger_drop(e, &Ledger::events); }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { e->t = std::chrono::steady_clock::now(); return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b)

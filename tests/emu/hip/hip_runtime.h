@@ -75,8 +75,8 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b);
 template <class T> hipError_t hipMalloc(T** p, size_t bytes) { return hipMalloc((void**)p, bytes); }
 constexpr unsigned hipHostMallocDefault = 0;
 constexpr unsigned hipHostMallocPortable = 1, hipHostMallocMapped = 2, hipHostMallocCoherent = 0x40000000;
-inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned = 0) { return hipMalloc(p, bytes); }
-inline hipError_t hipHostFree(void* p) { return hipFree(p); }
+hipError_t hipHostMalloc(void** p, size_t bytes, unsigned flags = 0);    /* (plain heap, kept apart in the shim's ledger) */
+hipError_t hipHostFree(void* p);
 
 // ---- launch ----------------------------------------------------------------
 void emu_launch(dim3 grid, dim3 block, const std::function<void()>& body);
