@@ -188,6 +188,9 @@ __device__ __forceinline__ uint32_t rank_round16(unsigned d, unsigned long long*
 #else
 #define SFX_OPAQUE_VGPR(x) asm volatile("" : "+v"(x))
 #endif
+// Loads written before this point are issued before it, stores written after it stay after it: a batch of independent loads
+// stays a batch in flight where the scheduler would otherwise pair every load with its store to save registers.  No instruction.
+#define SFX_ISSUE_ORDER() asm volatile("" ::: "memory")
 #ifndef SFX_WAVES_PER_EU
 #define SFX_WAVES_PER_EU(lo, hi) __attribute__((amdgpu_waves_per_eu(lo, hi)))
 #endif

@@ -1395,12 +1395,49 @@ struct H16Zero {
 // wrap when a sub-bucket holds >= 65536 suffixes of this stretch alone -- far beyond what the LDS sort accepts;
 // a wrap changes the sum of all counters by -65535 (low half: its carry lands in the high half) or -65536 (high
 // half), never by 0 in any combination, so the host detects it from the total (!= m) and takes the other route.
+// SPW = 32, 16, 8, 4 (symbols of 1, 2, 4, 8 bits, 32-bit keys: spw == SPW, bits * spw == kbits == 32): a word whose SPW positions
+// all lie below n is swept with constant funnel shifts and no test per position (the runtime form below pays a variable 64-bit
+// shift, a mask and a bound test per LDS atomic: 53 -> 32 us on 100 MB of DNA, round 9); the word that holds position n - 1 is
+// swept position by position.  The same counts by construction: window o of (w0, w1) is (w0 << o bits) | (w1 >> (32 - o bits)).
+// SPW = 0: any packing, everything at run time.
+template <int SPW>
 __global__ void __launch_bounds__(kH16Threads)
 k_hist16_text(PackedText t, int drop, uint64_t words_per_block, uint32_t* __restrict__ partial, H16Zero z)
 {
     z.clear(kH16Threads);
     __shared__ uint32_t h[kH16Words];                                 // 128 KiB
     const unsigned tid = threadIdx.x;
+    if constexpr (SPW != 0) {
+        constexpr unsigned kBits = 32u / (unsigned)SPW;
+        const uint64_t nwords = (t.n + (uint64_t)SPW - 1) / (uint64_t)SPW, nfull = t.n / (uint64_t)SPW;
+        const uint64_t qb = (uint64_t)blockIdx.x * words_per_block;
+        const uint64_t qe = dmin<uint64_t>(nwords, qb + words_per_block);
+        for (unsigned i = tid; i < (unsigned)kH16Words; i += kH16Threads) h[i] = 0;
+        __syncthreads();
+        uint32_t w0 = 0, w1 = 0;
+        if (qb + tid < qe) { w0 = t.words[qb + tid]; w1 = t.words[qb + tid + 1]; }
+        for (uint64_t q = qb + tid; q < qe; q += kH16Threads) {
+            const uint32_t a = w0, b = w1;
+            if (q + kH16Threads < qe) { w0 = t.words[q + kH16Threads]; w1 = t.words[q + kH16Threads + 1]; }
+            if (q < nfull) {
+#pragma unroll
+                for (int o = 0; o < SPW; o++) {
+                    const uint32_t top = (o == 0 ? a : __funnelshift_l(b, a, (unsigned)o * kBits)) >> drop;
+                    atomicAdd(&h[top >> 1], (top & 1u) ? 65536u : 1u);
+                }
+            } else {
+                const unsigned live = (unsigned)(t.n - q * (uint64_t)SPW);           // (the last word: 1 .. SPW - 1 positions)
+                for (unsigned o = 0; o < live; o++) {
+                    const uint32_t top = (o == 0 ? a : __funnelshift_l(b, a, o * kBits)) >> drop;
+                    atomicAdd(&h[top >> 1], (top & 1u) ? 65536u : 1u);
+                }
+            }
+        }
+        __syncthreads();
+        uint32_t* out = partial + (uint64_t)blockIdx.x * kH16Words;
+        for (unsigned i = tid; i < (unsigned)kH16Words; i += kH16Threads) out[i] = h[i];
+        return;
+    }
     const uint64_t nwords = (t.n + (uint64_t)t.spw - 1) / (uint64_t)t.spw;
     const uint64_t qb = (uint64_t)blockIdx.x * words_per_block;
     const uint64_t qe = dmin<uint64_t>(nwords, qb + words_per_block);
@@ -1462,45 +1499,62 @@ k_hist16_e64(const uint64_t* __restrict__ E, uint64_t m, int shift, uint64_t per
 // Everything between the histogram sweep and the first partition pass in ONE launch (round 7; rounds 3-6: a reduction, a
 // one-workgroup scan, a cursor kernel and a one-wave kernel that posted the statistics to the host).
 //   every workgroup  bins[b] += the counts of a slice of the workgroups' partial histograms: workgroup x + 32 y takes the 2048
-//                    bins from 2048 x (4 KB of every partial, one 8-byte load per thread, four rows in flight) and the partials
+//                    bins from 2048 x (4 KB of every partial, one 8-byte load per thread, eight rows in flight) and the partials
 //                    of the y-th of kPartClasses contiguous stretches of `rows_per_class` rows -- the workgroups that counted the
 //                    y-th stretch of the text; a wave's 256 bins are one top-8 bucket, so the sum over a wave is the number of
 //                    suffixes of that stretch in that bucket, class_top8[y * 256 + bucket];
-//   the last one     (to finish: a device-scope ticket) reads the 65536 counts in two halves through the LDS -- 16-byte loads,
-//                    coalesced, where round 3's scan had every lane on a line of its own -- and leaves
-//                      bins[b] = first position of sub-bucket b (in place), bins[65536] = m; cursor16 = the same (the second
-//                      partition pass advances it); cursor8[(x * 256 + j) * kCursorPad] = start of top-8 bucket j + what the
-//                      stretches before x put into it (the first pass's);
-//                      totals_lo[d] = sum over the high digits of bin (j, d), totals_hi[j] = sum over the low digits;
-//                      stat_out = {largest bin, sum of all bins, sub-buckets of more than `cap` suffixes, their suffixes,
-//                      suffixes in sub-buckets of more than `fast`}, posted to the host as well (PostTicket).
-// bins[0 .. 65536) and *ticket are zero on entry.
+//   the last one of a column  (the 8 workgroups x + 32 y of column x take a ticket of the column's) reads the column's 2048
+//                    summed counts back, four consecutive bins per thread in registers, scans them over the workgroup and leaves
+//                      bins[b] = first position of sub-bucket b INSIDE the column (in place);
+//                      totals_hi[j] = sum over the low digits of top-8 bucket j (a wave's 256 bins), its column-local start
+//                      in fin;  the column's row of low-digit sums and its statistics {largest bin, total, sub-buckets of more
+//                      than `cap` suffixes, their suffixes, suffixes in sub-buckets of more than `fast`} in fin;
+//   the last column  (a second ticket, 32 arrivals) scans the 32 column totals and leaves
+//                      bins[b] = first position of sub-bucket b, bins[65536] = m; cursor16 = the same (the second partition
+//                      pass advances it) -- 32 independent 16-byte loads per thread, each plus its column's offset;
+//                      cursor8[(x * 256 + j) * kCursorPad] = start of top-8 bucket j + what the stretches before x put into it
+//                      (the first pass's);  totals_lo[d] = sum over the high digits of bin (j, d), from the 32 rows;
+//                      stat_out = the statistics of the columns combined, posted to the host as well (PostTicket).
+// Rounds 7-8 had ONE last workgroup scan all 65536 bins through a 130 KiB LDS tile that turned coalesced loads into consecutive
+// bins per thread: a chain of dependent round trips on one CU while 255 waited.  A column's bins are consecutive per thread as
+// they are loaded, so nothing is transposed.  No workgroup waits for another: whoever arrives last at a ticket goes on (release
+// before the ticket, acquire after it), and takes what the others left from memory -- any workgroup can be the last.
+// Counts are integers: the result does not depend on who arrives when.
+// bins[0 .. 65536) and ticket[0 .. 33) are zero on entry.  fin: kH16FinWords words, written before they are read.
+// flip (SFX_FINISH_REVERSE=1, tests): workgroup i does the work of workgroup grid - 1 - i -- the emulator runs workgroups in
+// index order and would only ever see the last column and the last stretch finish last.
 struct OversizeEntry { uint32_t bin, start, size, off; };
 constexpr uint32_t kOversizeMax = 16384;
 constexpr int kH16FinThreads = 512;
-constexpr int kH16FinBins = 4 * kH16FinThreads;                      // bins of one workgroup of the reduction
-constexpr int kH16FinHalf = kH16Bins / 2;                            // bins the LDS holds at a time in the scan
-constexpr int kH16FinPer = kH16FinHalf / kH16FinThreads;             // consecutive bins per thread and half: 64
+constexpr int kH16FinBins = 4 * kH16FinThreads;                      // bins of one workgroup of the reduction = of a column
+constexpr int kH16FinCols = kH16Bins / kH16FinBins;                  // 32
+constexpr int kH16FinStat = 8;                                       // words of a column's statistics (5 used)
+constexpr int kH16FinWords = kH16FinCols * (kRadix + kH16FinStat) + kRadix;   // rows of low-digit sums, statistics, bucket starts
 __global__ void __launch_bounds__(kH16FinThreads)
 k_hist16_finish(const uint32_t* __restrict__ partial, unsigned nblocks, unsigned rows_per_class, uint32_t* bins,
-                uint32_t* class_top8, uint32_t* ticket, uint32_t* __restrict__ totals_lo, uint32_t* __restrict__ totals_hi,
-                uint32_t* __restrict__ stat_out, uint32_t cap, uint32_t fast, uint32_t* __restrict__ cursor16,
-                uint32_t* __restrict__ cursor8, PostTicket post)
+                uint32_t* class_top8, uint32_t* ticket, uint32_t* fin, uint32_t* __restrict__ totals_lo,
+                uint32_t* __restrict__ totals_hi, uint32_t* __restrict__ stat_out, uint32_t cap, uint32_t fast,
+                uint32_t* __restrict__ cursor16, uint32_t* __restrict__ cursor8, PostTicket post, unsigned flip)
 {
     constexpr int kWaves = kH16FinThreads / kWave;
-    __shared__ uint32_t tile[kH16FinHalf + kH16FinHalf / kH16FinPer];   // (one word of padding per thread's stretch: 130 KiB)
+    static_assert(kH16FinCols <= kWave && kRadix % kH16FinCols == 0, "one wave scans the columns; a column holds whole top-8 buckets");
+    static_assert(kWave * 4 == kRadix && 2 * kRadix == kH16FinThreads, "a wave's bins are one top-8 bucket");
     __shared__ uint32_t lo[kRadix];
     __shared__ uint32_t part[kWaves];
     __shared__ uint32_t sstat[5];
+    __shared__ uint32_t coloff[kH16FinCols];
     __shared__ uint32_t last;
+    uint32_t* const fin_lo = fin;                                                    // [column][low digit]
+    uint32_t* const fin_stat = fin_lo + kH16FinCols * kRadix;                        // [column][kH16FinStat]
+    uint32_t* const fin_top = fin_stat + kH16FinCols * kH16FinStat;                  // [top-8 bucket]: its start inside its column
     const unsigned tid = threadIdx.x;
+    const unsigned wg = flip ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
+    const unsigned bx = wg % (unsigned)kH16FinCols, by = wg / (unsigned)kH16FinCols;
     {
-        constexpr unsigned kGroups = kH16Bins / kH16FinBins;
-        const unsigned bx = blockIdx.x % kGroups, by = blockIdx.x / kGroups;
         const unsigned w0 = bx * (kH16FinBins / 2) + tid * 2;                        // this thread's two counter words = 4 bins
         uint32_t c[4] = {0, 0, 0, 0};
         const unsigned g1 = dmin(nblocks, (by + 1u) * rows_per_class);
-        constexpr int kFly = 4;
+        constexpr int kFly = 8;                                                      // (this part takes 27 us with 4 as with 8: it waits for its atomics, profiles/NOTES_r9.md)
         for (unsigned g = by * rows_per_class; g < g1; g += kFly) {
             uint2 v[kFly];
 #pragma unroll
@@ -1521,38 +1575,26 @@ k_hist16_finish(const uint32_t* __restrict__ partial, unsigned nblocks, unsigned
             if (c[k]) atomicAdd(&bins[2 * w0 + k], c[k]);
         uint32_t all = c[0] + c[1] + c[2] + c[3];
         for (int d = 32; d >= 1; d >>= 1) all += __shfl_xor(all, d);
-        static_assert(kWave * 4 == kRadix, "a wave's bins are one top-8 bucket");
         if (lane_id() == 0) class_top8[by * kRadix + (2u * w0) / (unsigned)kRadix] = all;
     }
-    // (release: this workgroup's counts before its ticket; acquire: every workgroup's counts after the last ticket)
+    // (release: this workgroup's counts before its ticket; acquire: the column's counts after the column's last ticket)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __syncthreads();
-    if (tid == 0) last = (atomicAdd(ticket, 1u) == gridDim.x - 1u) ? 1u : 0u;
+    if (tid == 0) last = (atomicAdd(ticket + 1u + bx, 1u) == kPartClasses - 1u) ? 1u : 0u;
     __syncthreads();
     if (!last) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (tid < (unsigned)kRadix) lo[tid] = 0;
-    if (tid < 5u) sstat[tid] = 0;
-    uint32_t lo4[4] = {0, 0, 0, 0}, carry = 0;
-    uint32_t most = 0, slow = 0, nover = 0, sover = 0;
-    auto padded = [](unsigned i) { return i + i / (unsigned)kH16FinPer; };
-    for (int h = 0; h < 2; h++) {
-        uint32_t* const src = bins + h * kH16FinHalf;
-        __syncthreads();                                                             // (the tile's readers of the first half are done)
-#pragma unroll 4
-        for (int k = 0; k < kH16FinPer / 4; k++) {
-            // (four bins whose low digits are 4 tid .. 4 tid + 3 mod 256, whatever k: their column sums stay in registers)
-            const unsigned i = (unsigned)k * kH16FinBins + 4u * tid;
-            const uint4 v = *reinterpret_cast<const uint4*>(src + i);
-            lo4[0] += v.x; lo4[1] += v.y; lo4[2] += v.z; lo4[3] += v.w;
-            const unsigned at = padded(i);
-            tile[at] = v.x; tile[at + 1] = v.y; tile[at + 2] = v.z; tile[at + 3] = v.w;
-        }
-        __syncthreads();
-        uint32_t* const mine = tile + padded(tid * kH16FinPer);                      // (thread t's 64 bins: banks t + j)
-        uint32_t sum = 0;
-        for (int j = 0; j < kH16FinPer; j++) {
-            const uint32_t x = mine[j];
+    // ---- the column: 2048 bins, four consecutive ones per thread, a wave's 256 = one top-8 bucket ----
+    {
+        if (tid < (unsigned)kRadix) lo[tid] = 0;
+        if (tid < 5u) sstat[tid] = 0;
+        uint32_t* const mine = bins + bx * (unsigned)kH16FinBins + 4u * tid;
+        const uint4 v = *reinterpret_cast<const uint4*>(mine);
+        const uint32_t c[4] = {v.x, v.y, v.z, v.w};
+        uint32_t sum = 0, most = 0, slow = 0, nover = 0, sover = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t x = c[k];
             sum += x;
             most = dmax(most, x);
             if (x > fast) slow += x;
@@ -1561,46 +1603,116 @@ k_hist16_finish(const uint32_t* __restrict__ partial, unsigned nblocks, unsigned
         const uint32_t incl = wave_scan_add(sum);
         if (lane_id() == 63) part[wave_id()] = incl;
         __syncthreads();
-        uint32_t run = carry + incl - sum, total = 0;
+        uint32_t run = incl - sum, total = 0;
+#pragma unroll
         for (unsigned k = 0; k < (unsigned)kWaves; k++) {
-            if (k < wave_id()) run += part[k];
-            total += part[k];
+            const uint32_t q = part[k];
+            if (k < wave_id()) run += q;
+            total += q;
         }
-        carry += total;
-        static_assert(kRadix % kH16FinPer == 0, "a top-8 bucket begins with a thread's first bin");
-        if ((tid * kH16FinPer) % (unsigned)kRadix == 0u) {
-            const unsigned j = ((unsigned)h * kH16FinHalf + tid * kH16FinPer) / (unsigned)kRadix;
-            uint32_t at = run;
-            for (unsigned x = 0; x < kPartClasses; x++) {
-                cursor8[(x * kRadix + j) * kCursorPad] = at;
-                at += class_top8[x * kRadix + j];
-            }
-            totals_hi[j] = at - run;
+        if (lane_id() == 0) {
+            const unsigned j = bx * (unsigned)kWaves + wave_id();
+            fin_top[j] = run;
+            totals_hi[j] = part[wave_id()];
         }
-        for (int j = 0; j < kH16FinPer; j++) {
-            const uint32_t x = mine[j];
-            mine[j] = run;
-            run += x;
+        uint4 s;
+        s.x = run;
+        s.y = s.x + c[0];
+        s.z = s.y + c[1];
+        s.w = s.z + c[2];
+        *reinterpret_cast<uint4*>(mine) = s;
+#pragma unroll
+        for (int k = 0; k < 4; k++) atomicAdd(&lo[(4u * tid + (unsigned)k) % (unsigned)kRadix], c[k]);
+        for (int d = 32; d >= 1; d >>= 1) {
+            most = dmax(most, __shfl_xor(most, d));
+            slow += __shfl_xor(slow, d);
+            nover += __shfl_xor(nover, d);
+            sover += __shfl_xor(sover, d);
+        }
+        if (lane_id() == 0) {
+            atomicMax(&sstat[0], most);
+            atomicAdd(&sstat[4], slow);
+            atomicAdd(&sstat[2], nover);
+            atomicAdd(&sstat[3], sover);
         }
         __syncthreads();
-#pragma unroll 4
-        for (int k = 0; k < kH16FinPer / 4; k++) {
-            const unsigned i = (unsigned)k * kH16FinBins + 4u * tid, at = padded(i);
-            const uint4 v = uint4{tile[at], tile[at + 1], tile[at + 2], tile[at + 3]};
-            *reinterpret_cast<uint4*>(src + i) = v;
-            *reinterpret_cast<uint4*>(cursor16 + h * kH16FinHalf + i) = v;
+        if (tid < (unsigned)kRadix) fin_lo[bx * (unsigned)kRadix + tid] = lo[tid];
+        if (tid == 0) {
+            uint32_t* const cs = fin_stat + bx * (unsigned)kH16FinStat;
+            cs[0] = sstat[0];
+            cs[1] = total;
+            cs[2] = sstat[2];
+            cs[3] = sstat[3];
+            cs[4] = sstat[4];
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; k++) atomicAdd(&lo[(4u * tid + (unsigned)k) % (unsigned)kRadix], lo4[k]);
-    atomicMax(&sstat[0], most);
-    if (slow) atomicAdd(&sstat[4], slow);
-    if (nover) { atomicAdd(&sstat[2], nover); atomicAdd(&sstat[3], sover); }
+    // (release: this column's starts, sums and statistics before the ticket; acquire: every column's after the last one)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __syncthreads();
-    if (tid < (unsigned)kRadix) totals_lo[tid] = lo[tid];
+    if (tid == 0) last = (atomicAdd(ticket, 1u) == (unsigned)kH16FinCols - 1u) ? 1u : 0u;
+    __syncthreads();
+    if (!last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    // ---- all columns: one wave scans the 32 totals and combines the statistics ----
+    if (tid < (unsigned)kWave) {
+        const bool in = tid < (unsigned)kH16FinCols;
+        const uint32_t* const cs = fin_stat + (in ? tid : 0u) * (unsigned)kH16FinStat;
+        uint32_t most = in ? cs[0] : 0u, all = in ? cs[1] : 0u, nover = in ? cs[2] : 0u, sover = in ? cs[3] : 0u, slow = in ? cs[4] : 0u;
+        const uint32_t incl = wave_scan_add(all);
+        if (in) coloff[tid] = incl - all;
+        for (int d = 32; d >= 1; d >>= 1) {
+            most = dmax(most, __shfl_xor(most, d));
+            all += __shfl_xor(all, d);
+            nover += __shfl_xor(nover, d);
+            sover += __shfl_xor(sover, d);
+            slow += __shfl_xor(slow, d);
+        }
+        if (tid == 0) { sstat[0] = most; sstat[1] = all; sstat[2] = nover; sstat[3] = sover; sstat[4] = slow; }
+    }
+    __syncthreads();
+    // the starts: column k's 16 bytes of this thread + the column's offset, 16 columns in flight
+    {
+        constexpr int kFly = 16;
+        static_assert(kH16FinCols % kFly == 0, "whole batches of columns");
+        for (int k0 = 0; k0 < kH16FinCols; k0 += kFly) {
+            uint4 v[kFly];
+#pragma unroll
+            for (int k = 0; k < kFly; k++) v[k] = *reinterpret_cast<const uint4*>(bins + (unsigned)(k0 + k) * kH16FinBins + 4u * tid);
+            SFX_ISSUE_ORDER();
+#pragma unroll
+            for (int k = 0; k < kFly; k++) {
+                const uint32_t off = coloff[k0 + k];
+                const unsigned i = (unsigned)(k0 + k) * kH16FinBins + 4u * tid;
+                const uint4 s = uint4{v[k].x + off, v[k].y + off, v[k].z + off, v[k].w + off};
+                *reinterpret_cast<uint4*>(bins + i) = s;
+                *reinterpret_cast<uint4*>(cursor16 + i) = s;
+            }
+        }
+    }
+    if (tid < (unsigned)kRadix) {
+        // the first pass's cursors of top-8 bucket tid (every load before the first store)
+        const unsigned j = tid;
+        uint32_t c8[kPartClasses];
+#pragma unroll
+        for (unsigned x = 0; x < kPartClasses; x++) c8[x] = class_top8[x * kRadix + j];
+        uint32_t at = fin_top[j] + coloff[j / (unsigned)(kRadix / kH16FinCols)];
+        SFX_ISSUE_ORDER();
+#pragma unroll
+        for (unsigned x = 0; x < kPartClasses; x++) {
+            cursor8[(x * kRadix + j) * kCursorPad] = at;
+            at += c8[x];
+        }
+    } else {
+        const unsigned d = tid - (unsigned)kRadix;
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < kH16FinCols; k++) sum += fin_lo[k * kRadix + d];
+        totals_lo[d] = sum;
+    }
+    __syncthreads();
     if (tid == 0) {
-        bins[kH16Bins] = carry;
-        const uint32_t words[5] = {sstat[0], carry, sstat[2], sstat[3], sstat[4]};
+        bins[kH16Bins] = sstat[1];
+        const uint32_t words[5] = {sstat[0], sstat[1], sstat[2], sstat[3], sstat[4]};
         for (int k = 0; k < 5; k++) stat_out[k] = words[k];
         post_words_from_kernel(post, words, 5u);
     }
@@ -2128,9 +2240,22 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
     if (from_elems)
         SFX_LAUNCH("radix_hist16_elems", (double)m * 8.0, k_hist16_e64, ch.blocks, kH16Threads, st, (const uint64_t*)e0, m, top_hi - 16,
                    ch.tiles_per_block * kH16Threads, partial, zero);
-    else
-        SFX_LAUNCH("radix_hist16_text", (double)m * text.bits / 8.0, k_hist16_text, ch.blocks, kH16Threads, st, text, low_bits,
-                   ch.tiles_per_block * kH16Threads, partial, zero);
+    else {
+        // (whole 32-bit keys of 1, 2, 4 or 8-bit symbols: the sweep with its shifts known at compile time)
+        auto sweep = [&](auto spw) -> int {
+            SFX_LAUNCH("radix_hist16_text", (double)m * text.bits / 8.0, k_hist16_text<decltype(spw)::value>, ch.blocks, kH16Threads, st, text,
+                       low_bits, ch.tiles_per_block * kH16Threads, partial, zero);
+            return SFX_OK;
+        };
+        const int fixed = (text.kbits == 32 && text.bits * text.spw == 32) ? text.spw : 0;
+        switch (fixed) {
+        case 32: SFX_TRY(sweep(std::integral_constant<int, 32>{})); break;
+        case 16: SFX_TRY(sweep(std::integral_constant<int, 16>{})); break;
+        case 8: SFX_TRY(sweep(std::integral_constant<int, 8>{})); break;
+        case 4: SFX_TRY(sweep(std::integral_constant<int, 4>{})); break;
+        default: SFX_TRY(sweep(std::integral_constant<int, 0>{})); break;
+        }
+    }
     // (the rows of the partial counts in kPartClasses contiguous stretches: k_partition's first pass wants the top-8 counts of each)
     const unsigned rows_per_class = (ch.blocks + kPartClasses - 1) / kPartClasses;
     const uint64_t class_len = (uint64_t)rows_per_class * ch.tiles_per_block * kH16Threads * (from_elems ? 1u : (uint64_t)text.spw);
@@ -2139,12 +2264,18 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
     uint32_t* cursor8 = class_top8 + kPartClasses * kRadix;
     static_assert(kH16Bins + 128 + 4 * kOversizeMax + kH16Bins + kPartClasses * kRadix * (1 + kCursorPad) <= kReserve, "the reserve holds the cursors too");
     // sub-bucket starts, digit totals, the cursors of both partition passes and the statistics, posted to the host by the kernel
-    // itself: one launch (k_hist16_finish); its ticket is a zeroed word behind the statistics
+    // itself: one launch (k_hist16_finish); its tickets (one of the grid's, one per column) are zeroed words behind the
+    // statistics, what its columns hand to the last one lies behind the cursors
+    uint32_t* fin = cursor8 + kPartClasses * kRadix * kCursorPad;
+    static_assert(kH16Bins + 128 + 4 * kOversizeMax + kH16Bins + kPartClasses * kRadix * (1 + kCursorPad) + kH16FinWords <= kReserve,
+                  "the reserve holds what the columns leave for the last one");
+    static_assert(64 + 16 + 1 + kH16FinCols <= 128, "the tickets lie inside what the sweep zeroes");
+    static const unsigned flip = [] { const char* e = dev_env("SFX_FINISH_REVERSE"); return (e && atoi(e) != 0) ? 1u : 0u; }();
     uint32_t host_stat[5] = {0, 0, 0, 0, 0};
     const PostTicket post = post_ticket();
     SFX_LAUNCH("radix_hist16_finish", (double)ch.blocks * kH16Words * 4 + (double)kH16Bins * 12, k_hist16_finish,
-               (kH16Bins / kH16FinBins) * kPartClasses, kH16FinThreads, st, (const uint32_t*)partial, ch.blocks, rows_per_class, bins, class_top8,
-               stat + 16, scr.totals, scr.totals + kRadix, stat, cap, dmin(cap, 4096u), cursor16, cursor8, post);
+               kH16FinCols * kPartClasses, kH16FinThreads, st, (const uint32_t*)partial, ch.blocks, rows_per_class, bins, class_top8,
+               stat + 16, fin, scr.totals, scr.totals + kRadix, stat, cap, dmin(cap, 4096u), cursor16, cursor8, post, flip);
     SFX_TRY(read_posted(host_stat, stat, sizeof(host_stat), post, st));
     const uint32_t host_max = host_stat[0], nover = host_stat[2];
     const uint64_t nlarge = host_stat[3], nslow = host_stat[4];
