@@ -355,6 +355,8 @@ struct TieRecords {
     uint32_t* lmask;
     uint32_t* hmask;
     bool want_keys;                // in: leave the sorted 32-bit keys in *split_k_out as well (the fused LCP reads them once)
+    uint32_t* zero;                // in: zero_words words of the caller's (its counter lines) that the route's histogram sweep zeroes
+    uint32_t zero_words;           //     on its way in, as it does its own (H16Zero): zero whenever `produced` comes back true
 };
 //    A producer that had the keys in registers anyway (the range filter) may have counted the
 //    digits itself: `hist_blocks` workgroups' counts at radix_partial(scratch)[(pass * 256 +

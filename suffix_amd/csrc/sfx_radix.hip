@@ -1377,18 +1377,22 @@ k_partition_text(Src src, uint64_t* __restrict__ out, uint64_t m, int shift, uin
 constexpr int kH16Bins = 1 << 16;
 constexpr int kH16Words = kH16Bins / 2;                              // two 16-bit counters per LDS word
 constexpr int kH16Threads = 1024;
-// What the kernels behind the sweep want zeroed (the sub-bucket counts with the statistics and k_hist16_finish's ticket behind
-// them; the tickets of the one-sweep passes): the sweep's workgroups clear it on their way in -- they are bound by their LDS
-// atomics, and a fill is a launch of its own in the stream (~4 us each, two of them before round 7).
+// What the kernels behind the sweep want zeroed (the statistics and k_hist16_finish's tickets behind the sub-bucket counts; the
+// tickets of the one-sweep passes; the counter lines of the caller's tie kernels): the sweep's workgroups clear it on their way
+// in -- they are bound by their LDS atomics, and a fill is a launch of its own in the stream (~4 us each, two of them before
+// round 7).
 struct H16Zero {
     uint32_t* a;
     uint32_t na;
     uint32_t* b;
     uint32_t nb;
+    uint32_t* c;                                                      // (the caller's: TieRecords::zero -- the counter lines of the tie kernels)
+    uint32_t nc;
     __device__ __forceinline__ void clear(unsigned threads) const
     {
         for (uint32_t i = blockIdx.x * threads + threadIdx.x; i < na; i += gridDim.x * threads) a[i] = 0;
         for (uint32_t i = blockIdx.x * threads + threadIdx.x; i < nb; i += gridDim.x * threads) b[i] = 0;
+        for (uint32_t i = blockIdx.x * threads + threadIdx.x; i < nc; i += gridDim.x * threads) c[i] = 0;
     }
 };
 // One sweep over the workgroup's stretch of the text with 16-bit counters (128 KiB of LDS).  A counter can only
@@ -1498,14 +1502,17 @@ k_hist16_e64(const uint64_t* __restrict__ E, uint64_t m, int shift, uint64_t per
 }
 // Everything between the histogram sweep and the first partition pass in ONE launch (round 7; rounds 3-6: a reduction, a
 // one-workgroup scan, a cursor kernel and a one-wave kernel that posted the statistics to the host).
-//   every workgroup  bins[b] += the counts of a slice of the workgroups' partial histograms: workgroup x + 32 y takes the 2048
+//   every workgroup  sums the counts of a slice of the workgroups' partial histograms: workgroup x + 32 y takes the 2048
 //                    bins from 2048 x (4 KB of every partial, one 8-byte load per thread, eight rows in flight) and the partials
 //                    of the y-th of kPartClasses contiguous stretches of `rows_per_class` rows -- the workgroups that counted the
 //                    y-th stretch of the text; a wave's 256 bins are one top-8 bucket, so the sum over a wave is the number of
-//                    suffixes of that stretch in that bucket, class_top8[y * 256 + bucket];
-//   the last one of a column  (the 8 workgroups x + 32 y of column x take a ticket of the column's) reads the column's 2048
-//                    summed counts back, four consecutive bins per thread in registers, scans them over the workgroup and leaves
-//                      bins[b] = first position of sub-bucket b INSIDE the column (in place);
+//                    suffixes of that stretch in that bucket, class_top8[y * 256 + bucket].  The 2048 sums go, 32 bits each,
+//                    over column x's segment of the stretch's first two rows with write-through stores (rounds 7-9 added them
+//                    to `bins`: 524 288 device-scope atomics on words that eight stretches share, behind a release fence per
+//                    workgroup); a stretch of one row keeps it;
+//   the last one of a column  (the 8 workgroups x + 32 y of column x take a ticket of the column's) adds the eight stretches'
+//                    sums, four consecutive bins per thread in registers, scans them over the workgroup and leaves
+//                      bins[b] = first position of sub-bucket b INSIDE the column;
 //                      totals_hi[j] = sum over the low digits of top-8 bucket j (a wave's 256 bins), its column-local start
 //                      in fin;  the column's row of low-digit sums and its statistics {largest bin, total, sub-buckets of more
 //                      than `cap` suffixes, their suffixes, suffixes in sub-buckets of more than `fast`} in fin;
@@ -1520,7 +1527,7 @@ k_hist16_e64(const uint64_t* __restrict__ E, uint64_t m, int shift, uint64_t per
 // they are loaded, so nothing is transposed.  No workgroup waits for another: whoever arrives last at a ticket goes on (release
 // before the ticket, acquire after it), and takes what the others left from memory -- any workgroup can be the last.
 // Counts are integers: the result does not depend on who arrives when.
-// bins[0 .. 65536) and ticket[0 .. 33) are zero on entry.  fin: kH16FinWords words, written before they are read.
+// ticket[0 .. 33) are zero on entry.  bins, fin (kH16FinWords words): written before they are read.  partial: overwritten.
 // flip (SFX_FINISH_REVERSE=1, tests): workgroup i does the work of workgroup grid - 1 - i -- the emulator runs workgroups in
 // index order and would only ever see the last column and the last stretch finish last.
 struct OversizeEntry { uint32_t bin, start, size, off; };
@@ -1531,7 +1538,7 @@ constexpr int kH16FinCols = kH16Bins / kH16FinBins;                  // 32
 constexpr int kH16FinStat = 8;                                       // words of a column's statistics (5 used)
 constexpr int kH16FinWords = kH16FinCols * (kRadix + kH16FinStat) + kRadix;   // rows of low-digit sums, statistics, bucket starts
 __global__ void __launch_bounds__(kH16FinThreads)
-k_hist16_finish(const uint32_t* __restrict__ partial, unsigned nblocks, unsigned rows_per_class, uint32_t* bins,
+k_hist16_finish(uint32_t* partial, unsigned nblocks, unsigned rows_per_class, uint32_t* bins,
                 uint32_t* class_top8, uint32_t* ticket, uint32_t* fin, uint32_t* __restrict__ totals_lo,
                 uint32_t* __restrict__ totals_hi, uint32_t* __restrict__ stat_out, uint32_t cap, uint32_t fast,
                 uint32_t* __restrict__ cursor16, uint32_t* __restrict__ cursor8, PostTicket post, unsigned flip)
@@ -1554,7 +1561,7 @@ k_hist16_finish(const uint32_t* __restrict__ partial, unsigned nblocks, unsigned
         const unsigned w0 = bx * (kH16FinBins / 2) + tid * 2;                        // this thread's two counter words = 4 bins
         uint32_t c[4] = {0, 0, 0, 0};
         const unsigned g1 = dmin(nblocks, (by + 1u) * rows_per_class);
-        constexpr int kFly = 8;                                                      // (this part takes 27 us with 4 as with 8: it waits for its atomics, profiles/NOTES_r9.md)
+        constexpr int kFly = 8;                                                      // (27 us with 4 as with 8 while the sums went to `bins` by atomics: profiles/NOTES_r9.md)
         for (unsigned g = by * rows_per_class; g < g1; g += kFly) {
             uint2 v[kFly];
 #pragma unroll
@@ -1570,15 +1577,26 @@ k_hist16_finish(const uint32_t* __restrict__ partial, unsigned nblocks, unsigned
                 c[3] += v[k].y >> 16;
             }
         }
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (c[k]) atomicAdd(&bins[2 * w0 + k], c[k]);
+        // the stretch's sums, 32 bits each, over the very words this thread read them from: bins 4 tid, 4 tid + 1 in the stretch's
+        // first row, 4 tid + 2, 4 tid + 3 in its second (nobody else reads this column's segment of this stretch's rows, and this
+        // thread has read both); a stretch of one row or none keeps its packed row, which the column stage reads as it is
+        // Write-through stores (relaxed, agent scope), drained by every wave before the workgroup's ticket: they stand in memory
+        // when the ticket is taken, with no release fence -- that fence writes the L2's dirty lines back, and with 8 KB freshly
+        // dirtied per workgroup it made this phase slower than the atomics it replaced (profiles/NOTES_r10.md).
+        if (g1 >= by * rows_per_class + 2u) {
+            unsigned long long* const own = reinterpret_cast<unsigned long long*>(partial + (uint64_t)(by * rows_per_class) * kH16Words + w0);
+            __hip_atomic_store(own, (unsigned long long)c[0] | ((unsigned long long)c[1] << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(own + kH16Words / 2, (unsigned long long)c[2] | ((unsigned long long)c[3] << 32), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        }
         uint32_t all = c[0] + c[1] + c[2] + c[3];
         for (int d = 32; d >= 1; d >>= 1) all += __shfl_xor(all, d);
-        if (lane_id() == 0) class_top8[by * kRadix + (2u * w0) / (unsigned)kRadix] = all;
+        if (lane_id() == 0) __hip_atomic_store(&class_top8[by * kRadix + (2u * w0) / (unsigned)kRadix], all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    // (release: this workgroup's counts before its ticket; acquire: the column's counts after the column's last ticket)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    // (this workgroup's write-through stores have landed before its ticket; acquire: the column's sums after the column's last ticket)
+#ifndef SFX_EMULATED
+    __builtin_amdgcn_s_waitcnt(0);
+#endif
     __syncthreads();
     if (tid == 0) last = (atomicAdd(ticket + 1u + bx, 1u) == kPartClasses - 1u) ? 1u : 0u;
     __syncthreads();
@@ -1589,8 +1607,33 @@ k_hist16_finish(const uint32_t* __restrict__ partial, unsigned nblocks, unsigned
         if (tid < (unsigned)kRadix) lo[tid] = 0;
         if (tid < 5u) sstat[tid] = 0;
         uint32_t* const mine = bins + bx * (unsigned)kH16FinBins + 4u * tid;
-        const uint4 v = *reinterpret_cast<const uint4*>(mine);
-        const uint32_t c[4] = {v.x, v.y, v.z, v.w};
+        // the eight stretches' sums of this thread's four bins: two 8-byte loads per stretch, all sixteen before the first add
+        const unsigned w0 = bx * (kH16FinBins / 2) + tid * 2;
+        uint2 r0[kPartClasses], r1[kPartClasses];
+#pragma unroll
+        for (unsigned y = 0; y < kPartClasses; y++) {
+            const unsigned g0 = y * rows_per_class, rows = g0 < nblocks ? nblocks - g0 : 0u;
+            const uint32_t* const row = partial + (uint64_t)g0 * kH16Words + w0;
+            r0[y] = rows >= 1u ? *reinterpret_cast<const uint2*>(row) : uint2{0u, 0u};
+            r1[y] = (rows >= 2u && rows_per_class >= 2u) ? *reinterpret_cast<const uint2*>(row + kH16Words) : uint2{0u, 0u};
+        }
+        SFX_ISSUE_ORDER();
+        uint32_t c[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (unsigned y = 0; y < kPartClasses; y++) {
+            const unsigned g0 = y * rows_per_class, rows = g0 < nblocks ? nblocks - g0 : 0u;
+            if (rows >= 2u && rows_per_class >= 2u) {                                // (32-bit sums in the stretch's first two rows)
+                c[0] += r0[y].x;
+                c[1] += r0[y].y;
+                c[2] += r1[y].x;
+                c[3] += r1[y].y;
+            } else {                                                                 // (its one packed row, or nothing)
+                c[0] += r0[y].x & 0xFFFFu;
+                c[1] += r0[y].x >> 16;
+                c[2] += r0[y].y & 0xFFFFu;
+                c[3] += r0[y].y >> 16;
+            }
+        }
         uint32_t sum = 0, most = 0, slow = 0, nover = 0, sover = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -2236,7 +2279,9 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
     const uint64_t room = m * sizeof(uint64_t) / (kH16Words * sizeof(uint32_t));     // partial histograms that fit e1
     if (room == 0) return SFX_OK;
     Chunking ch = make_chunking(nwords, kH16Threads, (unsigned)dmin<uint64_t>(room, 256));
-    const H16Zero zero = {bins, (uint32_t)(kH16Bins + 128), scr.tickets, 64u};             // (the counts and the statistics; the tickets)
+    // (the statistics and k_hist16_finish's tickets behind the counts; the sweeps' tickets; what the caller wants zero by the time
+    // the route has produced its ties)
+    const H16Zero zero = {bins + kH16Bins, 128u, scr.tickets, 64u, ties ? ties->zero : nullptr, ties ? ties->zero_words : 0u};
     if (from_elems)
         SFX_LAUNCH("radix_hist16_elems", (double)m * 8.0, k_hist16_e64, ch.blocks, kH16Threads, st, (const uint64_t*)e0, m, top_hi - 16,
                    ch.tiles_per_block * kH16Threads, partial, zero);
@@ -2274,7 +2319,7 @@ static int hybrid_sort_e64_text(uint64_t* e0, uint64_t* e1, uint64_t m, int bit_
     uint32_t host_stat[5] = {0, 0, 0, 0, 0};
     const PostTicket post = post_ticket();
     SFX_LAUNCH("radix_hist16_finish", (double)ch.blocks * kH16Words * 4 + (double)kH16Bins * 12, k_hist16_finish,
-               kH16FinCols * kPartClasses, kH16FinThreads, st, (const uint32_t*)partial, ch.blocks, rows_per_class, bins, class_top8,
+               kH16FinCols * kPartClasses, kH16FinThreads, st, partial, ch.blocks, rows_per_class, bins, class_top8,
                stat + 16, fin, scr.totals, scr.totals + kRadix, stat, cap, dmin(cap, 4096u), cursor16, cursor8, post, flip);
     SFX_TRY(read_posted(host_stat, stat, sizeof(host_stat), post, st));
     const uint32_t host_max = host_stat[0], nover = host_stat[2];

@@ -98,18 +98,44 @@ k_byte_hist(const uint8_t* __restrict__ text, uint64_t begin, uint64_t end,
 // (the sorted `alphas` of Bins::find_sizes :700): plain LDS stores of a flag, 16 bytes of
 // text per thread and step -- no atomics, so 4-symbol DNA does not serialise on 4 counters.
 // bins[c] = 1 for every byte value c that occurs (bins zeroed by the caller).
+// With an AlphaStage (a full build: tickets != nullptr) nobody writes bins.  Every workgroup leaves its 256 flags as 8 words
+// (bit c & 31 of word c / 32) in a slot of its own, and the workgroup that arrives last does what a launch of k_make_lut, a
+// 2 KiB copy and a stream synchronisation did before round 10: it ORs the slots, writes the dense symbol codes (lut) and the
+// 8 words, and posts the words to the host.  The grid has up to 2048 workgroups, so the tickets are sharded: workgroup w
+// arrives at shard w % shards, a shard's last arriver at the grid's ticket.  No workgroup waits for another.
+// The slots go out as write-through stores (relaxed, agent scope) that every storing wave drains before the workgroup's
+// ticket, and the last arriver reads them past its caches: no release fence.  Measured on 100 MB (profiles/NOTES_r10.md): a
+// release fence per workgroup took this kernel from 23 to 192 us, write-through stores of all workgroups into the SAME 256
+// words of bins to 101 us -- 8192 stores through the fabric to one line of memory; slots of their own cost nothing.
+// The grid's ticket is tickets[0], shard s's tickets[(1 + s) * kAlphaTicketStride]: 256 bytes apart -- with all 33 words in one
+// 128-byte line the 2048 arrivals of the grid's end cost 8 us more.  All zero on entry.
+// flip (SFX_FINISH_REVERSE=1, tests): workgroup i does the work of grid - 1 - i.
+constexpr unsigned kAlphaShards = 32, kAlphaTicketStride = 64;
+struct AlphaStage {
+    uint32_t* tickets;
+    unsigned long long* slots;                                       // 4 per workgroup of the grid
+    uint32_t* words;                                                 // 8
+    uint8_t* lut;                                                    // 256
+    PostTicket post;
+    unsigned flip;
+};
+__host__ __device__ inline unsigned alpha_shards(unsigned grid) { return dmin(kAlphaShards, (grid + 3u) / 4u); }
 __global__ void __launch_bounds__(kBlock)
-k_byte_presence(const uint8_t* __restrict__ text, uint64_t n, unsigned long long* __restrict__ bins)
+k_byte_presence(const uint8_t* __restrict__ text, uint64_t n, unsigned long long* bins, AlphaStage a)
 {
     __shared__ uint32_t present[256];
+    __shared__ uint32_t part[kWavesPerBlock];
+    __shared__ uint32_t flagw[8];
+    __shared__ uint32_t last;
     const unsigned tid = threadIdx.x;
+    const unsigned wg = a.flip ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
     present[tid] = 0;
     __syncthreads();
     const uint64_t n16 = n / 16;
     const uint4* t16 = reinterpret_cast<const uint4*>(text);        // text comes 16-byte aligned or is handled below
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     if ((reinterpret_cast<uintptr_t>(text) & 15u) == 0) {
-        for (uint64_t i = (uint64_t)blockIdx.x * kBlock + tid; i < n16; i += stride) {
+        for (uint64_t i = (uint64_t)wg * kBlock + tid; i < n16; i += stride) {
             const uint4 v = t16[i];
             const uint32_t wds[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -120,12 +146,64 @@ k_byte_presence(const uint8_t* __restrict__ text, uint64_t n, unsigned long long
                 present[wds[k] >> 24] = 1u;
             }
         }
-        for (uint64_t i = n16 * 16 + (uint64_t)blockIdx.x * kBlock + tid; i < n; i += stride) present[text[i]] = 1u;
+        for (uint64_t i = n16 * 16 + (uint64_t)wg * kBlock + tid; i < n; i += stride) present[text[i]] = 1u;
     } else {
-        for (uint64_t i = (uint64_t)blockIdx.x * kBlock + tid; i < n; i += stride) present[text[i]] = 1u;
+        for (uint64_t i = (uint64_t)wg * kBlock + tid; i < n; i += stride) present[text[i]] = 1u;
     }
     __syncthreads();
-    if (present[tid]) bins[tid] = 1ull;
+    if (!a.tickets) {
+        if (present[tid]) bins[tid] = 1ull;
+        return;
+    }
+    static_assert(kBlock == 256 && kWave == 64, "a thread per byte value, two flag words per wave");
+    {
+        const unsigned long long seen = __ballot(present[tid] != 0u);                // byte values 64 wave .. 64 wave + 63
+        if (lane_id() == 0) __hip_atomic_store(a.slots + (uint64_t)wg * 4u + wave_id(), seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#ifndef SFX_EMULATED
+    __builtin_amdgcn_s_waitcnt(0);
+#endif
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned shards = alpha_shards(gridDim.x), s = wg % shards;
+        const unsigned members = (gridDim.x - s + shards - 1u) / shards;            // workgroups w < grid with w % shards == s
+        uint32_t l = 0;
+        if (atomicAdd(a.tickets + (1u + s) * kAlphaTicketStride, 1u) == members - 1u) l = (atomicAdd(a.tickets, 1u) == shards - 1u) ? 1u : 0u;
+        last = l;
+    }
+    if (tid < 8u) flagw[tid] = 0;
+    __syncthreads();
+    if (!last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    {
+        // (thread t takes the 64-bit words t, t + 256, ..: always the same quarter of a slot, t & 3)
+        // (sixteen loads in flight: a plain loop over the grid's 8192 words cost this kernel 4.6 us more on 100 MB)
+        constexpr unsigned kFly = 16;
+        const unsigned total = gridDim.x * 4u;
+        unsigned long long mine = 0;
+        for (unsigned i0 = tid; i0 < total; i0 += kBlock * kFly) {
+            unsigned long long v[kFly];
+#pragma unroll
+            for (unsigned k = 0; k < kFly; k++) {
+                const unsigned i = i0 + k * kBlock;
+                v[k] = i < total ? __hip_atomic_load(a.slots + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+            }
+            SFX_ISSUE_ORDER();
+#pragma unroll
+            for (unsigned k = 0; k < kFly; k++) mine |= v[k];
+        }
+        if ((uint32_t)mine) atomicOr(&flagw[2u * (tid & 3u)], (uint32_t)mine);
+        if ((uint32_t)(mine >> 32)) atomicOr(&flagw[2u * (tid & 3u) + 1u], (uint32_t)(mine >> 32));
+    }
+    __syncthreads();
+    const uint32_t here = (flagw[tid >> 5] >> (tid & 31u)) & 1u;
+    uint32_t total;
+    a.lut[tid] = (uint8_t)block_scan_add_excl(here, part, total);                    // (k_make_lut's codes)
+    if (tid == 0) {
+        uint32_t words[8];
+        for (int k = 0; k < 8; k++) a.words[k] = words[k] = flagw[k];
+        post_words_from_kernel(a.post, words, 8u);
+    }
 }
 
 // dense symbol codes from the 256 global byte counts (one workgroup, thread = byte value)
@@ -1377,19 +1455,29 @@ k_tie_direct(const uint32_t* __restrict__ tmask, uint64_t m, PackedText t, uint3
         if (n_left) atomicAdd(&line[2], n_left);
     }
 }
+// The sums of the counter lines, into totals[0 .. 3) and to the host under `post` (one workgroup).  It leaves the lines zero
+// behind it: the next user in the same build (k_tie_heads after k_tie_direct) needs no fill of its own.
 __global__ void __launch_bounds__(kBlock)
-k_tie_totals(const uint32_t* __restrict__ lines, uint32_t* __restrict__ totals)
+k_tie_totals(uint32_t* __restrict__ lines, uint32_t* __restrict__ totals, PostTicket post)
 {
     __shared__ uint32_t part[3][kWavesPerBlock];
     uint32_t a = 0, b = 0, c = 0;
-    for (unsigned i = threadIdx.x; i < kTieSlots; i += kBlock) { a += lines[i * 4u]; b += lines[i * 4u + 1u]; c += lines[i * 4u + 2u]; }
+    for (unsigned i = threadIdx.x; i < kTieSlots; i += kBlock) {
+        uint4* const line = reinterpret_cast<uint4*>(lines) + i;
+        const uint4 v = *line;
+        a += v.x; b += v.y; c += v.z;
+        *line = uint4{0u, 0u, 0u, 0u};
+    }
     for (int d = 32; d >= 1; d >>= 1) { a += (uint32_t)__shfl_xor(a, d); b += (uint32_t)__shfl_xor(b, d); c += (uint32_t)__shfl_xor(c, d); }
     if (lane_id() == 0) { part[0][wave_id()] = a; part[1][wave_id()] = b; part[2][wave_id()] = c; }
     __syncthreads();
-    if (threadIdx.x < 3) {
-        uint32_t x = 0;
-        for (int w = 0; w < kWavesPerBlock; w++) x += part[threadIdx.x][w];
-        totals[threadIdx.x] = x;
+    if (threadIdx.x == 0) {
+        uint32_t words[3] = {0, 0, 0};
+        for (int k = 0; k < 3; k++) {
+            for (int w = 0; w < kWavesPerBlock; w++) words[k] += part[k][w];
+            totals[k] = words[k];
+        }
+        post_words_from_kernel(post, words, 3u);
     }
 }
 // k_tie_heads (the leftover path): hmask bit r = slot r is tied and the first of its run -- the slot before is untied or holds
@@ -2046,13 +2134,23 @@ int byte_histogram_dev(const uint8_t* d_text, uint64_t begin, uint64_t end, uint
 // `n_words_out` > 0: write exactly that many words (zeros past the text) instead of the
 // default (n + spw - 1) / spw + 3; `packed_in`: the text is already packed (partitioned
 // build after an all-gather of packed shards) -- only the alphabet is derived.
+// `staged`: a k_byte_presence launched on `st` with this AlphaStage precedes -- its last workgroup wrote the LUT and posts the
+// presence flags as 8 words: no launch, no copy and no stream synchronisation here, and d_bins is not read.
 static int prepare_text(const uint8_t* d_text, uint64_t n, const unsigned long long* d_bins,
                         uint8_t* d_lut, uint32_t* d_packed, hipStream_t st, Alphabet* alpha,
-                        PackedText* pt, uint64_t n_words_out = 0, const uint32_t* packed_in = nullptr)
+                        PackedText* pt, uint64_t n_words_out = 0, const uint32_t* packed_in = nullptr,
+                        const AlphaStage* staged = nullptr)
 {
     unsigned long long host_bins[256];
-    if (!packed_in) SFX_LAUNCH("make_lut", 0.0, k_make_lut, 1, kBlock, st, d_bins, d_lut);
-    SFX_TRY(read_back(host_bins, d_bins, sizeof(host_bins), st));
+    if (staged) {
+        if (packed_in || staged->lut != d_lut) return SFX_ERR_INTERNAL;
+        uint32_t flags[8];
+        SFX_TRY(read_posted(flags, staged->words, sizeof(flags), staged->post, st));
+        for (int c = 0; c < 256; c++) host_bins[c] = (flags[c >> 5] >> (c & 31)) & 1u;
+    } else {
+        if (!packed_in) SFX_LAUNCH("make_lut", 0.0, k_make_lut, 1, kBlock, st, d_bins, d_lut);
+        SFX_TRY(read_back(host_bins, d_bins, sizeof(host_bins), st));
+    }
     *alpha = make_alphabet(host_bins, n);
     if (packed_in) {
         pt->words = packed_in;
@@ -2102,7 +2200,7 @@ int byte_presence_host(const uint8_t* d_text, uint64_t n, void* d_small4k, unsig
     SFX_HIP(hipMemsetAsync(bins, 0, 256 * sizeof(unsigned long long), st));
     if (n) {
         const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock * 64 - 1) / (kBlock * 64), kMaxGrid);
-        SFX_LAUNCH("byte_presence", (double)n, k_byte_presence, grid, kBlock, st, d_text, n, bins);
+        SFX_LAUNCH("byte_presence", (double)n, k_byte_presence, grid, kBlock, st, d_text, n, bins, AlphaStage{});
     }
     return read_back(host_bins256, bins, 256 * sizeof(unsigned long long), st);
 }
@@ -2117,7 +2215,7 @@ int pack_small_alphabet(const uint8_t* d_text, uint64_t n, int max_bits, void* s
     uint8_t* lut = reinterpret_cast<uint8_t*>(small) + 256 * sizeof(unsigned long long);
     SFX_HIP(hipMemsetAsync(bins, 0, 256 * sizeof(unsigned long long), st));
     const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock * 64 - 1) / (kBlock * 64), kMaxGrid);
-    SFX_LAUNCH("byte_presence", (double)n, k_byte_presence, grid, kBlock, st, d_text, n, bins);
+    SFX_LAUNCH("byte_presence", (double)n, k_byte_presence, grid, kBlock, st, d_text, n, bins, AlphaStage{});
     unsigned long long host_bins[256];
     SFX_TRY(read_back(host_bins, bins, sizeof(host_bins), st));
     const Alphabet alpha = make_alphabet(host_bins);
@@ -2392,7 +2490,10 @@ static int sort_and_refine(const PackedText& pt, int cpk, uint64_t count, bool f
     uint32_t* V_next;
     bool in_place = false;
     int in1 = 0;
-    TieRecords ties = {false, nullptr, nullptr, nullptr, lcp_fuse != nullptr};
+    // (the counter lines of the tie kernels: zeroed by the hybrid route's first kernel, left zero again by k_tie_totals)
+    uint32_t* const tie_lines = reinterpret_cast<uint32_t*>(b.deep_slots);      // (idle until the first deep round)
+    static_assert(kTieSlots * 4 * sizeof(uint32_t) <= kDeepSlotWords * sizeof(unsigned long long), "the counter lines fit");
+    TieRecords ties = {false, nullptr, nullptr, nullptr, lcp_fuse != nullptr, tie_lines, kTieSlots * 4u};
     if (sizeof(KeyT) == 4) {
         // E64 elements; the last pass drops every suffix straight into its SA slot and
         // leaves the sorted 32-bit keys in the element buffer it did not read
@@ -2442,17 +2543,16 @@ static int sort_and_refine(const PackedText& pt, int cpk, uint64_t count, bool f
                        b.part_head, b.part_keep, b.part_ghead, b.F, fuse);
         }
         const uint64_t nwords = (count + 31) / 32;
-        uint32_t* const lines = reinterpret_cast<uint32_t*>(b.deep_slots);     // (idle until the first deep round)
-        static_assert(kTieSlots * 4 * sizeof(uint32_t) <= kDeepSlotWords * sizeof(unsigned long long), "the counter lines fit");
-        SFX_HIP(hipMemsetAsync(lines, 0, kTieSlots * 4 * sizeof(uint32_t), st));
+        uint32_t* const lines = tie_lines;
+        uint32_t host_totals[3] = {0, 0, 0};
         {
             const uint64_t waves = (nwords / 2 + kWave - 1) / kWave + 1;          // (a wave: 64 lanes x 2 mask words)
             const unsigned grid = (unsigned)dmin<uint64_t>((waves + kWavesPerBlock - 1) / kWavesPerBlock, 4 * kMaxGrid);
             SFX_LAUNCH("tie_direct", (double)count * 0.125, k_tie_direct, grid, kBlock, st, ties.tmask, count, pt, sa, lines, kTieRunMax, ties.lmask);
-            SFX_LAUNCH("tie_totals", 0.0, k_tie_totals, 1, kBlock, st, (const uint32_t*)lines, b.totals);
+            const PostTicket post = post_ticket();
+            SFX_LAUNCH("tie_totals", 0.0, k_tie_totals, 1, kBlock, st, lines, b.totals, post);
+            SFX_TRY(read_posted(host_totals, b.totals, sizeof(host_totals), post, st));
         }
-        uint32_t host_totals[3] = {0, 0, 0};
-        SFX_TRY(read_back(host_totals, b.totals, sizeof(host_totals), st));
         kept = host_totals[0];
         if (kept > count || (uint64_t)host_totals[1] * 2 > kept || host_totals[2] > kept) return SFX_ERR_INTERNAL;
         stats.active_after_initial = kept;
@@ -2465,13 +2565,13 @@ static int sort_and_refine(const PackedText& pt, int cpk, uint64_t count, bool f
         stats.small_bucket_resolved += kept - host_totals[2];
         kept = host_totals[2];
         {
-            SFX_HIP(hipMemsetAsync(lines, 0, kTieSlots * 4 * sizeof(uint32_t), st));
             const unsigned hgrid = (unsigned)dmin<uint64_t>((nwords + kBlock - 1) / kBlock, kMaxGrid);
             SFX_LAUNCH("tie_heads", (double)count * 0.25 + (double)kept * 8, k_tie_heads, hgrid, kBlock, st, (const uint32_t*)ties.lmask, count, pt,
                        (const uint32_t*)sa, ties.hmask, lines);
-            SFX_LAUNCH("tie_totals", 0.0, k_tie_totals, 1, kBlock, st, (const uint32_t*)lines, b.totals);
+            const PostTicket post = post_ticket();
+            SFX_LAUNCH("tie_totals", 0.0, k_tie_totals, 1, kBlock, st, lines, b.totals, post);
             uint32_t runs = 0;
-            SFX_TRY(read_back(&runs, b.totals, sizeof(runs), st));
+            SFX_TRY(read_posted(&runs, b.totals, sizeof(runs), post, st));
             groups = runs;
             if (groups * 2 > kept) return SFX_ERR_INTERNAL;
             Chunking ch = make_chunking(nwords, kBlock);
@@ -2566,14 +2666,22 @@ static int build_sa_impl(const uint8_t* d_text, uint64_t n, uint32_t* d_sa, void
     carve_sa(ar, n, n, n, &b);
     if (ar.overflow) return SFX_ERR_WORKSPACE;
 
-    SFX_HIP(hipMemsetAsync(b.bins, 0, 256 * sizeof(unsigned long long), st));
+    // the alphabet: presence flags, LUT and the flags' way to the host in one launch (AlphaStage).  The workgroups' slots and,
+    // behind them, the tickets live in the radix scratch, idle until the sort; only the tickets need a fill.  The 8 flag words:
+    // the last of b.totals' 64 words (the totals are its first three).
+    constexpr unsigned kAlphaSlotWords = kMaxGrid * 8, kAlphaTicketWords = (1 + kAlphaShards) * kAlphaTicketStride, kAlphaWordsAt = 56;
+    static_assert((uint64_t)kAlphaSlotWords + kAlphaTicketWords <= (uint64_t)8 * 256 * 1024, "slots and tickets fit the radix scratch");
+    static const unsigned flip = [] { const char* e = dev_env("SFX_FINISH_REVERSE"); return (e && atoi(e) != 0) ? 1u : 0u; }();
+    const AlphaStage stage = {b.hist + kAlphaSlotWords, reinterpret_cast<unsigned long long*>(b.hist), b.totals + kAlphaWordsAt, b.lut,
+                              post_ticket(), flip};
+    SFX_HIP(hipMemsetAsync(stage.tickets, 0, kAlphaTicketWords * sizeof(uint32_t), st));
     {
         const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock * 64 - 1) / (kBlock * 64), kMaxGrid);
-        SFX_LAUNCH("byte_presence", (double)n, k_byte_presence, grid, kBlock, st, d_text, n, b.bins);
+        SFX_LAUNCH("byte_presence", (double)n, k_byte_presence, grid, kBlock, st, d_text, n, b.bins, stage);
     }
     Alphabet alpha;
     PackedText pt;
-    SFX_TRY(prepare_text(d_text, n, b.bins, b.lut, b.packed, st, &alpha, &pt));
+    SFX_TRY(prepare_text(d_text, n, b.bins, b.lut, b.packed, st, &alpha, &pt, 0, nullptr, &stage));
     int key_bits, cpk;
     choose_key(alpha, n, &key_bits, &cpk);
     stats.sigma = alpha.sigma;
