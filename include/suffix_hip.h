@@ -767,6 +767,75 @@ int sfx_common_substrings_dev(const uint32_t* d_sa, const uint32_t* d_lcp, const
 int sfx_common_substrings_u32(const uint32_t* sa, const uint32_t* lcp, const uint32_t* df, uint64_t n, const uint64_t* doc_starts,
                               uint64_t ndocs, uint32_t* len_out, uint32_t* pos_out);
 
+/* ---- document listing with term frequencies and top-k per interval -------------------------
+ * Which documents hold a pattern, and how often each?  da[0..n) and doc_starts[0..ndocs) are a collection's arrays as
+ * sfx_build_gsa_u32* takes and writes them; the nq rank intervals [s_j, e_j) with s_j <= e_j <= n are as
+ * sfx_gindex_query* returns them (all occurrences of one string under the truncated-suffix model).  Any rank interval
+ * is legal: a tree node's lb .. rb + 1, or [0, n).
+ *
+ *   tf_j(d)   the number of ranks r in [s_j, e_j) with da[r] == d.
+ *   D_j       the set of documents d with tf_j(d) > 0.  Empty documents never appear.
+ *   order     SFX_DOCLIST_BY_DOC (0): list j holds D_j ascending by document id.
+ *             SFX_DOCLIST_BY_TF (1): descending tf, ties ascending by id.
+ *   top_k     0: the whole list; otherwise the first min(top_k, |D_j|) entries of the list in the chosen order.
+ *   output    CSR: doc[] and tf[] (u32), first[0 .. nq] (u64); list j is [first[j], first[j+1]); first[nq] = Z counts
+ *             entries, not written ones.  The output is determined bit for bit by (da, intervals, order, top_k).
+ *
+ * The index (sfx_doclist): PREV[r] = the previous rank of r's document (or none) and R = the ranks ordered by (document,
+ * rank), both from one stable sort of (da, rank).  Every text position contributes one suffix, so document d's ranks are
+ * R[doc_starts[d] .. doc_end(d)) and tf_j(d) is the difference of two bisections inside that slice.  The object holds
+ * sfx_doclist_bytes(n) = 8n bytes (+ at most 512 of padding); sfx_doclist_create_dev borrows d_da and d_doc_starts (keep
+ * them alive until sfx_doclist_destroy), sfx_doclist_create copies them (4n + 8 ndocs more).
+ * What creation proves: every da entry is < ndocs; doc_starts starts with 0, never decreases and stays <= n; slot k of
+ * the sorted (da, rank) pairs names the document that owns text position k -- hence document d has exactly its length in
+ * ranks.  Otherwise SFX_ERR_ARG, found through the one read-back of a create, with nothing read or written out of bounds.
+ * n == 0 gives a valid empty handle; ndocs == 0 with n > 0 is SFX_ERR_ARG; n or ndocs > u32::MAX SFX_ERR_TOO_LARGE.
+ * Creation scratch: sfx_doclist_create_workspace_bytes(n) <= 24.5 n + 9 MiB bytes of the caller's (any contents), or, with
+ * d_workspace == NULL, of the buffer pool of the host-pointer entry points (sfx_release_cached_buffers() returns it).
+ * occ_cut: intervals longer than occ_cut are listed by document (lanes bisect every document's slice: 2 ndocs log random
+ * lines whatever e - s is), the others by occurrence (PREV is streamed; the first occurrence of a document in the
+ * interval bisects).  0 = automatic, 32 ndocs (measured: DESIGN.md section 24).  Both routes give the same bytes.
+ *
+ * sfx_doclist_list_dev queues on the caller's stream and synchronises it ONCE, to read (Z_full, Z, flags) back; the
+ * ordering of the entries and their copy into d_doc / d_tf are queued behind that read-back, so those two arrays are
+ * complete in stream order (d_first is complete when the call returns).  That queued work reads the workspace: unlike the
+ * other `_dev` calls, keep the workspace alive and unwritten until the stream has passed it (a later call on the SAME
+ * stream may reuse it; freeing it, or using it on another stream, needs a synchronisation or an event first).  A call keeps no state in the object and takes
+ * its memory from the workspace: any number of threads may call on one object, each with its own workspace.
+ *   *listed_out = Z_full = the sum of |D_j|, always.
+ *   Z_full <= list_limit: *count_out = Z, the first min(Z, capacity) entries are written and nothing past them, and
+ *   first (when given) is complete whatever capacity is.
+ *   Z_full > list_limit: SFX_OK, nothing is written to doc, tf or first, and *count_out = 0.  A list_limit above
+ *   u32::MAX counts as u32::MAX.
+ *   SFX_ERR_ARG: order > 1, listed_out / count_out NULL, d_doc or d_tf NULL while capacity > 0, a NULL interval array
+ *   of a non-empty call, an interval with s > e or e > n (found on the device, reported through the same read-back,
+ *   nothing written), a workspace off SFX_WORKSPACE_ALIGN.  nq >= 2^32: SFX_ERR_TOO_LARGE.  A workspace below
+ *   sfx_doclist_workspace_bytes(nq, list_limit) is SFX_ERR_WORKSPACE.  nq == 0 or n == 0: SFX_OK, first all zeros.
+ *   Workspace <= 36 nq + 25 L + 9 MiB bytes, L = min(list_limit, u32::MAX): per interval its item count, three offsets
+ *   and the cut length; per entry two (u64 key, u32 value) pairs for the sort, whose scratch is 8 MiB + L / 2.
+ *   d_start / d_end / d_doc / d_tf need 4-byte alignment, d_first 8.
+ * sfx_doclist_list: the same with host buffers, staged through HBM; it lowers list_limit to the sum of
+ * min(e_j - s_j, ndocs), which Z_full cannot exceed.
+ * Not covered: listing straight from pattern bytes in one call (sfx_gindex_query* gives the intervals), weights other
+ * than tf, the multi-GPU path. */
+#define SFX_DOCLIST_BY_DOC 0u
+#define SFX_DOCLIST_BY_TF 1u
+typedef struct sfx_doclist sfx_doclist;
+uint64_t sfx_doclist_bytes(uint64_t n);
+uint64_t sfx_doclist_create_workspace_bytes(uint64_t n);
+int sfx_doclist_create_dev(const uint32_t* d_da, uint64_t n, const uint64_t* d_doc_starts, uint64_t ndocs, uint64_t occ_cut,
+                           void* d_workspace /* NULL: pooled */, uint64_t workspace_bytes, void* stream, sfx_doclist** out);
+int sfx_doclist_create(const uint32_t* da, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs, uint64_t occ_cut, sfx_doclist** out);
+void sfx_doclist_destroy(sfx_doclist* dx);
+uint64_t sfx_doclist_workspace_bytes(uint64_t nq, uint64_t list_limit);
+int sfx_doclist_list_dev(const sfx_doclist* dx, const uint32_t* d_start, const uint32_t* d_end, uint64_t nq, uint32_t order, uint32_t top_k,
+                         uint64_t list_limit, uint32_t* d_doc, uint32_t* d_tf, uint64_t capacity, uint64_t* d_first /* nq + 1, may be NULL */,
+                         uint64_t* listed_out /* host */, uint64_t* count_out /* host */,
+                         void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_doclist_list(const sfx_doclist* dx, const uint32_t* start, const uint32_t* end, uint64_t nq, uint32_t order, uint32_t top_k,
+                     uint64_t list_limit, uint32_t* doc_out, uint32_t* tf_out, uint64_t capacity, uint64_t* first_out,
+                     uint64_t* listed_out, uint64_t* count_out);
+
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the
  * text shard [shard_begin, shard_end).

@@ -93,6 +93,10 @@ NAMES = [
     ("k_lce_query", "lce_query"), ("k_lce_range_min", "lce_range_min"), ("k_lce_ranks", "lce_ranks"),
     ("k_docs_check", "docs_check"), ("k_docs_argmin", "docs_argmin"), ("k_docs_runs", "docs_runs"), ("k_docs_counts", "docs_counts"),
     ("k_docs_longest", "docs_longest"), ("k_docs_best", "docs_best"), ("k_docs_suffix_max", "docs_suffix_max"),
+    ("k_dl_check", "doclist_check"), ("k_dl_work", "doclist_work"), ("k_dl_count<true>", "doclist_count_docs"), ("k_dl_count<false>", "doclist_count"),
+    ("k_dl_offsets", "doclist_offsets"), ("k_dl_emit<true>", "doclist_emit_docs"), ("k_dl_emit<false>", "doclist_emit"),
+    ("k_dl_first", "doclist_first"), ("k_dl_cut", "doclist_cut"), ("k_dl_publish", "doclist_publish"), ("k_dl_keys", "doclist_keys"),
+    ("k_dl_write", "doclist_write"),
     ("k_ms_search_dir", "ms_search_dir"), ("k_ms_search", "ms_search"), ("k_ms_gsa_search", "ms_gsa_search"),
     # -- not part of a build's profile: the polled read-back and the memory-system probes
     ("detail::k_post_words", "post_words"), ("k_mb_copy", "mb_copy"), ("k_mb_gather", "mb_gather"), ("k_mb_scatter", "mb_scatter"),

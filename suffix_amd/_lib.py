@@ -168,6 +168,16 @@ ABI = [
     ("sfx_common_substrings_workspace_bytes", _u64, [_u64]),
     ("sfx_common_substrings_dev", _int, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp]),
     ("sfx_common_substrings_u32", _int, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
+    ("sfx_doclist_bytes", _u64, [_u64]),
+    ("sfx_doclist_create_workspace_bytes", _u64, [_u64]),
+    ("sfx_doclist_create_dev", _int, [_vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, ctypes.POINTER(_vp)]),
+    ("sfx_doclist_create", _int, [_vp, _u64, _vp, _u64, _u64, ctypes.POINTER(_vp)]),
+    ("sfx_doclist_destroy", None, [_vp]),
+    ("sfx_doclist_workspace_bytes", _u64, [_u64, _u64]),
+    ("sfx_doclist_list_dev", _int, [_vp, _vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64),
+                                    ctypes.POINTER(_u64), _vp, _u64, _vp]),
+    ("sfx_doclist_list", _int, [_vp, _vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64),
+                                ctypes.POINTER(_u64)]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),

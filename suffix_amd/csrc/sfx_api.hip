@@ -19,6 +19,7 @@
 #include "sfx_hamming.hip"  // k-mismatch pattern search, likewise (over sfx_mem.hip's expansion)
 #include "sfx_lce.hip"  // longest common extensions (inverse table + LCP min-tree), likewise
 #include "sfx_docs.hip"  // document counts per lcp-interval and k-common substrings, likewise (over sfx_lce.hip's levels)
+#include "sfx_doclist.hip"  // document listing with term frequencies and top-k, likewise
 
 namespace sfx {
 
@@ -1147,6 +1148,113 @@ int sfx_common_substrings_u32(const uint32_t* sa, const uint32_t* lcp, const uin
                                   (uint32_t*)dn.p, (uint32_t*)dp.p, dw.p, wsb, st));
     SFX_HIP(hipMemcpyAsync(len_out, dn.p, ndocs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     SFX_HIP(hipMemcpyAsync(pos_out, dp.p, ndocs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+
+// ---- document listing with term frequencies and top-k (include/suffix_hip.h) ----------------
+uint64_t sfx_doclist_bytes(uint64_t n) { return doclist_bytes(n); }
+uint64_t sfx_doclist_create_workspace_bytes(uint64_t n) { return doclist_create_workspace_bytes(n); }
+uint64_t sfx_doclist_workspace_bytes(uint64_t nq, uint64_t list_limit) { return doclist_workspace_bytes(nq, list_limit); }
+// d_workspace == NULL: the scratch comes from the pool of the host-pointer entry points, as sfx_lce_create_dev's does
+static int doclist_create_pooled(const uint32_t* d_da, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, uint64_t occ_cut, void* ws,
+                                 uint64_t ws_bytes, hipStream_t st, bool own, sfx_doclist** out)
+{
+    if (ws || !out || n == 0 || n > 0xFFFFFFFFull || ndocs == 0 || ndocs > 0xFFFFFFFFull || !d_da || !d_starts)
+        return doclist_create_dev(d_da, n, d_starts, ndocs, occ_cut, ws, ws_bytes, st, own, out);
+    const uint64_t need = doclist_create_workspace_bytes(n);
+    DevBuf scratch;
+    SFX_TRY(scratch.alloc(need));
+    const int rc = doclist_create_dev(d_da, n, d_starts, ndocs, occ_cut, scratch.p, need, st, own, out);
+    if (rc != SFX_OK) (void)hipStreamSynchronize(st);
+    return rc;
+}
+int sfx_doclist_create_dev(const uint32_t* d_da, uint64_t n, const uint64_t* d_doc_starts, uint64_t ndocs, uint64_t occ_cut, void* d_workspace,
+                           uint64_t workspace_bytes, void* stream, sfx_doclist** out)
+{
+    SFX_NEED_U32(d_da);
+    SFX_NEED_U64(d_doc_starts);
+    SFX_NEED_WS(d_workspace, workspace_bytes, doclist_create_workspace_bytes(n));
+    return doclist_create_pooled(d_da, n, d_doc_starts, ndocs, occ_cut, d_workspace, workspace_bytes, (hipStream_t)stream, false, out);
+}
+int sfx_doclist_create(const uint32_t* da, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs, uint64_t occ_cut, sfx_doclist** out)
+{
+    if (n == 0 || n > 0xFFFFFFFFull || ndocs == 0 || ndocs > 0xFFFFFFFFull || !da || !doc_starts || !out)
+        return doclist_create_dev(nullptr, n, nullptr, ndocs, occ_cut, nullptr, 0, nullptr, false, out);      // (decided on the host)
+    SFX_TRY(check_device());
+    void* d_da = nullptr;
+    void* d_starts = nullptr;
+    hipStream_t st = call_stream();
+    int rc = SFX_OK;
+    {
+        StreamDrain drain{st};
+        rc = [&]() -> int {
+            SFX_HIP(dev_malloc(&d_da, n * sizeof(uint32_t)));                                                // the handle's own copies
+            SFX_HIP(dev_malloc(&d_starts, ndocs * sizeof(uint64_t)));
+            SFX_HIP(hipMemcpyAsync(d_da, da, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            SFX_HIP(hipMemcpyAsync(d_starts, doc_starts, ndocs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            return doclist_create_pooled((const uint32_t*)d_da, n, (const uint64_t*)d_starts, ndocs, occ_cut, nullptr, 0, st, true, out);
+        }();
+    }
+    if (rc != SFX_OK) {
+        if (d_da) (void)dev_free(d_da);
+        if (d_starts) (void)dev_free(d_starts);
+    }
+    return rc;
+}
+void sfx_doclist_destroy(sfx_doclist* dx) { doclist_destroy(dx); }
+int sfx_doclist_list_dev(const sfx_doclist* dx, const uint32_t* d_start, const uint32_t* d_end, uint64_t nq, uint32_t order, uint32_t top_k,
+                         uint64_t list_limit, uint32_t* d_doc, uint32_t* d_tf, uint64_t capacity, uint64_t* d_first, uint64_t* listed_out,
+                         uint64_t* count_out, void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    SFX_NEED_U32(d_start, d_end, d_doc, d_tf);
+    SFX_NEED_U64(d_first);
+    SFX_NEED_WS(d_workspace, workspace_bytes, doclist_workspace_bytes(nq, list_limit));
+    return doclist_list_dev(dx, d_start, d_end, nq, order, top_k, list_limit, d_doc, d_tf, capacity, d_first, listed_out, count_out,
+                            d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sfx_doclist_list(const sfx_doclist* dx, const uint32_t* start, const uint32_t* end, uint64_t nq, uint32_t order, uint32_t top_k,
+                     uint64_t list_limit, uint32_t* doc_out, uint32_t* tf_out, uint64_t capacity, uint64_t* first_out, uint64_t* listed_out,
+                     uint64_t* count_out)
+{
+    if (!dx || !listed_out || !count_out || order > SFX_DOCLIST_BY_TF) return SFX_ERR_ARG;
+    *listed_out = *count_out = 0;
+    if (nq > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (capacity && (!doc_out || !tf_out)) return SFX_ERR_ARG;
+    if (nq == 0 || dx->n == 0) {
+        if (first_out) memset(first_out, 0, (nq + 1) * sizeof(uint64_t));
+        return SFX_OK;
+    }
+    if (!start || !end) return SFX_ERR_ARG;
+    uint64_t bound = 0;                                                    // (Z_full cannot be larger: the workspace need not be either)
+    for (uint64_t j = 0; j < nq; j++) {
+        if (start[j] > end[j] || end[j] > dx->n) return SFX_ERR_ARG;
+        bound += dmin<uint64_t>(end[j] - start[j], dx->ndocs);
+    }
+    SFX_TRY(check_device());
+    list_limit = dmin(list_limit, dmax<uint64_t>(bound, 1));
+    capacity = dmin(capacity, list_limit);
+    const uint64_t wsb = doclist_workspace_bytes(nq, list_limit);
+    DevBuf ds, de, dd, dt, df, dw;
+    SFX_TRY(ds.alloc(nq * sizeof(uint32_t)));
+    SFX_TRY(de.alloc(nq * sizeof(uint32_t)));
+    SFX_TRY(dd.alloc(capacity * sizeof(uint32_t)));
+    SFX_TRY(dt.alloc(capacity * sizeof(uint32_t)));
+    if (first_out) SFX_TRY(df.alloc((nq + 1) * sizeof(uint64_t)));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(ds.p, start, nq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(de.p, end, nq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(doclist_list_dev(dx, (const uint32_t*)ds.p, (const uint32_t*)de.p, nq, order, top_k, list_limit, capacity ? (uint32_t*)dd.p : nullptr,
+                             capacity ? (uint32_t*)dt.p : nullptr, capacity, (uint64_t*)df.p, listed_out, count_out, dw.p, wsb, st));
+    if (*listed_out > list_limit) return SFX_OK;                           // (refused: nothing was written)
+    const uint64_t z = dmin<uint64_t>(*count_out, capacity);
+    if (z) {
+        SFX_HIP(hipMemcpyAsync(doc_out, dd.p, z * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(tf_out, dt.p, z * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    if (first_out) SFX_HIP(hipMemcpyAsync(first_out, df.p, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     SFX_HIP(hipStreamSynchronize(st));
     return SFX_OK;
 }

@@ -656,6 +656,9 @@ int gindex_build_dev(const uint64_t* d_starts, uint64_t ndocs, uint64_t n, const
 // PREV alone (no checks): (K0, V0) / (K1, V1) are n entries each of scratch, radix_scratch as for the sorts
 int gsa_prev_dev(const uint32_t* d_da, uint64_t n, uint64_t ndocs, uint32_t* d_prev, uint64_t* K0, uint32_t* V0, uint64_t* K1, uint32_t* V1,
                  uint32_t* radix_scratch, hipStream_t st);
+// the same, and where the sort left the pairs ordered by (DA, rank): *keys / *ranks (either may be nullptr) point into the scratch
+int gsa_prev_sorted_dev(const uint32_t* d_da, uint64_t n, uint64_t ndocs, uint32_t* d_prev, uint64_t* K0, uint32_t* V0, uint64_t* K1,
+                        uint32_t* V1, uint32_t* radix_scratch, hipStream_t st, const uint64_t** keys, const uint32_t** ranks);
 uint64_t gindex_query_scratch_bytes(uint64_t nq);
 int gindex_query_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_starts, uint64_t ndocs, const uint32_t* d_sa,
                      const uint32_t* d_da, const uint32_t* d_prev, const uint8_t* d_q, const uint64_t* d_qoff, uint64_t nq,

@@ -873,12 +873,21 @@ int gindex_build_dev(const uint64_t* d_starts, uint64_t ndocs, uint64_t n, const
 int gsa_prev_dev(const uint32_t* d_da, uint64_t n, uint64_t ndocs, uint32_t* d_prev, uint64_t* K0, uint32_t* V0, uint64_t* K1, uint32_t* V1,
                  uint32_t* scratch, hipStream_t st)
 {
+    return gsa_prev_sorted_dev(d_da, n, ndocs, d_prev, K0, V0, K1, V1, scratch, st, nullptr, nullptr);
+}
+// ... and where the stable sort left (DA, rank) ordered by (DA, rank), for sfx_doclist.hip: *keys / *ranks point into
+// (K0, V0) or (K1, V1) and stay valid until those are written again
+int gsa_prev_sorted_dev(const uint32_t* d_da, uint64_t n, uint64_t ndocs, uint32_t* d_prev, uint64_t* K0, uint32_t* V0, uint64_t* K1,
+                        uint32_t* V1, uint32_t* scratch, hipStream_t st, const uint64_t** keys, const uint32_t** ranks)
+{
     const unsigned grid = (unsigned)dmin<uint64_t>((n + kBlock - 1) / kBlock, kMaxGrid);
     SFX_LAUNCH("gsa_prev", (double)n * 16, k_gsa_prev_keys, grid, kBlock, st, d_da, n, K0, V0);
     int in1 = 0;
     SFX_TRY(radix_sort_kv64(K0, V0, K1, V1, n, 0, bits_for(ndocs - 1), scratch, st, &in1, nullptr, nullptr));
     SFX_LAUNCH("gsa_prev", (double)n * 16, k_gsa_prev, grid, kBlock, st, (const uint64_t*)(in1 ? K1 : K0), (const uint32_t*)(in1 ? V1 : V0),
                n, d_prev);
+    if (keys) *keys = in1 ? K1 : K0;
+    if (ranks) *ranks = in1 ? V1 : V0;
     return SFX_OK;
 }
 

@@ -922,15 +922,96 @@ class LceDeviceIndex:
     __del__ = close
 
 
+DOCLIST_ORDERS = {"doc": 0, "tf": 1}
+
+
+class DocListDeviceIndex:
+    """Which documents lie in a rank interval of a collection, and how often each: from the device tensors da (uint32 in
+    int32 storage) and doc_starts (int64) of `build_gsa` (sfx_doclist_create_dev).  The handle holds PREV and the ranks
+    ordered by (document, rank), 8n bytes; da and doc_starts are borrowed (kept alive here).  Creation verifies da against
+    doc_starts and synchronises the current stream once.  occ_cut: intervals longer than it are listed by document, the
+    others by occurrence (0 = automatic, 32 ndocs); both give the same arrays."""
+
+    def __init__(self, da, doc_starts, occ_cut=0, engine=None):
+        self._eng = engine or default_engine()
+        _check_u32(da, "da")
+        if doc_starts.dtype != torch.int64 or doc_starts.dim() != 1 or not doc_starts.is_contiguous():
+            raise TypeError("doc_starts must be a contiguous 1-D int64 tensor with one entry per document")
+        if doc_starts.device != da.device:
+            raise ValueError(f"doc_starts must be on the device of da ({da.device})")
+        if da.is_cuda:
+            self._eng.require_device()
+        self._dev, self.n, self.ndocs = da.device, da.numel(), doc_starts.numel()
+        self._keep = (da, doc_starts)                                   # (borrowed by the index: keep them alive)
+        self._on = torch.empty(0, dtype=torch.uint8, device=da.device)
+        h = ctypes.c_void_p()
+        with _on(da):
+            self._eng.check(self._eng.lib.sfx_doclist_create_dev(_p(da), self.n, _p(doc_starts), self.ndocs, int(occ_cut), None, 0,
+                                                                 _stream_ptr(da), ctypes.byref(h)), "sfx_doclist_create_dev")
+        self._h = h
+        self.nbytes = int(self._eng.lib.sfx_doclist_bytes(self.n))
+
+    def workspace(self, nq, list_limit):
+        return torch.empty(int(self._eng.lib.sfx_doclist_workspace_bytes(int(nq), int(list_limit))), dtype=torch.uint8, device=self._dev)
+
+    def list(self, start, end, order="doc", top_k=0, list_limit=1 << 30, capacity=None, workspace=None):
+        """-> (doc, tf, first, listed): list j -- the documents with a rank in [start[j], end[j]) and their counts there,
+        ascending by document (order "doc") or by descending count, ties by document ("tf"), cut to the first top_k
+        entries when top_k > 0 -- is doc / tf [first[j] : first[j + 1]] (uint32 in int32 storage; first int64, nq + 1
+        entries); listed = the number of entries before the cut.  More than list_limit of those raise SuffixHipError.
+        Without a workspace of the caller's, list_limit is lowered to what the interval lengths allow, which reads their
+        sum back (one more synchronisation).  With `capacity` only the first `capacity` entries are returned (first stays
+        complete).  Runs on the current stream and synchronises it once; doc and tf are complete in stream order: the ordering
+        is queued behind that synchronisation and reads the workspace, so a `workspace` of the caller's must stay alive and
+        unwritten until the stream has passed it (the one made here is torch's, which frees in stream order)."""
+        if order not in DOCLIST_ORDERS:
+            raise ValueError(f"order must be one of {sorted(DOCLIST_ORDERS)}")
+        _check_u32(start, "start")
+        nq = start.numel()
+        _check_u32(end, "end", nq)
+        if start.device != self._dev or end.device != self._dev:
+            raise ValueError(f"start and end must be on the index's device ({self._dev})")
+        top_k, list_limit = int(top_k), int(list_limit)
+        if not 0 <= top_k <= 0xFFFFFFFF:
+            raise ValueError("top_k must be in 0 .. 2^32 - 1")
+        if list_limit < 1:
+            raise ValueError("list_limit must be at least 1")
+        if workspace is None:
+            if nq:
+                lens = (end.to(torch.int64) & 0xFFFFFFFF) - (start.to(torch.int64) & 0xFFFFFFFF)
+                list_limit = min(list_limit, max(int(lens.clamp(0, max(self.ndocs, 1)).sum().item()), 1))
+            workspace = self.workspace(nq, list_limit)
+        first = torch.zeros(nq + 1, dtype=torch.int64, device=self._dev)
+        cap = min(list_limit, 0xFFFFFFFF) if capacity is None else int(capacity)
+        doc, tf = (torch.empty(cap, dtype=torch.int32, device=self._dev) for _ in range(2))
+        listed, count = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        with _on(self._on):
+            self._eng.check(self._eng.lib.sfx_doclist_list_dev(self._h, _p(start), _p(end), nq, DOCLIST_ORDERS[order], top_k, list_limit,
+                                                               _p(doc), _p(tf), cap, _p(first), ctypes.byref(listed), ctypes.byref(count),
+                                                               _p(workspace), workspace.numel(), _stream_ptr(self._on)), "sfx_doclist_list_dev")
+        if listed.value > min(list_limit, 0xFFFFFFFF):
+            raise SuffixHipError(f"sfx_doclist_list_dev: {listed.value} entries exceed list_limit = {list_limit}")
+        z = min(int(count.value), cap)
+        return doc[:z], tf[:z], first, int(listed.value)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._eng.lib.sfx_doclist_destroy(h)
+
+    __del__ = close
+
+
 class GeneralizedDeviceIndex:
     """Resident generalized index over device tensors (text, doc_starts, GSA, DA) -- borrowed, keep them alive;
     `query` = per query (start, end, found, any, ndocs): matches inside one document only, ndocs = the number of
     distinct documents that contain the query (sfx_gindex_query_dev)."""
 
-    def __init__(self, text, doc_starts, sa, da, engine=None):
+    def __init__(self, text, doc_starts, sa, da, engine=None, occ_cut=0):
         self._eng = engine or default_engine()
         _check_u8(text)
         self._keep = (text, doc_starts, sa, da)
+        self.occ_cut = int(occ_cut)                 # of the listing index `documents` makes: DocListDeviceIndex's (0 = automatic)
         self._text = text
         h = ctypes.c_void_p()
         with _on(text):
@@ -958,6 +1039,25 @@ class GeneralizedDeviceIndex:
                                                                _p(anyp), _p(ndocs), _stream_ptr(self._text)), "sfx_gindex_query_dev")
         return start, end, found, anyp, ndocs
 
+    def documents(self, qbytes, qoff, order="doc", top_k=0, list_limit=1 << 30, capacity=None):
+        """The documents that hold each query and its count in each: the search (without its count of documents, which
+        walks every occurrence) and then DocListDeviceIndex.list over the intervals -> (doc, tf, first, listed).  The
+        listing index is made on the first call, with the occ_cut given to the constructor, and kept."""
+        dev = self._text.device
+        if qoff.dtype != torch.int64 or qoff.dim() != 1 or not qoff.is_contiguous() or qoff.numel() < 1:
+            raise TypeError("qoff must be a contiguous 1-D int64 tensor of nq + 1 offsets")
+        if qbytes.dtype != torch.uint8 or qbytes.dim() != 1 or not qbytes.is_contiguous() or qbytes.device != dev or qoff.device != dev:
+            raise TypeError(f"qbytes must be a contiguous 1-D uint8 tensor on the index's device ({dev}), as qoff")
+        if getattr(self, "_doclist", None) is None:
+            self._doclist = DocListDeviceIndex(self._keep[3], self._keep[1], occ_cut=self.occ_cut, engine=self._eng)
+        nq = qoff.numel() - 1
+        start = torch.zeros(nq, dtype=torch.int32, device=dev)
+        end = torch.zeros(nq, dtype=torch.int32, device=dev)
+        with _on(self._text):
+            self._eng.check(self._eng.lib.sfx_gindex_query_dev(self._h, _p(qbytes), _p(qoff), nq, _p(start), _p(end), None, None, None,
+                                                               _stream_ptr(self._text)), "sfx_gindex_query_dev")
+        return self._doclist.list(start, end, order=order, top_k=top_k, list_limit=list_limit, capacity=capacity)
+
     def match_stats(self, query, max_len=0, want_src=False, want_interval=False):
         """As the module's match_stats, against the collection: a match lies inside one document, ranks are GSA ranks
         (sfx_gindex_match_stats_dev)."""
@@ -982,6 +1082,9 @@ class GeneralizedDeviceIndex:
                         max_candidates, capacity, workspace)
 
     def close(self):
+        dx, self._doclist = getattr(self, "_doclist", None), None
+        if dx is not None:
+            dx.close()
         h, self._h = getattr(self, "_h", None), None
         if h:
             self._eng.lib.sfx_gindex_destroy(h)

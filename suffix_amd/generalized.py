@@ -10,6 +10,8 @@ no match spans two documents.
     lcp_lens()       common prefix of neighbouring truncated suffixes (0 first)
     positions(q)     [(doc, offset)] of every occurrence of q, in table order
     documents(q)     sorted distinct documents containing q; document_frequency(q) = their number
+    document_listing(q, order, top_k)         (docs, tf): those documents with q's count in each, by id or ranked by count
+    interval_documents(start, end, ...)       the same for any rank interval of the table
     document_counts()             distinct documents under every lcp-interval (per boundary of the table)
     interval_document_frequency(start, end)   the same for any pattern's rank interval, from two prefix sums
     common_substring_lengths()    the longest string common to at least d documents, for every d
@@ -33,6 +35,7 @@ from ._lib import default_engine
 from .table import Mems, _LceHandle, _approx_positions, _as_bytes, _match_stats, _mems, _ptr, _repeat_lens, _repeat_spans, _shared_spans
 
 _NONE = 0xFFFFFFFF
+_DOCLIST_ORDERS = {"doc": 0, "tf": 1}
 
 
 class GeneralizedSuffixTable:
@@ -49,6 +52,7 @@ class GeneralizedSuffixTable:
         self._starts = starts
         self._index = None
         self._lce = _LceHandle(self._eng)
+        self._doclist = None                             # the sfx_doclist handle: made on first use
         self._counts = self._common_arrays = None        # (df, dup_prefix) / (len, pos): made on first use
         n = self._tarr.size
         if n > 0xFFFFFFFF:
@@ -103,6 +107,12 @@ class GeneralizedSuffixTable:
         lx = getattr(self, "_lce", None)
         if lx:
             lx.close()
+        dx, self._doclist = getattr(self, "_doclist", None), None
+        if dx:
+            try:
+                self._eng.lib.sfx_doclist_destroy(dx)
+            except Exception:
+                pass
 
     # -- accessors --------------------------------------------------------------------------
     def table(self):
@@ -208,9 +218,57 @@ class GeneralizedSuffixTable:
         """(document, offset) of some occurrence, or None (the empty query included, as SuffixTable)."""
         return self.any_position_batch([query])[0]
 
-    def documents_batch(self, queries):
+    def _doclist_index(self):
+        """The sfx_doclist handle, made by the first listing (sfx_doclist_create copies da and doc_starts) and kept."""
+        if self._doclist is None:
+            self._eng.require_device()
+            h = ctypes.c_void_p()
+            self._eng.check(self._eng.lib.sfx_doclist_create(_ptr(self._da), self.len(), _ptr(self._starts), self._starts.size, 0,
+                                                             ctypes.byref(h)), "sfx_doclist_create")
+            self._doclist = h
+        return self._doclist
+
+    def _list_intervals(self, start, end, order, top_k):
+        """-> (doc, tf, first) of sfx_doclist_list for the rank intervals [start[j], end[j])."""
+        if order not in _DOCLIST_ORDERS:
+            raise ValueError(f"order must be one of {sorted(_DOCLIST_ORDERS)}")
+        top_k = int(top_k)
+        if not 0 <= top_k <= _NONE:
+            raise ValueError("top_k must be in 0 .. 2^32 - 1")
+        s, e = np.ascontiguousarray(start, dtype=np.uint32), np.ascontiguousarray(end, dtype=np.uint32)
+        nq = int(s.size)
+        first = np.zeros(nq + 1, dtype=np.uint64)
+        cap = int(np.minimum(e.astype(np.int64) - s.astype(np.int64), max(self._starts.size, 1)).sum()) if nq else 0
+        doc, tf = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        if cap:
+            listed, count = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            self._eng.check(self._eng.lib.sfx_doclist_list(self._doclist_index(), _ptr(s), _ptr(e), nq, _DOCLIST_ORDERS[order], top_k, cap,
+                                                           _ptr(doc), _ptr(tf), cap, _ptr(first), ctypes.byref(listed), ctypes.byref(count)),
+                            "sfx_doclist_list")
+            doc, tf = doc[:int(count.value)], tf[:int(count.value)]
+        return doc, tf, first
+
+    def document_listing_batch(self, queries, order="doc", top_k=0):
+        """Per query one (docs, tf) pair of uint32 arrays: the documents that contain it and how often it occurs in each,
+        ascending by document id (order "doc") or by descending count with ties by id ("tf"); top_k > 0 keeps the first
+        top_k entries of that order.  One search and one listing call for the batch."""
         res = self.query_batch(queries)
-        return [sorted(set(self._da[int(s):int(e)].tolist())) for s, e in zip(res["start"], res["end"])]
+        doc, tf, first = self._list_intervals(res["start"], res["end"], order, top_k)
+        return [(doc[int(a):int(b)], tf[int(a):int(b)]) for a, b in zip(first[:-1], first[1:])]
+
+    def document_listing(self, query, order="doc", top_k=0):
+        return self.document_listing_batch([query], order=order, top_k=top_k)[0]
+
+    def interval_documents(self, start, end, order="doc", top_k=0):
+        """(docs, tf) for any rank interval of the table -- table()[start:end], e.g. a tree node's lb .. rb + 1."""
+        start, end = int(start), int(end)
+        if not 0 <= start <= end <= self.len():
+            raise IndexError("interval_documents: not a rank interval of the table")
+        doc, tf, _ = self._list_intervals([start], [end], order, top_k)
+        return doc, tf
+
+    def documents_batch(self, queries):
+        return [d.tolist() for d, _ in self.document_listing_batch(queries)]
 
     def documents(self, query):
         """Sorted distinct ids of the documents that contain `query`."""
