@@ -836,6 +836,60 @@ int sfx_doclist_list(const sfx_doclist* dx, const uint32_t* start, const uint32_
                      uint64_t list_limit, uint32_t* doc_out, uint32_t* tf_out, uint64_t capacity, uint64_t* first_out,
                      uint64_t* listed_out, uint64_t* count_out);
 
+/* ---- maximal repetitions (runs), the Lyndon array, tandem repeats --------------------------
+ * T is a plain text of n bytes, 0 <= n < 2^32 - 1 (larger: SFX_ERR_TOO_LARGE).  Collections are out of scope.
+ *
+ *   run       a triple (b, e, p), 0 <= b < e <= n, p >= 1, such that p is the smallest period of T[b..e), e - b >= 2p,
+ *             b == 0 or T[b-1] != T[b-1+p], and e == n or T[e] != T[e-p].  (b, p) determines e; there are fewer than n runs.
+ *             T[b..e) is its first p bytes written (e - b) / p times in a row: the tandem repeats of T.
+ *   lyn_o[i]  the Lyndon array under order o: o = 0 byte order, o = 1 reversed byte order; in both a proper prefix is smaller
+ *             than its extension.  lyn_o[i] = nss_o(i) - i, nss_o(i) = the least j > i whose suffix is smaller than the suffix
+ *             at i under o, or n.  Over the inverse table of order o: the next j > i with isa_o[j] < isa_o[i].  The table of
+ *             order 1 is the table of the complemented text (byte -> 255 - byte).  T[i .. i + lyn_o[i]) is the longest Lyndon
+ *             word of order o that starts at i.
+ *   Lyndon factorization: the factors start at i_0 = 0, i_{k+1} = i_k + lyn_0[i_k].
+ *
+ * sfx_lyndon_array_dev: d_lyn[0..n) from an inverse table (sfx_inverse_table_dev), queued on the stream: no read-back, no
+ * synchronisation.  d_isa is not verified -- its values are only compared, no address is formed from them.  Workspace
+ * sfx_lyndon_array_workspace_bytes(n) <= 4n + n / 7 + 2 KiB bytes.  sfx_lyndon_array_u32: host buffers; sa == NULL builds the
+ * table of `text` under `order` (0 | 1, anything else SFX_ERR_ARG); a given sa is taken as the table of that order (text may
+ * then be NULL) and must be a permutation of [0, n), else SFX_ERR_ARG.
+ *
+ * sfx_runs_dev: every run that passes the filter (min_period <= p <= max_period, e - b >= min_len; max_period 0 = n; filter
+ * NULL = all), ascending by (begin, period), unique, determined bit for bit by T and the filter.  *count_out is always the
+ * full count; the first min(count, capacity) triples in that order are written and nothing past them; capacity n always
+ * suffices.  d_sa / d_lcp are the tables of T as sfx_build_sa_lcp_u32_dev writes them.  A d_sa that is not a permutation of
+ * [0, n) is SFX_ERR_ARG (proven while its inverse table is made, nothing read or written out of bounds).  d_lcp is not
+ * verified: no address is formed from it, and every reported triple satisfies 0 <= b < e <= n and 2p <= e - b whatever it
+ * holds (with a foreign d_lcp the triples are otherwise unspecified, and at most n are counted).
+ * The call builds the table of the complemented text (sfx_build_sa_u32_dev: its read-backs), then synchronises the stream
+ * ONCE, to read (count, flags) back; the ordering of the triples and their copy into d_begin / d_end / d_period are queued
+ * behind that read-back, so the three arrays are complete in stream order, and the workspace must stay alive and unwritten
+ * until the stream has passed that work (as sfx_doclist_list_dev).  The `_dev` route allocates nothing.
+ *   Workspace: with up(x) = x rounded up to 256 and tw(n) = the words of the 32-ary levels above n words
+ *   (sum of ceil(n / 32^k) rounded up to 32, while the level below has more than 32 words; <= n / 31 + 32 per level),
+ *     sfx_runs_workspace_bytes(n) = up(256) + 2 up(8 * 2048) + 2 up(8 * 2049) + up(n) + 5 up(4n) + up(4 tw(n))
+ *                                   + max(up(sfx_sa_workspace_bytes(n)), late(n)),
+ *     late(n) = up(4 tw(n)) + 3 up(4n) + 2 up(8n) + up(4 s(n)),   s(n) = the words of the radix sort's scratch, <= 2 Mi + n / 8
+ *   hence <= 21.13 n + 80 KiB + max(sfx_sa_workspace_bytes(n) + 256, 28.63 n + 8.1 MiB).
+ *   SFX_ERR_ARG: count_out NULL, a NULL text or table of a non-empty call, an output array NULL while capacity > 0, a
+ *   workspace off SFX_WORKSPACE_ALIGN.  A workspace below sfx_runs_workspace_bytes(n) is SFX_ERR_WORKSPACE.  n == 0: SFX_OK,
+ *   count 0.  d_sa, d_lcp and the three outputs need 4-byte alignment.
+ * sfx_runs_u32: the same with host buffers, staged through the buffer pool; sa == NULL builds both tables, lcp == NULL with
+ * a given sa builds the LCP array (lcp without sa is SFX_ERR_ARG).
+ * Not built: collections, the multi-GPU path, the Rust binding, a direct comparison of the first text bytes in front of the
+ * first extension, the partitioned scatter for the inverse tables of more than 2^27 entries. */
+typedef struct { uint32_t min_period, max_period, min_len, reserved; } sfx_runs_filter_t;
+uint64_t sfx_lyndon_array_workspace_bytes(uint64_t n);
+int sfx_lyndon_array_dev(const uint32_t* d_isa, uint64_t n, uint32_t* d_lyn, void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_lyndon_array_u32(const uint8_t* text, uint64_t n, const uint32_t* sa /* NULL: built */, int order, uint32_t* lyn_out);
+uint64_t sfx_runs_workspace_bytes(uint64_t n);
+int sfx_runs_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint32_t* d_lcp, const sfx_runs_filter_t* filter /* NULL: all */,
+                 uint32_t* d_begin, uint32_t* d_end, uint32_t* d_period, uint64_t capacity, uint64_t* count_out /* host */,
+                 void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_runs_u32(const uint8_t* text, uint64_t n, const uint32_t* sa /* NULL: built */, const uint32_t* lcp /* NULL: built */,
+                 const sfx_runs_filter_t* filter, uint32_t* begin, uint32_t* end, uint32_t* period, uint64_t capacity, uint64_t* count_out);
+
 /* ---- range-partitioned construction (multi-GPU, one rank per GPU) ----------- */
 /* Every rank holds the whole text in HBM (all-gathered over RCCL) and owns the
  * text shard [shard_begin, shard_end).

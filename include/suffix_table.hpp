@@ -9,7 +9,7 @@
 //   tests/tests.rs:18-20; never a fallback of new_) / from_parts / into_parts / lcp_lens / table / text / len / is_empty /
 //   suffix / suffix_bytes / contains / positions / any_position,
 // plus the additive positions_batch / contains_batch, repeat_lens / repeated_spans, bwt / unbwt, lz77 / unlz, mems, approx_positions,
-// inverse_table / lce / lcp_range_min and fm_index (class FmIndex below: the same queries from the transform alone).  Errors that are panics
+// inverse_table / lce / lcp_range_min, runs / lyndon_array / lyndon_factorization and fm_index (class FmIndex below: the same queries from the transform alone).  Errors that are panics
 // in the reference (assert! :380, assert_eq! :117) are std::runtime_error /
 // std::length_error here.  Text is indexed by BYTES (:379).
 #pragma once
@@ -332,6 +332,45 @@ public:
         check(sfx_unlz(len.data(), src.data(), reinterpret_cast<const uint8_t*>(lit.data()), len.size(), n,
                        reinterpret_cast<uint8_t*>(&out[0])), "unlz");
         return out;
+    }
+    // additive: the maximal repetitions (runs) of the text -- its tandem repeats -- and the Lyndon array (suffix_hip.h,
+    // sfx_runs_u32 / sfx_lyndon_array_u32).  runs(): one entry per (begin, end, period) with period the smallest period of
+    // text[begin..end), end - begin >= 2 period, extendable to neither side; ascending by (begin, period); kept when
+    // min_period <= period <= max_period (0: no limit) and end - begin >= min_len.  lyndon_array(order): the length of the
+    // longest Lyndon word starting at every byte under byte order (0) or reversed byte order (1); lyndon_factorization():
+    // the starts of the Lyndon factors.
+    struct Runs {
+        std::vector<uint32_t> begin, end, period;
+        size_t size() const { return begin.size(); }
+        double exponent(size_t k) const { return (double)(end[k] - begin[k]) / (double)period[k]; }
+    };
+    Runs runs(uint32_t min_period = 1, uint32_t max_period = 0, uint32_t min_len = 0) const
+    {
+        const size_t n = text_.size();
+        Runs r{std::vector<uint32_t>(n), std::vector<uint32_t>(n), std::vector<uint32_t>(n)};
+        const sfx_runs_filter_t flt{min_period, max_period, min_len, 0};
+        uint64_t z = 0;
+        if (n)
+            check(sfx_runs_u32(bytes(text_), n, table_.data(), nullptr, &flt, r.begin.data(), r.end.data(), r.period.data(), n, &z), "runs");
+        r.begin.resize((size_t)z);
+        r.end.resize((size_t)z);
+        r.period.resize((size_t)z);
+        return r;
+    }
+    std::vector<uint32_t> lyndon_array(int order = 0) const
+    {
+        if (order != 0 && order != 1) throw std::invalid_argument("lyndon_array: order must be 0 or 1");
+        std::vector<uint32_t> lyn(text_.size());
+        if (!lyn.empty())
+            check(sfx_lyndon_array_u32(bytes(text_), text_.size(), order == 0 ? table_.data() : nullptr, order, lyn.data()), "lyndon_array");
+        return lyn;
+    }
+    std::vector<uint32_t> lyndon_factorization() const
+    {
+        const std::vector<uint32_t> lyn = lyndon_array(0);
+        std::vector<uint32_t> starts;
+        for (size_t i = 0; i < lyn.size(); i += lyn[i]) starts.push_back((uint32_t)i);
+        return starts;
     }
 
 private:

@@ -97,6 +97,9 @@ NAMES = [
     ("k_dl_offsets", "doclist_offsets"), ("k_dl_emit<true>", "doclist_emit_docs"), ("k_dl_emit<false>", "doclist_emit"),
     ("k_dl_first", "doclist_first"), ("k_dl_cut", "doclist_cut"), ("k_dl_publish", "doclist_publish"), ("k_dl_keys", "doclist_keys"),
     ("k_dl_write", "doclist_write"),
+    ("k_runs_complement", "runs_complement"), ("k_runs_lyndon_tile", "runs_lyndon_tile"), ("k_runs_lyndon_open", "runs_lyndon_open"),
+    ("k_runs_candidates", "runs_candidates"), ("k_runs_offsets", "runs_offsets"), ("k_runs_compact", "runs_compact"),
+    ("k_runs_extend", "runs_extend"), ("k_runs_gather", "runs_gather"), ("k_runs_write", "runs_write"),
     ("k_ms_search_dir", "ms_search_dir"), ("k_ms_search", "ms_search"), ("k_ms_gsa_search", "ms_gsa_search"),
     # -- not part of a build's profile: the polled read-back and the memory-system probes
     ("detail::k_post_words", "post_words"), ("k_mb_copy", "mb_copy"), ("k_mb_gather", "mb_gather"), ("k_mb_scatter", "mb_scatter"),

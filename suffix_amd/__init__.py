@@ -8,8 +8,8 @@ points for torch tensors, and the range-partitioned multi-GPU build.
 """
 from ._lib import Engine, SuffixHipError, default_engine  # noqa: F401
 from .generalized import GeneralizedSuffixTable  # noqa: F401
-from .table import FmIndex, LzFactorization, Mems, SuffixTable, unbwt, unlz  # noqa: F401
+from .table import FmIndex, LzFactorization, Mems, Runs, SuffixTable, unbwt, unlz  # noqa: F401
 from .tree import SuffixTree  # noqa: F401
 
 __all__ = ["SuffixTable", "SuffixTree", "GeneralizedSuffixTable", "FmIndex", "Engine", "SuffixHipError", "default_engine", "unbwt",
-           "LzFactorization", "unlz", "Mems"]
+           "LzFactorization", "unlz", "Mems", "Runs"]

@@ -55,6 +55,10 @@ class ResourceStats(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
+class RunsFilter(ctypes.Structure):
+    _fields_ = [("min_period", _u32), ("max_period", _u32), ("min_len", _u32), ("reserved", _u32)]
+
+
 # every symbol include/suffix_hip.h declares: (name, restype, argtypes)
 ABI = [
     ("sfx_strerror", ctypes.c_char_p, [_int]),
@@ -178,6 +182,12 @@ ABI = [
                                     ctypes.POINTER(_u64), _vp, _u64, _vp]),
     ("sfx_doclist_list", _int, [_vp, _vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64),
                                 ctypes.POINTER(_u64)]),
+    ("sfx_lyndon_array_workspace_bytes", _u64, [_u64]),
+    ("sfx_lyndon_array_dev", _int, [_vp, _u64, _vp, _vp, _u64, _vp]),
+    ("sfx_lyndon_array_u32", _int, [_vp, _u64, _vp, _int, _vp]),
+    ("sfx_runs_workspace_bytes", _u64, [_u64]),
+    ("sfx_runs_dev", _int, [_vp, _u64, _vp, _vp, ctypes.POINTER(RunsFilter), _vp, _vp, _vp, _u64, ctypes.POINTER(_u64), _vp, _u64, _vp]),
+    ("sfx_runs_u32", _int, [_vp, _u64, _vp, _vp, ctypes.POINTER(RunsFilter), _vp, _vp, _vp, _u64, ctypes.POINTER(_u64)]),
     ("sfx_byte_histogram_dev", _int, [_vp, _u64, _u64, _vp, _vp]),
     ("sfx_key_histogram_dev", _int, [_vp, _u64, _u64, _u64, _vp, _int, _vp, _vp]),
     ("sfx_sa_range_workspace_bytes", _u64, [_u64, _u64]),

@@ -18,6 +18,7 @@
 #include "sfx_mem.hip"  // maximal exact matches, likewise
 #include "sfx_hamming.hip"  // k-mismatch pattern search, likewise (over sfx_mem.hip's expansion)
 #include "sfx_lce.hip"  // longest common extensions (inverse table + LCP min-tree), likewise
+#include "sfx_runs.hip"  // Lyndon arrays and maximal repetitions (runs) of a plain text, likewise (over sfx_lce.hip's tables)
 #include "sfx_docs.hip"  // document counts per lcp-interval and k-common substrings, likewise (over sfx_lce.hip's levels)
 #include "sfx_doclist.hip"  // document listing with term frequencies and top-k, likewise
 
@@ -1255,6 +1256,102 @@ int sfx_doclist_list(const sfx_doclist* dx, const uint32_t* start, const uint32_
         SFX_HIP(hipMemcpyAsync(tf_out, dt.p, z * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     if (first_out) SFX_HIP(hipMemcpyAsync(first_out, df.p, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+
+// ---- Lyndon arrays and maximal repetitions (runs) of a plain text (include/suffix_hip.h) ----------------------------
+uint64_t sfx_lyndon_array_workspace_bytes(uint64_t n) { return lyndon_array_workspace_bytes(n); }
+int sfx_lyndon_array_dev(const uint32_t* d_isa, uint64_t n, uint32_t* d_lyn, void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    SFX_NEED_U32(d_isa, d_lyn);
+    SFX_NEED_WS(d_workspace, workspace_bytes, lyndon_array_workspace_bytes(n));
+    return lyndon_array_dev(d_isa, n, d_lyn, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sfx_lyndon_array_u32(const uint8_t* text, uint64_t n, const uint32_t* sa, int order, uint32_t* lyn_out)
+{
+    if (order != 0 && order != 1) return SFX_ERR_ARG;
+    if (n > kRunsMaxN) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if ((!sa && !text) || !lyn_out) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    const uint64_t bytes = n * sizeof(uint32_t);
+    const uint64_t wsb = dmax(sa ? 0 : sa_workspace_bytes(n), lyndon_array_workspace_bytes(n));
+    DevBuf dt, ds, di, dl, dw;
+    if (!sa) SFX_TRY(dt.alloc(n));
+    SFX_TRY(ds.alloc(bytes));
+    SFX_TRY(di.alloc(bytes));
+    SFX_TRY(dl.alloc(bytes));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    if (sa) {
+        SFX_HIP(hipMemcpyAsync(ds.p, sa, bytes, hipMemcpyHostToDevice, st));
+    } else {
+        SFX_HIP(hipMemcpyAsync(dt.p, text, n, hipMemcpyHostToDevice, st));
+        if (order == 1) SFX_LAUNCH("runs_complement", (double)n * 2, k_runs_complement, lce_grid(n), kBlock, st, (const uint8_t*)dt.p, n, (uint8_t*)dt.p);
+        SFX_TRY(build_sa_u32_dev((const uint8_t*)dt.p, n, (uint32_t*)ds.p, dw.p, wsb, st));
+    }
+    SFX_TRY(lyndon_from_table_dev((const uint32_t*)ds.p, n, (uint32_t*)di.p, (uint32_t*)dl.p, dw.p, wsb, st));
+    SFX_HIP(hipMemcpyAsync(lyn_out, dl.p, bytes, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+uint64_t sfx_runs_workspace_bytes(uint64_t n) { return runs_workspace_bytes(n); }
+int sfx_runs_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint32_t* d_lcp, const sfx_runs_filter_t* filter, uint32_t* d_begin,
+                 uint32_t* d_end, uint32_t* d_period, uint64_t capacity, uint64_t* count_out, void* d_workspace, uint64_t workspace_bytes,
+                 void* stream)
+{
+    SFX_NEED_U32(d_sa, d_lcp, d_begin, d_end, d_period);
+    SFX_NEED_WS(d_workspace, workspace_bytes, runs_workspace_bytes(n));
+    return runs_dev(d_text, n, d_sa, d_lcp, filter, d_begin, d_end, d_period, capacity, count_out, d_workspace, workspace_bytes,
+                    (hipStream_t)stream);
+}
+int sfx_runs_u32(const uint8_t* text, uint64_t n, const uint32_t* sa, const uint32_t* lcp, const sfx_runs_filter_t* filter, uint32_t* begin,
+                 uint32_t* end, uint32_t* period, uint64_t capacity, uint64_t* count_out)
+{
+    if (!count_out) return SFX_ERR_ARG;
+    *count_out = 0;
+    if (n > kRunsMaxN) return SFX_ERR_TOO_LARGE;
+    if (n == 0) return SFX_OK;
+    if (!text || (lcp && !sa) || (capacity && (!begin || !end || !period))) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    if (capacity > n) capacity = n;                                      // (fewer than n runs)
+    const uint64_t bytes = n * sizeof(uint32_t);
+    const uint64_t wsb = dmax(sa ? (lcp ? 0 : lcp_workspace_bytes(n)) : sa_lcp_workspace_bytes(n), runs_workspace_bytes(n));
+    DevBuf dt, ds, dl, dout, dw;
+    SFX_TRY(dt.alloc(n));
+    SFX_TRY(ds.alloc(bytes));
+    SFX_TRY(dl.alloc(bytes));
+    ArenaSizer osz;
+    for (int i = 0; i < 3; i++) osz.take<uint32_t>(capacity);
+    SFX_TRY(dout.alloc(osz.used));
+    Arena oa(dout.p, dmax<uint64_t>(osz.used, 1));
+    uint32_t* const db = oa.take<uint32_t>(capacity);
+    uint32_t* const de = oa.take<uint32_t>(capacity);
+    uint32_t* const dp = oa.take<uint32_t>(capacity);
+    if (oa.overflow) return SFX_ERR_INTERNAL;
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(dt.p, text, n, hipMemcpyHostToDevice, st));
+    if (!sa) {
+        SFX_TRY(build_sa_lcp_u32_dev((const uint8_t*)dt.p, n, (uint32_t*)ds.p, (uint32_t*)dl.p, dw.p, wsb, st));
+    } else {
+        SFX_HIP(hipMemcpyAsync(ds.p, sa, bytes, hipMemcpyHostToDevice, st));
+        if (lcp)
+            SFX_HIP(hipMemcpyAsync(dl.p, lcp, bytes, hipMemcpyHostToDevice, st));
+        else
+            SFX_TRY(build_lcp_u32_dev((const uint8_t*)dt.p, n, (const uint32_t*)ds.p, (uint32_t*)dl.p, dw.p, wsb, st));
+    }
+    SFX_TRY(runs_dev((const uint8_t*)dt.p, n, (const uint32_t*)ds.p, (const uint32_t*)dl.p, filter, db, de, dp,
+                     capacity, count_out, dw.p, wsb, st));
+    const uint64_t k = dmin<uint64_t>(*count_out, capacity);
+    if (k) {
+        SFX_HIP(hipMemcpyAsync(begin, db, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(end, de, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(period, dp, k * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
     SFX_HIP(hipStreamSynchronize(st));
     return SFX_OK;
 }

@@ -594,6 +594,14 @@ int doc_counts_dev(const uint32_t* d_da, const uint32_t* d_lcp, uint64_t n, uint
 uint64_t common_substrings_workspace_bytes(uint64_t ndocs);
 int common_substrings_dev(const uint32_t* d_sa, const uint32_t* d_lcp, const uint32_t* d_df, uint64_t n, const uint64_t* d_starts,
                           uint64_t ndocs, uint32_t* d_len, uint32_t* d_pos, void* ws, uint64_t ws_bytes, hipStream_t st);
+// Lyndon arrays and maximal repetitions (runs) of a plain text (sfx_runs.hip); runs_dev synchronises the stream once for
+// (count, flags), lyndon_array_dev not at all
+uint64_t lyndon_array_workspace_bytes(uint64_t n);
+int lyndon_array_dev(const uint32_t* d_isa, uint64_t n, uint32_t* d_lyn, void* ws, uint64_t ws_bytes, hipStream_t st);
+int lyndon_from_table_dev(const uint32_t* d_sa, uint64_t n, uint32_t* d_isa, uint32_t* d_lyn, void* ws, uint64_t ws_bytes, hipStream_t st);
+uint64_t runs_workspace_bytes(uint64_t n);
+int runs_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, const uint32_t* d_lcp, const sfx_runs_filter_t* filter, uint32_t* d_begin,
+             uint32_t* d_end, uint32_t* d_period, uint64_t capacity, uint64_t* count_out, void* ws, uint64_t ws_bytes, hipStream_t st);
 // bucket directory of the resident index (sfx_query.hip)
 int dir_shape(uint64_t n, int bits, int* k_out, int* dbits_out, uint64_t* entries_out);
 uint64_t dir_scratch_words(uint64_t entries);

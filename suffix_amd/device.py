@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from ._lib import REP_SCOPES, FmInfo, SuffixHipError, default_engine
+from ._lib import REP_SCOPES, FmInfo, RunsFilter, SuffixHipError, default_engine
 
 
 def _on(t):
@@ -787,6 +787,73 @@ def inverse_table(sa, out=None, workspace=None, engine=None):
         eng.check(eng.lib.sfx_inverse_table_dev(_p(sa), n, _p(out), _p(workspace), workspace.numel(), _stream_ptr(sa)),
                   "sfx_inverse_table_dev")
     return out
+
+
+def lyndon_array_workspace(n, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_lyndon_array_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def lyndon_array(isa, out=None, workspace=None, engine=None):
+    """The Lyndon array of the order whose inverse table isa is (inverse_table of the text's table: byte order; of the
+    complemented text's table: reversed byte order): lyn[i] = the distance to the next j > i with isa[j] < isa[i], or to
+    n.  uint32 in int32 storage; queued on the current stream, nothing is read back (sfx_lyndon_array_dev)."""
+    eng = engine or default_engine()
+    _check_u32(isa, "isa")
+    n = isa.numel()
+    if isa.is_cuda:
+        eng.require_device()
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=isa.device)
+    _check_u32(out, "out", n)
+    if workspace is None:
+        workspace = lyndon_array_workspace(n, isa.device, eng)
+    with _on(isa):
+        eng.check(eng.lib.sfx_lyndon_array_dev(_p(isa), n, _p(out), _p(workspace), workspace.numel(), _stream_ptr(isa)),
+                  "sfx_lyndon_array_dev")
+    return out
+
+
+def runs_workspace(n, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_runs_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def runs(text, sa, lcp, min_period=1, max_period=None, min_len=0, capacity=None, workspace=None, engine=None):
+    """The maximal repetitions (runs) of a plain text from its table and LCP array (uint32 in int32 storage, on the
+    text's device): every (begin, end, period) with period the smallest period of text[begin:end], end - begin >= 2 *
+    period, and no extension to either side; min_period <= period <= max_period (None: n) and end - begin >= min_len.
+    -> (begin, end, period, count): three int32 tensors cut to min(count, capacity) triples ascending by (begin,
+    period), and the full count.  capacity None: n, which always suffices.  Synchronises the current stream once for
+    the count; the three arrays are complete in stream order (sfx_runs_dev)."""
+    eng = engine or default_engine()
+    _check_u8(text)
+    n = text.numel()
+    _check_u32(sa, "sa", n)
+    _check_u32(lcp, "lcp", n)
+    for t in (sa, lcp):
+        if t.device != text.device:
+            raise ValueError(f"all arrays must be on one device ({text.device})")
+    if max_period is not None and int(max_period) < 1:
+        raise ValueError("max_period must be at least 1 (None: no limit)")
+    for v in (min_period, min_len, max_period or 0):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("filters must be in 0 .. 2^32 - 1")
+    flt = RunsFilter(int(min_period), 0 if max_period is None else int(max_period), int(min_len), 0)
+    if text.is_cuda:
+        eng.require_device()
+    cap = n if capacity is None else int(capacity)
+    dev = text.device
+    begin, end, period = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
+    if workspace is None:
+        workspace = runs_workspace(n, dev, eng)
+    count = ctypes.c_uint64(0)
+    with _on(text):
+        eng.check(eng.lib.sfx_runs_dev(_p(text), n, _p(sa), _p(lcp), ctypes.byref(flt), _p(begin), _p(end), _p(period), cap,
+                                       ctypes.byref(count), _p(workspace), workspace.numel(), _stream_ptr(text)), "sfx_runs_dev")
+    z = int(count.value)
+    k = min(z, cap)
+    return begin[:k].clone(), end[:k].clone(), period[:k].clone(), z
 
 
 def doc_counts_workspace(n, device, engine=None):

@@ -23,6 +23,7 @@ Same method names, argument meaning and error behaviour as the Rust API:
     (none)                                   .bwt(sample_step) / suffix_amd.unbwt(bwt, samples, sample_step)
     (none)                                   .fm_index(sample_step) / suffix_amd.FmIndex: the same queries from the transform alone
     (none)                                   .inverse_table() / .lce(i, j, mismatches) / .lce_batch / .lcp_range_min[_batch]
+    (none)                                   .runs(min_period, max_period, min_len) / .lyndon_array(order) / .lyndon_factorization()
 
 Text is indexed by BYTES (every UTF-8 byte offset has a suffix, :29-31 of the
 crate docs and :379); `str` input is encoded as UTF-8.  Construction, LCP and
@@ -32,7 +33,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import REP_SCOPES, FmInfo, SuffixHipError, default_engine
+from ._lib import REP_SCOPES, FmInfo, RunsFilter, SuffixHipError, default_engine
 
 _NONE = 0xFFFFFFFF
 
@@ -327,6 +328,28 @@ class LzFactorization:
         return f"LzFactorization(n={self.n}, z={len(self)})"
 
 
+class Runs:
+    """The maximal repetitions of a text (SuffixTable.runs): uint32 arrays begin / end / period, one entry per run,
+    ascending by (begin, period).  text[begin:end] has smallest period `period`, is at least two periods long and cannot be
+    extended to either side; exponent = (end - begin) / period says how often the unit is written."""
+
+    def __init__(self, begin, end, period, n):
+        self.begin, self.end, self.period, self.n = begin, end, period, int(n)
+
+    def __len__(self):
+        return int(self.begin.size)
+
+    def triples(self):
+        return list(zip(self.begin.tolist(), self.end.tolist(), self.period.tolist()))
+
+    @property
+    def exponent(self):
+        return (self.end.astype(np.float64) - self.begin) / self.period
+
+    def __repr__(self):
+        return f"Runs(n={self.n}, runs={len(self)})"
+
+
 class SuffixTable:
     def __init__(self, text, _table=None, engine=None):
         self._eng = engine or default_engine()
@@ -576,6 +599,50 @@ class SuffixTable:
                                                        n, ctypes.byref(count)), "sfx_lz77_u32")
         z = int(count.value)
         return LzFactorization(*[a[:z].copy() for a in arrs], n, engine=self._eng)
+
+    # -- maximal repetitions, Lyndon array ------------------------------------------------------------
+    def lyndon_array(self, order=0):
+        """lyn (uint32): lyn[i] = the length of the longest Lyndon word that starts at byte i, under byte order (order
+        0) or reversed byte order (order 1); in both a proper prefix is smaller than its extension.  Order 1 builds the
+        table of the complemented text (sfx_lyndon_array_u32)."""
+        if order not in (0, 1):
+            raise ValueError("order must be 0 (byte order) or 1 (reversed byte order)")
+        n = self.len()
+        lyn = np.zeros(n, dtype=np.uint32)
+        if n:
+            self._eng.require_device()
+            self._eng.check(self._eng.lib.sfx_lyndon_array_u32(_ptr(self._tarr), n, _ptr(self._table) if order == 0 else None, order,
+                                                               _ptr(lyn)), "sfx_lyndon_array_u32")
+        return lyn
+
+    def lyndon_factorization(self):
+        """The starts (int64) of the Lyndon factors of the text: 0, then every start plus the Lyndon word at it."""
+        lyn = self.lyndon_array(0)
+        starts, i, n = [], 0, self.len()
+        while i < n:
+            starts.append(i)
+            i += int(lyn[i])
+        return np.asarray(starts, dtype=np.int64)
+
+    def runs(self, min_period=1, max_period=None, min_len=0):
+        """The maximal repetitions (Runs) -- the tandem repeats of the text: every (begin, end, period) such that period
+        is the smallest period of text[begin:end], end - begin >= 2 * period and the repetition extends to neither side;
+        kept when min_period <= period <= max_period (None: no limit) and end - begin >= min_len."""
+        if max_period is not None and int(max_period) < 1:
+            raise ValueError("max_period must be at least 1 (None: no limit)")
+        for v in (min_period, min_len, max_period or 0):
+            if not 0 <= int(v) <= _NONE:
+                raise ValueError("filters must be in 0 .. 2^32 - 1")
+        n = self.len()
+        arrs = [np.zeros(n, dtype=np.uint32) for _ in range(3)]
+        count = ctypes.c_uint64(0)
+        flt = RunsFilter(int(min_period), 0 if max_period is None else int(max_period), int(min_len), 0)
+        if n:
+            self._eng.require_device()
+            self._eng.check(self._eng.lib.sfx_runs_u32(_ptr(self._tarr), n, _ptr(self._table), None, ctypes.byref(flt),
+                                                       *[_ptr(a) for a in arrs], n, ctypes.byref(count)), "sfx_runs_u32")
+        z = int(count.value)
+        return Runs(*[a[:z].copy() for a in arrs], n)
 
     def fm_index(self, sample_step=64, occ_step=0):
         """An FmIndex over this table's transform: the same positions() / contains() / count() from about 1.4 n bytes

@@ -3,7 +3,7 @@
 // over the MI355X engine's C++ host mirror (include/suffix_table.hpp -> libsuffix_hip.so),
 // extended into the large-file driver SURVEY.md 8(f) asks for:
 //
-//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q [--mismatches K]]... [--repeats L [--earlier]] [--lce I,J[,I,J...] [--mismatches K]] [--isa] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]
+//   suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q [--mismatches K]]... [--repeats L [--earlier]] [--lce I,J[,I,J...] [--mismatches K]] [--isa] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--runs [--min-period P] [--max-period Q] [--min-len L]] [--lyndon] [--time]
 //
 //   --dump PREFIX   write PREFIX.sa (and PREFIX.lcp with --lcp) as raw little-endian u32
 //                   arrays -- the on-disk form SuffixTable::from_parts (:111-119) reloads
@@ -45,6 +45,11 @@
 //   suffix-array PREFIX.lz --unlz --out OUT
 //                   restore the file from a factorization (no table is built); a truncated or corrupted one ends with
 //                   status 2 and a message, and OUT is not written
+//   --runs [--min-period P] [--max-period Q] [--min-len L]
+//                   the maximal repetitions (tandem repeats) of FILE: "Runs: Z", then one "begin end period" line per run --
+//                   FILE[begin .. end) has smallest period `period`, is at least two periods long and extends to neither
+//                   side -- ascending by (begin, period); only periods in P .. Q and runs of at least L bytes (defaults: all)
+//   --lyndon        the Lyndon factorization of FILE under byte order: "Lyndon factors: K", then one factor start per line
 //   --time          wall-clock milliseconds of construction / LCP (host pointers, i.e.
 //                   including the PCIe copies: the device-resident rate is bench.py's)
 //
@@ -96,7 +101,8 @@ int main(int argc, char** argv)
     std::vector<std::string> queries;
     bool want_lcp = false, timing = false, earlier = false, unlz = false, min_len_given = false, unique = false, max_pairs_given = false;
     long long repeats = -1, mismatches = 0;
-    bool want_isa = false, mismatches_given = false;
+    bool want_isa = false, mismatches_given = false, want_runs = false, want_lyndon = false;
+    long long min_period = 1, max_period = 0;
     std::vector<uint32_t> lce_pos;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -121,6 +127,13 @@ int main(int argc, char** argv)
             if (mems < 1 || mems > 0xFFFFFFFFll) { fprintf(stderr, "--mems needs a length of at least 1\n"); return 1; }
         }
         else if (a == "--unique") unique = true;
+        else if (a == "--runs") want_runs = true;
+        else if (a == "--lyndon") want_lyndon = true;
+        else if (a == "--min-period" || a == "--max-period") {
+            const long long v = atoll(need(a.c_str()));
+            if (v < 1 || v > 0xFFFFFFFFll) { fprintf(stderr, "%s needs a period of at least 1\n", a.c_str()); return 1; }
+            (a == "--min-period" ? min_period : max_period) = v;
+        }
         else if (a == "--isa") want_isa = true;
         else if (a == "--lce") {
             // I,J[,I,J...]: an even number of positions
@@ -175,8 +188,9 @@ int main(int argc, char** argv)
     if (approx && (mismatches > 255 || !fm.empty())) { fprintf(stderr, "--query Q --mismatches K needs K <= 255 and a text, not a transform (--fm)\n"); return 1; }
     if (mems > 0 && min_len_given && lz.empty()) { fprintf(stderr, "--mems L takes its length itself: --min-len belongs to the span report of --match alone\n"); return 1; }
     if (mems < 0 && (unique || max_pairs_given)) { fprintf(stderr, "--unique and --max-pairs need --mems L\n"); return 1; }
+    if (!want_runs && (min_period != 1 || max_period != 0)) { fprintf(stderr, "--min-period and --max-period need --runs\n"); return 1; }
     if (file.empty()) {
-        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q [--mismatches K]]... [--repeats L [--earlier]] [--lce I,J[,I,J...] [--mismatches K]] [--isa] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--time]\n       suffix-array PREFIX.lz --unlz --out OUT\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
+        fprintf(stderr, "usage: suffix-array FILE [--lcp] [--dump PREFIX] [--load PREFIX] [--query Q [--mismatches K]]... [--repeats L [--earlier]] [--lce I,J[,I,J...] [--mismatches K]] [--isa] [--match FILE2 [--min-len L | --mems L [--unique] [--max-pairs P]]] [--bwt PREFIX [--step S]] [--lz PREFIX [--min-len L]] [--runs [--min-period P] [--max-period Q] [--min-len L]] [--lyndon] [--time]\n       suffix-array PREFIX.lz --unlz --out OUT\n       suffix-array PREFIX.bwt --fm PREFIX.bwi --query Q... [--occ-step B]\n");
         return 1;
     }
     std::string text;
@@ -349,6 +363,20 @@ int main(int argc, char** argv)
             for (const auto& be : spans) covered += be.second - be.first;
             std::cout << "Shared with " << match << " (>= " << min_len << " bytes): " << spans.size() << " spans, " << covered << " bytes\n";
             for (const auto& be : spans) std::cout << be.first << " " << be.second << " " << ms.src[be.first] << "\n";
+        }
+        if (want_runs) {
+            t0 = std::chrono::steady_clock::now();
+            const auto r = st.runs((uint32_t)min_period, (uint32_t)max_period, min_len_given ? (uint32_t)min_len : 0u);
+            if (timing) std::cout << "runs ms: " << ms_since(t0) << "\n";
+            std::cout << "Runs: " << r.size() << "\n";
+            for (size_t k = 0; k < r.size(); k++) std::cout << r.begin[k] << " " << r.end[k] << " " << r.period[k] << "\n";
+        }
+        if (want_lyndon) {
+            t0 = std::chrono::steady_clock::now();
+            const auto starts = st.lyndon_factorization();
+            if (timing) std::cout << "lyndon ms: " << ms_since(t0) << "\n";
+            std::cout << "Lyndon factors: " << starts.size() << "\n";
+            for (uint32_t b : starts) std::cout << b << "\n";
         }
         if (!bwt.empty()) {
             t0 = std::chrono::steady_clock::now();
