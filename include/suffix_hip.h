@@ -628,8 +628,8 @@ int sfx_gindex_mems(const sfx_gindex* gx, const uint8_t* query, uint64_t m, uint
  *   text's suffix array is unspecified.  sfx_index_hamming_dev searches the pieces through the bucket directory and
  *   the key tree, sfx_gindex_hamming_dev with the collection's search.
  * sfx_index_hamming / sfx_gindex_hamming: the same with host buffers, staged through HBM.
- * Not covered: edit distance (insertions and deletions), search over the FM-index, wildcards, per-pattern k, the
- * multi-GPU path. */
+ * Not covered: search over the FM-index, wildcards, per-pattern k, the multi-GPU path.  (Insertions and deletions:
+ * the k-error search further down.) */
 uint64_t sfx_hamming_workspace_bytes(uint64_t nq, uint32_t max_mismatches, uint64_t cand_limit);
 int sfx_hamming_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
                     const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq, uint32_t max_mismatches, uint64_t cand_limit,
@@ -652,6 +652,88 @@ int sfx_index_hamming(const sfx_index* ix, const uint8_t* qbytes, const uint64_t
 int sfx_gindex_hamming(const sfx_gindex* gx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq, uint32_t max_mismatches,
                        uint64_t cand_limit, uint32_t* pattern_out, uint32_t* tpos_out, uint8_t* mism_out, uint64_t capacity,
                        uint64_t* first_out, uint64_t* cands_out, uint64_t* count_out);
+
+/* ---- k-error pattern search against the table ----------------------------------------------
+ * Where does a pattern occur if up to k bytes may be substituted, inserted or deleted (unit-cost Levenshtein distance)?
+ * T = the indexed text of n bytes with table sa.  Patterns arrive as qbytes / qoff, exactly as for
+ * sfx_index_hamming_dev; m_j = the length of pattern j, k = max_errors, 0 <= k <= 31.  Every pattern needs
+ * m_j >= k + 1 (a shorter one would occur at every position).
+ *   occurrence   of pattern j: an end position e for which some s <= e has ed(P_j, T[s..e)) <= k, T[s..e) inside one
+ *                document for a collection (the truncated-suffix model).  dist = the least such distance over s,
+ *                tbegin = the LARGEST s that attains it (the shortest best alignment), tend = e.  The triple is a
+ *                property of (T, doc_starts, P_j, k) alone.
+ *   pieces       as for the k-mismatch search: pattern j is cut at b_t = floor(t * m_j / (k + 1)); no piece is empty.
+ *   candidates   triples (j, t, r), r a rank in the exact interval of piece t, numbered ascending by j, t, r; C of
+ *                them.  q = sa[r], qe = q + |piece t|; lo / hi = the bounds of the text, or of q's document.
+ *                left value   L = min over s in [max(lo, q - b_t - k), q] of ed(P_j[0..b_t), T[s..q)), s* = the largest
+ *                             s that attains L
+ *                right values R(e) = ed(P_j[b_(t+1)..m_j), T[qe..e)) for e in [qe, min(hi, qe + m_j - b_(t+1) + k)]
+ *   hits         a candidate yields a hit (j, e, L + R(e), s*) for every e with L + R(e) <= k; H hits in all.  An
+ *                alignment with at most k edits leaves one piece untouched, so it passes through a candidate, and its
+ *                two parts cost at least L and R(e), while L + R(e) is itself the cost of an alignment: the occurrence
+ *                at (j, e) has dist = the least L + R(e) over its hits and tbegin = the largest s* among the hits that
+ *                attain it.  Expect several hits per occurrence.
+ *   output       the quadruples (pattern, tbegin, tend, dist), ascending by pattern, then by tend; Z = the number of
+ *                distinct (j, e).  first[0 .. nq] (u64) in CSR form, complete whatever `capacity` is; first[nq] = Z.
+ *                Determined bit for bit by the inputs.  At k = 0 the quadruples of pattern j are (p, p + m_j, 0) for
+ *                the positions p of the exact search, ascending by p.
+ * Work is proportional to C times the pattern length in the worst case (an extension is abandoned once every cell of
+ * its band is above the budget) plus a sort of the H hits: the caller gives cand_limit and hit_limit.
+ *
+ * sfx_edit_dev / sfx_index_edit_dev / sfx_gindex_edit_dev: everything is queued on the caller's stream, which is
+ *   synchronised once to read (C, H, flags) back and, when there are hits, a second time behind the sort and the
+ *   merge, for Z.  The calls keep no state in the index and take their memory from the workspace (the piece search of
+ *   sfx_index_edit_dev is sfx_index_query_dev, as for sfx_index_hamming_dev): any number of threads may call on one
+ *   index at once, each with its own workspace.
+ *   *cands_out = C and *hits_out = H always (H = 0 when C is refused).  C <= cand_limit and H <= hit_limit:
+ *   *count_out = Z, the first min(Z, capacity) quadruples are written and nothing past them, and first (when given)
+ *   is complete.  C > cand_limit or H > hit_limit: SFX_OK, nothing is written to the quadruple arrays or to first, and
+ *   *count_out = 0 -- the refusal is recognised by *cands_out > cand_limit or *hits_out > hit_limit.
+ *   SFX_ERR_ARG: cand_limit == 0, hit_limit == 0 or hit_limit >= 2^32 (hits are numbered in 32 bits), max_errors > 31,
+ *   cands_out / hits_out / count_out NULL, a quadruple array NULL while capacity > 0, a NULL input of a non-empty
+ *   call, a qoff that is not monotone or a pattern with m_j <= k (both found on the device, reported through the same
+ *   read-back), a workspace off SFX_WORKSPACE_ALIGN.  SFX_ERR_TOO_LARGE: n > u32::MAX, a pattern longer than u32::MAX
+ *   (found on the device likewise), nq * (k + 1) >= 2^32.  A workspace below
+ *   sfx_edit_workspace_bytes(nq, max_errors, cand_limit, hit_limit) is SFX_ERR_WORKSPACE.
+ *   nq == 0 or n == 0: SFX_OK with C = H = Z = 0, first all zero if given.
+ *   Workspace <= 24 (P + 1) + cand_limit / 7 + 30 hit_limit + 9 MiB bytes with P = nq (k + 1) (a cand_limit above
+ *   P * u32::MAX counts as that, a hit_limit above (2 k + 1) cand_limit as that).
+ *   d_text and d_qbytes may have any alignment, d_pattern / d_tbegin / d_tend need 4 bytes, d_qoff / d_first 8.
+ *   Outside the caller's buffers nothing is written; outside T, sa (da and doc_starts of a collection), the patterns
+ *   and the workspace nothing is read; no load of an extension touches a byte outside the candidate's two windows
+ *   [max(lo, q - b_t - k), q) and [qe, min(hi, qe + m_j - b_(t+1) + k)) or outside the pattern.
+ *   sfx_edit_dev takes text and table as they are: for any table whose entries are all < n nothing is read or written
+ *   out of bounds and every loop ends; what is reported for a table that is not the text's suffix array is
+ *   unspecified.
+ * sfx_index_edit / sfx_gindex_edit: the same with host buffers, staged through HBM; they find a short pattern on the
+ *   host.
+ * Not covered: local-minima-only reporting, the alignment script (CIGAR), per-pattern k, k > 31, search over the
+ * FM-index, the multi-GPU path. */
+uint64_t sfx_edit_workspace_bytes(uint64_t nq, uint32_t max_errors, uint64_t cand_limit, uint64_t hit_limit);
+int sfx_edit_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa,
+                 const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq, uint32_t max_errors, uint64_t cand_limit, uint64_t hit_limit,
+                 uint32_t* d_pattern, uint32_t* d_tbegin, uint32_t* d_tend, uint8_t* d_dist, uint64_t capacity,
+                 uint64_t* d_first /* nq + 1, may be NULL */,
+                 uint64_t* cands_out /* host */, uint64_t* hits_out /* host */, uint64_t* count_out /* host */,
+                 void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_index_edit_dev(const sfx_index* ix,
+                       const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq, uint32_t max_errors, uint64_t cand_limit, uint64_t hit_limit,
+                       uint32_t* d_pattern, uint32_t* d_tbegin, uint32_t* d_tend, uint8_t* d_dist, uint64_t capacity, uint64_t* d_first,
+                       uint64_t* cands_out /* host */, uint64_t* hits_out /* host */, uint64_t* count_out /* host */,
+                       void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_gindex_edit_dev(const sfx_gindex* gx,
+                        const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t nq, uint32_t max_errors, uint64_t cand_limit, uint64_t hit_limit,
+                        uint32_t* d_pattern, uint32_t* d_tbegin, uint32_t* d_tend, uint8_t* d_dist, uint64_t capacity, uint64_t* d_first,
+                        uint64_t* cands_out /* host */, uint64_t* hits_out /* host */, uint64_t* count_out /* host */,
+                        void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_index_edit(const sfx_index* ix, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq, uint32_t max_errors,
+                   uint64_t cand_limit, uint64_t hit_limit, uint32_t* pattern_out, uint32_t* tbegin_out, uint32_t* tend_out,
+                   uint8_t* dist_out, uint64_t capacity, uint64_t* first_out, uint64_t* cands_out, uint64_t* hits_out,
+                   uint64_t* count_out);
+int sfx_gindex_edit(const sfx_gindex* gx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq, uint32_t max_errors,
+                    uint64_t cand_limit, uint64_t hit_limit, uint32_t* pattern_out, uint32_t* tbegin_out, uint32_t* tend_out,
+                    uint8_t* dist_out, uint64_t capacity, uint64_t* first_out, uint64_t* cands_out, uint64_t* hits_out,
+                    uint64_t* count_out);
 
 /* ---- LCE index: inverse table, LCP range minima, k-mismatch extension -------- */
 /* How far do the suffixes at two positions of the indexed text agree?  T has n bytes, with table sa and lcp as

@@ -124,6 +124,25 @@ extern "C" {
                              cand_limit: u64, d_pattern: *mut u32, d_tpos: *mut u32, d_mism: *mut u8, capacity: u64,
                              d_first: *mut u64, cands_out: *mut u64, count_out: *mut u64, d_workspace: *mut c_void,
                              workspace_bytes: u64, stream: *mut c_void) -> c_int;
+    // k-error pattern search (edit distance) of a batch of patterns; DeviceIndex::edit_positions below goes through
+    // sfx_index_edit (host buffers; the outputs may be null at capacity 0, first_out may be null).  Like the rest of this
+    // crate the declarations and the wrapper have not been compiled (no Rust toolchain where the engine is built): the
+    // signature check of tests/test_rust_crate.py holds them against the header
+    fn sfx_index_edit(ix: *const SfxIndex, qbytes: *const u8, qoff: *const u64, nq: u64, max_errors: u32, cand_limit: u64,
+                      hit_limit: u64, pattern_out: *mut u32, tbegin_out: *mut u32, tend_out: *mut u32, dist_out: *mut u8,
+                      capacity: u64, first_out: *mut u64, cands_out: *mut u64, hits_out: *mut u64, count_out: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_edit_workspace_bytes(nq: u64, max_errors: u32, cand_limit: u64, hit_limit: u64) -> u64;
+    #[allow(dead_code)]
+    fn sfx_edit_dev(d_text: *const u8, n: u64, d_sa: *const u32, d_qbytes: *const u8, d_qoff: *const u64, nq: u64,
+                    max_errors: u32, cand_limit: u64, hit_limit: u64, d_pattern: *mut u32, d_tbegin: *mut u32, d_tend: *mut u32,
+                    d_dist: *mut u8, capacity: u64, d_first: *mut u64, cands_out: *mut u64, hits_out: *mut u64,
+                    count_out: *mut u64, d_workspace: *mut c_void, workspace_bytes: u64, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_index_edit_dev(ix: *const SfxIndex, d_qbytes: *const u8, d_qoff: *const u64, nq: u64, max_errors: u32,
+                          cand_limit: u64, hit_limit: u64, d_pattern: *mut u32, d_tbegin: *mut u32, d_tend: *mut u32,
+                          d_dist: *mut u8, capacity: u64, d_first: *mut u64, cands_out: *mut u64, hits_out: *mut u64,
+                          count_out: *mut u64, d_workspace: *mut c_void, workspace_bytes: u64, stream: *mut c_void) -> c_int;
     // FM-index over that pair (sfx_fm_*): the size bound; the handle functions take `sfx_fm*`, a type the signature check
     // of this block (tests/test_rust_crate.py) has no mapping for yet, so they are not bound here
     fn sfx_fm_bytes(n: u64, sample_step: u32, occ_step: u32) -> u64;
@@ -466,6 +485,62 @@ impl DeviceIndex {
         r.candidates = cands;
         Ok(r)
     }
+    /// Additive API: where do `queries` occur in the indexed text within `errors` (<= 31) substitutions, insertions and
+    /// deletions (unit-cost edit distance)?  Every query needs more than `errors` bytes.  Per query, in order:
+    /// `first[j] .. first[j + 1]` are its entries of `tbegin`, `tend` and `dist`, ascending by `tend`: an occurrence is
+    /// an end position for which some `text[tbegin .. tend)` is within `errors` edits of the query, with the least such
+    /// distance and the largest begin that attains it.  `Err((cands, hits))`: more than `max_candidates` exact piece
+    /// hits, or more than `max_hits` (candidate, end) pairs before the merge; nothing was written.
+    pub fn edit_positions(&self, queries: &[&[u8]], errors: u32, max_candidates: u64, max_hits: u64) -> Result<EditPositions, (u64, u64)> {
+        assert!(errors <= 31 && max_candidates >= 1 && max_hits >= 1 && max_hits < (1u64 << 32));
+        assert!(queries.iter().all(|q| q.len() > errors as usize));
+        let mut off = vec![0u64];
+        let mut blob = Vec::new();
+        for q in queries {
+            blob.extend_from_slice(q);
+            off.push(blob.len() as u64);
+        }
+        let nq = queries.len();
+        let mut cap = (4 * nq).max(1024);
+        let (mut cands, mut hits, mut count) = (0u64, 0u64, 0u64);
+        let mut r = EditPositions { first: vec![0u64; nq + 1], tbegin: Vec::new(), tend: Vec::new(), dist: Vec::new(), candidates: 0, hits: 0 };
+        let mut pattern: Vec<u32> = Vec::new();
+        for _ in 0..2 {                                        // the room is a guess: once more when there were more
+            pattern.resize(cap, 0);
+            r.tbegin.resize(cap, 0);
+            r.tend.resize(cap, 0);
+            r.dist.resize(cap, 0);
+            check(unsafe {
+                sfx_index_edit(self.0, blob.as_ptr(), off.as_ptr(), nq as u64, errors, max_candidates, max_hits,
+                               pattern.as_mut_ptr(), r.tbegin.as_mut_ptr(), r.tend.as_mut_ptr(), r.dist.as_mut_ptr(), cap as u64,
+                               r.first.as_mut_ptr(), &mut cands, &mut hits, &mut count)
+            }, "sfx_index_edit");
+            if cands > max_candidates || hits > max_hits {
+                return Err((cands, hits));
+            }
+            if count as usize <= cap {
+                break;
+            }
+            cap = count as usize;
+        }
+        r.tbegin.truncate(count as usize);
+        r.tend.truncate(count as usize);
+        r.dist.truncate(count as usize);
+        r.candidates = cands;
+        r.hits = hits;
+        Ok(r)
+    }
+}
+/// The k-error occurrences of a batch of queries (`DeviceIndex::edit_positions`), in CSR form: the occurrences of query j
+/// are the entries `first[j] .. first[j + 1]` of `tbegin` / `tend` / `dist`; `candidates` = the exact piece hits looked
+/// at, `hits` = the (candidate, end) pairs they found before the merge.
+pub struct EditPositions {
+    pub first: Vec<u64>,
+    pub tbegin: Vec<u32>,
+    pub tend: Vec<u32>,
+    pub dist: Vec<u8>,
+    pub candidates: u64,
+    pub hits: u64,
 }
 /// The k-mismatch occurrences of a batch of queries (`DeviceIndex::approx_positions`), in CSR form: the occurrences of
 /// query j are the entries `first[j] .. first[j + 1]` of `tpos` / `mism`; `candidates` = the exact piece hits looked at.

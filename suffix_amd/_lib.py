@@ -152,6 +152,17 @@ ABI = [
                                       ctypes.POINTER(_u64), _vp, _u64, _vp]),
     ("sfx_index_hamming", _int, [_vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     ("sfx_gindex_hamming", _int, [_vp, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    ("sfx_edit_workspace_bytes", _u64, [_u64, _u32, _u64, _u64]),
+    ("sfx_edit_dev", _int, [_vp, _u64, _vp, _vp, _vp, _u64, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64),
+                            ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp, _u64, _vp]),
+    ("sfx_index_edit_dev", _int, [_vp, _vp, _vp, _u64, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64),
+                                  ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp, _u64, _vp]),
+    ("sfx_gindex_edit_dev", _int, [_vp, _vp, _vp, _u64, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64),
+                                   ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp, _u64, _vp]),
+    ("sfx_index_edit", _int, [_vp, _vp, _vp, _u64, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64),
+                              ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    ("sfx_gindex_edit", _int, [_vp, _vp, _vp, _u64, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64),
+                               ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     ("sfx_inverse_table_workspace_bytes", _u64, [_u64]),
     ("sfx_inverse_table_dev", _int, [_vp, _u64, _vp, _vp, _u64, _vp]),
     ("sfx_inverse_table_u32", _int, [_vp, _u64, _vp]),

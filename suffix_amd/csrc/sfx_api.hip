@@ -17,6 +17,7 @@
 #include "sfx_lz.hip"   // LZ77 factorization and its decoder, likewise
 #include "sfx_mem.hip"  // maximal exact matches, likewise
 #include "sfx_hamming.hip"  // k-mismatch pattern search, likewise (over sfx_mem.hip's expansion)
+#include "sfx_edit.hip"  // k-error (edit distance) pattern search, likewise (over sfx_hamming.hip's pieces)
 #include "sfx_lce.hip"  // longest common extensions (inverse table + LCP min-tree), likewise
 #include "sfx_runs.hip"  // Lyndon arrays and maximal repetitions (runs) of a plain text, likewise (over sfx_lce.hip's tables)
 #include "sfx_docs.hip"  // document counts per lcp-interval and k-common substrings, likewise (over sfx_lce.hip's levels)
@@ -1665,6 +1666,135 @@ int sfx_gindex_hamming(const sfx_gindex* gx, const uint8_t* qbytes, const uint64
 {
     return hamming_host(nullptr, gx, qbytes, qoff, nq, max_mismatches, cand_limit, pattern_out, tpos_out, mism_out, capacity, first_out,
                         cands_out, count_out);
+}
+
+// ---- k-error pattern search (include/suffix_hip.h) ----------------------------------------
+uint64_t sfx_edit_workspace_bytes(uint64_t nq, uint32_t max_errors, uint64_t cand_limit, uint64_t hit_limit)
+{
+    return edit_workspace_bytes(nq, max_errors, cand_limit, hit_limit);
+}
+#define SFX_ED_TAIL_PARAMS                                                                                                      \
+    const uint8_t *d_qbytes, const uint64_t *d_qoff, uint64_t nq, uint32_t max_errors, uint64_t cand_limit, uint64_t hit_limit,  \
+        uint32_t *d_pattern, uint32_t *d_tbegin, uint32_t *d_tend, uint8_t *d_dist, uint64_t capacity, uint64_t *d_first,        \
+        uint64_t *cands_out, uint64_t *hits_out, uint64_t *count_out, void *d_workspace, uint64_t workspace_bytes, void *stream
+#define SFX_ED_TAIL_ARGS                                                                                                        \
+    d_qbytes, d_qoff, nq, max_errors, cand_limit, hit_limit, d_pattern, d_tbegin, d_tend, d_dist, capacity, d_first, cands_out,  \
+        hits_out, count_out, d_workspace, workspace_bytes, (hipStream_t)stream
+#define SFX_ED_NEED()                                                                                          \
+    SFX_NEED_U64(d_qoff, d_first);                                                                             \
+    SFX_NEED_U32(d_pattern, d_tbegin, d_tend);                                                                 \
+    SFX_NEED_WS(d_workspace, workspace_bytes, edit_workspace_bytes(nq, max_errors, cand_limit, hit_limit))
+int sfx_edit_dev(const uint8_t* d_text, uint64_t n, const uint32_t* d_sa, SFX_ED_TAIL_PARAMS)
+{
+    SFX_NEED_U32(d_sa);
+    SFX_ED_NEED();
+    const HmSource s = {d_text, n, d_sa, nullptr, nullptr, 0};
+    auto search = [&](const uint8_t* q, const uint64_t* po, uint64_t np, uint32_t* lo, uint32_t* hi, hipStream_t st) {
+        return query_batch_dev(d_text, n, d_sa, n, q, po, np, lo, hi, nullptr, nullptr, st);
+    };
+    return edit_dev(s, search, SFX_ED_TAIL_ARGS);
+}
+int sfx_index_edit_dev(const sfx_index* ix, SFX_ED_TAIL_PARAMS)
+{
+    SFX_ED_NEED();
+    if (!ix) return SFX_ERR_ARG;
+    const HmSource s = {ix->d_text, ix->n, ix->d_sa, nullptr, nullptr, 0};
+    // the directory and the key tree, as for any batch; the tree's phase-2 scratch belongs to the calling thread
+    auto search = [&](const uint8_t* q, const uint64_t* po, uint64_t np, uint32_t* lo, uint32_t* hi, hipStream_t st) {
+        return sfx_index_query_dev(ix, q, po, np, lo, hi, nullptr, nullptr, st);
+    };
+    return edit_dev(s, search, SFX_ED_TAIL_ARGS);
+}
+int sfx_gindex_edit_dev(const sfx_gindex* gx, SFX_ED_TAIL_PARAMS)
+{
+    SFX_ED_NEED();
+    if (!gx) return SFX_ERR_ARG;
+    if (gx->n && (!gx->d_starts || !gx->d_da || gx->ndocs == 0)) return SFX_ERR_ARG;
+    const HmSource s = {gx->d_text, gx->n, gx->d_sa, gx->d_starts, gx->d_da, gx->ndocs};
+    auto search = [&](const uint8_t* q, const uint64_t* po, uint64_t np, uint32_t* lo, uint32_t* hi, hipStream_t st) {
+        return gindex_query_dev(gx->d_text, gx->n, gx->d_starts, gx->ndocs, gx->d_sa, gx->d_da, gx->d_prev, q, po, np, lo, hi, nullptr,
+                                nullptr, nullptr, nullptr, 0, st);
+    };
+    return edit_dev(s, search, SFX_ED_TAIL_ARGS);
+}
+#undef SFX_ED_TAIL_PARAMS
+#undef SFX_ED_TAIL_ARGS
+#undef SFX_ED_NEED
+// host buffers staged through HBM on the calling thread's stream; exactly one of ix / gx is given
+static int edit_host(const sfx_index* ix, const sfx_gindex* gx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq, uint32_t k,
+                     uint64_t cand_limit, uint64_t hit_limit, uint32_t* pattern_out, uint32_t* tbegin_out, uint32_t* tend_out,
+                     uint8_t* dist_out, uint64_t capacity, uint64_t* first_out, uint64_t* cands_out, uint64_t* hits_out, uint64_t* count_out)
+{
+    if ((!ix && !gx) || !cands_out || !hits_out || !count_out || cand_limit == 0 || hit_limit == 0 || hit_limit > kEdMaxHits || k > kEdMaxK)
+        return SFX_ERR_ARG;
+    *cands_out = *hits_out = *count_out = 0;
+    const uint64_t n = ix ? ix->n : gx->n;
+    if (n > 0xFFFFFFFFull || (nq && ed_piece_count(nq, k) == 0)) return SFX_ERR_TOO_LARGE;
+    if (capacity && (!pattern_out || !tbegin_out || !tend_out || !dist_out)) return SFX_ERR_ARG;
+    if (nq && !qoff) return SFX_ERR_ARG;
+    if (nq == 0 || n == 0) {
+        if (first_out) memset(first_out, 0, (nq + 1) * sizeof(uint64_t));
+        return SFX_OK;
+    }
+    for (uint64_t j = 0; j < nq; j++) {
+        if (qoff[j + 1] < qoff[j]) return SFX_ERR_ARG;
+        if (qoff[j + 1] - qoff[j] > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    }
+    for (uint64_t j = 0; j < nq; j++)
+        if (qoff[j + 1] - qoff[j] <= k) return SFX_ERR_ARG;
+    const uint64_t qtotal = qoff[nq];
+    if (qtotal && !qbytes) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    cand_limit = dmin(cand_limit, nq * (k + 1) * n);                       // (C cannot be larger: the workspace need not be either)
+    hit_limit = dmin(hit_limit, ed_hit_room(nq * (k + 1), k, cand_limit, hit_limit));
+    capacity = dmin(capacity, dmin(hit_limit, nq * (n + 1)));              // (an occurrence per pattern and end at the most)
+    const uint64_t wsb = edit_workspace_bytes(nq, k, cand_limit, hit_limit);
+    DevBuf dq, doff, dj, db, de, dd, df, dw;
+    SFX_TRY(dq.alloc(dmax<uint64_t>(qtotal, 1)));
+    SFX_TRY(doff.alloc((nq + 1) * sizeof(uint64_t)));
+    SFX_TRY(dj.alloc(capacity * sizeof(uint32_t)));
+    SFX_TRY(db.alloc(capacity * sizeof(uint32_t)));
+    SFX_TRY(de.alloc(capacity * sizeof(uint32_t)));
+    SFX_TRY(dd.alloc(capacity));
+    if (first_out) SFX_TRY(df.alloc((nq + 1) * sizeof(uint64_t)));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(dq.p, qbytes, qtotal, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(doff.p, qoff, (nq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    uint32_t *oj = capacity ? (uint32_t*)dj.p : nullptr, *ob = capacity ? (uint32_t*)db.p : nullptr, *oe = capacity ? (uint32_t*)de.p : nullptr;
+    uint8_t* od = capacity ? (uint8_t*)dd.p : nullptr;
+    if (ix)
+        SFX_TRY(sfx_index_edit_dev(ix, (const uint8_t*)dq.p, (const uint64_t*)doff.p, nq, k, cand_limit, hit_limit, oj, ob, oe, od, capacity,
+                                   (uint64_t*)df.p, cands_out, hits_out, count_out, dw.p, wsb, st));
+    else
+        SFX_TRY(sfx_gindex_edit_dev(gx, (const uint8_t*)dq.p, (const uint64_t*)doff.p, nq, k, cand_limit, hit_limit, oj, ob, oe, od, capacity,
+                                    (uint64_t*)df.p, cands_out, hits_out, count_out, dw.p, wsb, st));
+    if (*cands_out > cand_limit || *hits_out > hit_limit) return SFX_OK;   // (refused: nothing was written)
+    const uint64_t z = dmin<uint64_t>(*count_out, capacity);
+    if (z) {
+        SFX_HIP(hipMemcpyAsync(pattern_out, dj.p, z * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(tbegin_out, db.p, z * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(tend_out, de.p, z * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SFX_HIP(hipMemcpyAsync(dist_out, dd.p, z, hipMemcpyDeviceToHost, st));
+    }
+    if (first_out) SFX_HIP(hipMemcpyAsync(first_out, df.p, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+int sfx_index_edit(const sfx_index* ix, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq, uint32_t max_errors, uint64_t cand_limit,
+                   uint64_t hit_limit, uint32_t* pattern_out, uint32_t* tbegin_out, uint32_t* tend_out, uint8_t* dist_out, uint64_t capacity,
+                   uint64_t* first_out, uint64_t* cands_out, uint64_t* hits_out, uint64_t* count_out)
+{
+    return edit_host(ix, nullptr, qbytes, qoff, nq, max_errors, cand_limit, hit_limit, pattern_out, tbegin_out, tend_out, dist_out, capacity,
+                     first_out, cands_out, hits_out, count_out);
+}
+int sfx_gindex_edit(const sfx_gindex* gx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t nq, uint32_t max_errors, uint64_t cand_limit,
+                    uint64_t hit_limit, uint32_t* pattern_out, uint32_t* tbegin_out, uint32_t* tend_out, uint8_t* dist_out, uint64_t capacity,
+                    uint64_t* first_out, uint64_t* cands_out, uint64_t* hits_out, uint64_t* count_out)
+{
+    return edit_host(nullptr, gx, qbytes, qoff, nq, max_errors, cand_limit, hit_limit, pattern_out, tbegin_out, tend_out, dist_out, capacity,
+                     first_out, cands_out, hits_out, count_out);
 }
 
 // ---- suffix-tree topology, generalized suffix array -------------------------------------------

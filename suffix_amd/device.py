@@ -366,6 +366,13 @@ class DeviceIndex:
         return _hamming(self._eng, call, "sfx_index_hamming_dev", self._text.numel(), qbytes, qoff, self._text, mismatches,
                         max_candidates, capacity, workspace)
 
+    def edit_search(self, qbytes, qoff, errors, max_candidates=1 << 30, max_hits=1 << 22, capacity=None, workspace=None):
+        """As the module's edit_search, against the index's text and (checked) table; the pieces are searched through the
+        directory and the key tree (sfx_index_edit_dev).  Keeps no state in the index: threads may call at once."""
+        call = lambda *tail: self._eng.lib.sfx_index_edit_dev(self._h, *tail)
+        return _edit_search(self._eng, call, "sfx_index_edit_dev", self._text.numel(), qbytes, qoff, self._text, errors, max_candidates,
+                            max_hits, capacity, workspace)
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
@@ -765,6 +772,82 @@ def hamming(text, sa, qbytes, qoff, mismatches, max_candidates=1 << 30, capacity
     return _hamming(eng, call, "sfx_hamming_dev", n, qbytes, qoff, text, mismatches, max_candidates, capacity, workspace)
 
 
+EDIT_MAX_ERRORS = 31
+
+
+def edit_workspace(nq, errors, max_candidates, max_hits, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_edit_workspace_bytes(int(nq), int(errors), int(max_candidates), int(max_hits))), dtype=torch.uint8,
+                       device=device)
+
+
+def _edit_search(eng, call, name, n, qbytes, qoff, anchor, errors, max_candidates, max_hits, capacity, workspace):
+    """The checks, buffers and the repeated call every edit_search entry shares; call(tail...) -> status."""
+    if qbytes.dtype != torch.uint8 or qbytes.dim() != 1 or not qbytes.is_contiguous():
+        raise TypeError("qbytes must be a contiguous 1-D uint8 tensor")
+    if qoff.dtype != torch.int64 or qoff.dim() != 1 or not qoff.is_contiguous() or qoff.numel() < 1:
+        raise TypeError("qoff must be a contiguous 1-D int64 tensor of nq + 1 offsets")
+    dev = anchor.device
+    if qbytes.device != dev or qoff.device != dev:
+        raise ValueError(f"qbytes and qoff must be on the text's device ({dev})")
+    k, max_candidates, max_hits = int(errors), int(max_candidates), int(max_hits)
+    if not 0 <= k <= EDIT_MAX_ERRORS:
+        raise ValueError(f"errors must be in 0 .. {EDIT_MAX_ERRORS}")
+    if max_candidates < 1 or not 1 <= max_hits < 1 << 32:
+        raise ValueError("max_candidates must be at least 1 and max_hits in 1 .. 2^32 - 1")
+    nq = qoff.numel() - 1
+    if nq and int((qoff[1:] - qoff[:-1]).min()) <= k:                # (the library finds it too: SFX_ERR_ARG)
+        raise ValueError(f"every pattern needs at least errors + 1 = {k + 1} bytes")
+    max_candidates = min(max_candidates, max(nq * (k + 1) * n, 1))   # (there are no more: keeps the workspace small)
+    max_hits = min(max_hits, max_candidates * (2 * k + 1))
+    if anchor.is_cuda:
+        eng.require_device()
+    if workspace is None:
+        workspace = edit_workspace(nq, k, max_candidates, max_hits, dev, eng)
+    first = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    cap = min(max(4 * nq, 1024), max_hits) if capacity is None else int(capacity)
+    cands, hits, count = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    for _ in range(2):
+        pat, tbegin, tend = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
+        dist = torch.empty(cap, dtype=torch.uint8, device=dev)
+        with _on(anchor):
+            eng.check(call(_p(qbytes), _p(qoff), nq, k, max_candidates, max_hits, _p(pat), _p(tbegin), _p(tend), _p(dist), cap, _p(first),
+                           ctypes.byref(cands), ctypes.byref(hits), ctypes.byref(count), _p(workspace), workspace.numel(),
+                           _stream_ptr(anchor)), name)
+        if cands.value > max_candidates:
+            raise SuffixHipError(f"{name}: {cands.value} candidates exceed max_candidates = {max_candidates}; use longer patterns, "
+                                 "fewer errors or raise max_candidates")
+        if hits.value > max_hits:
+            raise SuffixHipError(f"{name}: {hits.value} hits exceed max_hits = {max_hits}; use longer patterns, fewer errors or raise "
+                                 "max_hits")
+        if count.value <= cap or capacity is not None:
+            break
+        cap = int(count.value)
+    z = min(int(count.value), cap)
+    return first, pat[:z].clone(), tbegin[:z].clone(), tend[:z].clone(), dist[:z].clone(), int(cands.value), int(hits.value)
+
+
+def edit_search(text, sa, qbytes, qoff, errors, max_candidates=1 << 30, max_hits=1 << 22, capacity=None, workspace=None, engine=None):
+    """Where do the patterns (qbytes uint8, qoff int64 of nq + 1 offsets, as for hamming) occur in (text, sa) within
+    `errors` (0 .. 31) substitutions, insertions and deletions -- unit-cost edit distance; all tensors on one device.
+    Every pattern needs more than `errors` bytes: a shorter one raises ValueError (the offsets are read back for it).
+    -> (first, pattern, tbegin, tend, dist, candidates, hits): the occurrences of pattern j are the entries
+    first[j] .. first[j + 1], ascending by tend; an occurrence is an end tend with its least distance dist (uint8) and
+    the largest begin that attains it.  candidates = the exact piece hits looked at, hits = the (candidate, end) pairs
+    they found before the merge.  More than max_candidates / max_hits raise SuffixHipError naming the count.  The room
+    is guessed and the call repeated once when there were more; with `capacity` it runs once and returns the first
+    `capacity` occurrences (first stays complete).  Runs on the current stream and synchronises it at most twice per
+    call; the table is not checked (sfx_edit_dev)."""
+    eng = engine or default_engine()
+    _check_u8(text)
+    _check_u32(sa, "sa", text.numel())
+    if sa.device != text.device:
+        raise ValueError(f"sa must be on the text's device ({text.device})")
+    n = text.numel()
+    call = lambda *tail: eng.lib.sfx_edit_dev(_p(text), n, _p(sa), *tail)
+    return _edit_search(eng, call, "sfx_edit_dev", n, qbytes, qoff, text, errors, max_candidates, max_hits, capacity, workspace)
+
+
 def inverse_table_workspace(n, device, engine=None):
     eng = engine or default_engine()
     return torch.empty(int(eng.lib.sfx_inverse_table_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
@@ -1147,6 +1230,13 @@ class GeneralizedDeviceIndex:
         call = lambda *tail: self._eng.lib.sfx_gindex_hamming_dev(self._h, *tail)
         return _hamming(self._eng, call, "sfx_gindex_hamming_dev", self._text.numel(), qbytes, qoff, self._text, mismatches,
                         max_candidates, capacity, workspace)
+
+    def edit_search(self, qbytes, qoff, errors, max_candidates=1 << 30, max_hits=1 << 22, capacity=None, workspace=None):
+        """As the module's edit_search, against the collection: an occurrence lies inside one document, tbegin and tend
+        are text positions (sfx_gindex_edit_dev)."""
+        call = lambda *tail: self._eng.lib.sfx_gindex_edit_dev(self._h, *tail)
+        return _edit_search(self._eng, call, "sfx_gindex_edit_dev", self._text.numel(), qbytes, qoff, self._text, errors, max_candidates,
+                            max_hits, capacity, workspace)
 
     def close(self):
         dx, self._doclist = getattr(self, "_doclist", None), None

@@ -32,7 +32,7 @@ import ctypes
 import numpy as np
 
 from ._lib import default_engine
-from .table import Mems, _LceHandle, _approx_positions, _as_bytes, _match_stats, _mems, _ptr, _repeat_lens, _repeat_spans, _shared_spans
+from .table import Mems, _LceHandle, _approx_positions, _as_bytes, _edit_positions, _match_stats, _mems, _ptr, _repeat_lens, _repeat_spans, _shared_spans
 
 _NONE = 0xFFFFFFFF
 _DOCLIST_ORDERS = {"doc": 0, "tf": 1}
@@ -392,6 +392,23 @@ class GeneralizedSuffixTable:
         """(positions, mismatches): text positions ascending and the differing bytes of each window."""
         _, tpos, mism = self.approx_positions_batch([query], mismatches, sort=True)
         return tpos, mism
+
+    # -- k-error pattern search ---------------------------------------------------------------------
+    def edit_positions_batch(self, queries, errors, max_candidates=1 << 30, max_hits=1 << 22):
+        """As SuffixTable.edit_positions_batch, against the collection: an occurrence lies inside ONE document; tbegin and
+        tend are text positions doc_starts[doc] + offset.  -> (first, tbegin, tend, dist, doc)."""
+        first, tbegin, tend, dist = _edit_positions(self._eng, self._eng.lib.sfx_gindex_edit, "sfx_gindex_edit", self._ensure_index,
+                                                    self.len(), queries, errors, max_candidates, max_hits)
+        # the document of an occurrence: the last one that starts before tend (an occurrence has text bytes: tend > tbegin)
+        d = np.searchsorted(self._starts, tend.astype(np.uint64), side="left").astype(np.int64) - 1
+        return first, tbegin, tend, dist, d.astype(np.uint32)
+
+    def edit_positions(self, pattern, k):
+        """[(doc, begin, end, dist)] of `pattern` within k edits, begin and end as offsets in the document, ascending by
+        document and end."""
+        _, tbegin, tend, dist, doc = self.edit_positions_batch([pattern], k)
+        base = self._starts[doc].astype(np.int64) if doc.size else np.zeros(0, dtype=np.int64)
+        return list(zip(doc.tolist(), (tbegin - base).tolist(), (tend - base).tolist(), dist.tolist()))
 
     # -- longest common extensions ----------------------------------------------------------------
     def _lce_index(self):

@@ -267,6 +267,47 @@ def _approx_positions(eng, fn, name, index, n, queries, mismatches, max_candidat
     return first, tpos, mism
 
 
+def _edit_positions(eng, fn, name, index, n, queries, errors, max_candidates, max_hits):
+    """sfx_index_edit / sfx_gindex_edit on host arrays -> (first uint64, tbegin uint32, tend uint32, dist uint8).  The
+    first call guesses the room; a second one follows when there were more."""
+    qs = [_as_bytes(q) for q in queries]
+    k, max_candidates, max_hits = int(errors), int(max_candidates), int(max_hits)
+    if not 0 <= k <= 31:
+        raise ValueError("errors must be in 0 .. 31")
+    if max_candidates < 1 or not 1 <= max_hits < 1 << 32:
+        raise ValueError("max_candidates must be at least 1 and max_hits in 1 .. 2^32 - 1")
+    if any(len(q) <= k for q in qs):
+        raise ValueError(f"every pattern needs at least errors + 1 = {k + 1} bytes")
+    nq = len(qs)
+    first = np.zeros(nq + 1, dtype=np.uint64)
+    if not nq or not n:
+        return first, np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+    off = np.zeros(nq + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(q) for q in qs], dtype=np.uint64)
+    blob = np.frombuffer(b"".join(qs), dtype=np.uint8)
+    max_candidates = min(max_candidates, nq * (k + 1) * n)          # (there are no more candidates)
+    max_hits = min(max_hits, max_candidates * (2 * k + 1))
+    eng.require_device()
+    cands, hits, count = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    cap = min(max(4 * nq, 1024), max_hits)
+    for _ in range(2):
+        pat, tbegin, tend = (np.zeros(cap, dtype=np.uint32) for _ in range(3))
+        dist = np.zeros(cap, dtype=np.uint8)
+        eng.check(fn(index(), _ptr(blob), _ptr(off), nq, k, max_candidates, max_hits, _ptr(pat), _ptr(tbegin), _ptr(tend), _ptr(dist), cap,
+                     _ptr(first), ctypes.byref(cands), ctypes.byref(hits), ctypes.byref(count)), name)
+        if cands.value > max_candidates:
+            raise SuffixHipError(f"{name}: {cands.value} candidates exceed max_candidates = {max_candidates}; use longer patterns, "
+                                 "fewer errors or raise max_candidates")
+        if hits.value > max_hits:
+            raise SuffixHipError(f"{name}: {hits.value} hits exceed max_hits = {max_hits}; use longer patterns, fewer errors or raise "
+                                 "max_hits")
+        if count.value <= cap:
+            break
+        cap = int(count.value)
+    z = int(count.value)
+    return first, tbegin[:z].copy(), tend[:z].copy(), dist[:z].copy()
+
+
 def _bwt_step(sample_step):
     step = int(sample_step or 0)
     if step < 0 or step > 0x80000000 or step & (step - 1):
@@ -695,6 +736,24 @@ class SuffixTable:
         and the uint8 number of differing bytes of each."""
         _, tpos, mism = self.approx_positions_batch([query], mismatches, sort=True)
         return tpos, mism
+
+    # -- k-error pattern search ---------------------------------------------------------------------
+    def edit_positions_batch(self, queries, errors, max_candidates=1 << 30, max_hits=1 << 22):
+        """Where do the queries occur within `errors` (0 .. 31) substitutions, insertions and deletions (unit-cost edit
+        distance)?  -> (first, tbegin, tend, dist): the occurrences of queries[j] are the entries first[j]:first[j + 1],
+        ascending by tend.  An occurrence is an END position tend for which some text[s:tend] is within `errors` edits
+        of the query; dist (uint8) is the least such distance and tbegin (uint32) the largest s that attains it.
+        Neighbouring ends of one alignment are occurrences of their own.  Every query needs more than `errors` bytes
+        (ValueError otherwise: it would occur everywhere).
+        The work grows with the exact hits of the k + 1 pieces of every query, the candidates, and with the (candidate,
+        end) pairs they find: more than max_candidates or max_hits raise SuffixHipError naming the count."""
+        return _edit_positions(self._eng, self._eng.lib.sfx_index_edit, "sfx_index_edit", self._ensure_index, self.len(), queries, errors,
+                               max_candidates, max_hits)
+
+    def edit_positions(self, pattern, k):
+        """[(begin, end, dist)] of `pattern` within k edits, ascending by end (see edit_positions_batch)."""
+        _, tbegin, tend, dist = self.edit_positions_batch([pattern], k)
+        return list(zip(tbegin.tolist(), tend.tolist(), dist.tolist()))
 
     def __repr__(self):                                              # Debug, :296-312
         lines = ["", "-----------------------------------------", "SUFFIX TABLE",
