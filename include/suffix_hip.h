@@ -261,6 +261,57 @@ int sfx_build_gsa_u32_dev(const uint8_t* d_text, uint64_t n, const uint64_t* d_d
                           void* d_workspace, uint64_t workspace_bytes, void* stream);
 int sfx_build_gsa_u32(const uint8_t* text, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs,
                       uint32_t* sa_out, uint32_t* da_out, uint32_t* lcp_out);
+/* ---- merge of two generalized suffix arrays: add documents without a rebuild ------
+ * A = the first ndocs_a documents (n_a bytes), B = the documents behind them (n_b bytes).  sa_a / da_a / lcp_a and
+ * sa_b / da_b / lcp_b are exactly what sfx_build_gsa_u32 returns for A alone and for B alone, so B's positions and
+ * document numbers are relative to B.  text[0 .. n_a + n_b) and doc_starts[0 .. ndocs) describe the whole collection;
+ * doc_starts[ndocs_a] == n_a (ndocs_a == ndocs: B is empty; ndocs_a == 0: A is).  Equal truncated suffixes are ordered
+ * by position, so an added document never moves an old suffix relative to another and sorts behind every old suffix
+ * equal to it: the arrays of the whole collection are the STABLE MERGE of the two sets, the old entry first on equal
+ * strings.  For the new suffix x_j at B-rank j, p[j] = the number of old truncated suffixes <= x_j (an equal one
+ * counts), left[j] / right[j] = its common prefix with the old suffix at rank p[j] - 1 / p[j], never past a document
+ * end, 0 where there is no such rank.  x_j goes to slot p[j] + j and writes sa_b[j] + n_a, da_b[j] + ndocs_a and the
+ * lcp lcp_b[j] when the slot in front holds a new suffix too, else left[j]; old rank r goes to slot
+ * r + #{j : p[j] <= r} and writes sa_a[r], da_a[r] and right[j] of the new suffix in the slot in front, lcp_a[r] when
+ * that slot is old.  Cost: one bisection over the old table per NEW suffix (O(log n_a + match length) compared bytes)
+ * and one streaming pass; no sort.
+ *   match_limit   adding a near-copy of a long document compares a number of bytes quadratic in its length.  0: no
+ *                 limit.  Otherwise a comparison stops once a common prefix exceeds match_limit.
+ *   *longest_out  the largest left / right, capped at match_limit + 1 when a comparison stopped.  *longest_out >
+ *                 match_limit (match_limit > 0): SFX_OK, NOTHING is written to d_sa / d_da / d_lcp -- the refusal is
+ *                 recognised by that inequality, as sfx_mems_dev's pair_limit is; build the whole collection instead.
+ *   d_da_a / d_da_b may be NULL (the documents are then found from doc_starts); d_da / d_lcp may be NULL to skip them,
+ *   and d_lcp_a / d_lcp_b are read only when d_lcp is given.
+ * SFX_ERR_ARG, found on the device and read back before anything indexes by it: doc_starts not as sfx_build_gsa_u32
+ * wants it or with doc_starts[ndocs_a] != n_a, an sa_a entry >= n_a, an sa_b entry >= n_b, a da_a entry >= ndocs_a, a
+ * da_b entry >= ndocs - ndocs_a; after the rank search: p not non-decreasing (sa_b is no GSA of B).  Arrays that pass
+ * these checks without being GSAs give some answer; nothing is read or written out of bounds.  SFX_ERR_ARG on the host:
+ * ndocs_a > ndocs, bytes without documents on either side, a NULL among the needed arrays, longest_out NULL, an output
+ * that overlaps an input or the workspace, a pointer off its alignment.  n_a + n_b > u32::MAX: SFX_ERR_TOO_LARGE.
+ * n_a + n_b == 0: SFX_OK.  n_b == 0 or n_a == 0 copies the other side (offset as above).
+ * sfx_gsa_merge_workspace_bytes(n_a, n_b) <= 12 n_b + 34 KiB (p, left, right; one word per wave of the rank search); a
+ * shorter one is SFX_ERR_WORKSPACE.  The device entry borrows everything, keeps nothing, allocates nothing, and may run
+ * from several threads and streams at once.  It synchronises `stream` twice (the check, the rank search) and returns with
+ * its last kernel queued.
+ * sfx_gsa_merge_u32: the same over host pointers.  sfx_gsa_extend_u32: the whole collection's text and doc_starts plus
+ * A's arrays; builds B = documents ndocs_a .. with sfx_build_gsa_u32_dev and merges.  *route_out says what produced the
+ * outputs: SFX_GSA_ROUTE_MERGE, SFX_GSA_ROUTE_REBUILD (refused and rebuild_on_limit != 0: one build of the whole
+ * collection) or SFX_GSA_ROUTE_NONE (refused, rebuild_on_limit == 0: nothing written). */
+enum { SFX_GSA_ROUTE_NONE = 0, SFX_GSA_ROUTE_MERGE = 1, SFX_GSA_ROUTE_REBUILD = 2 };
+uint64_t sfx_gsa_merge_workspace_bytes(uint64_t n_a, uint64_t n_b);
+int sfx_gsa_merge_dev(const uint8_t* d_text, const uint64_t* d_doc_starts, uint64_t ndocs, uint64_t ndocs_a,
+                      const uint32_t* d_sa_a, const uint32_t* d_da_a /* may be NULL */, const uint32_t* d_lcp_a, uint64_t n_a,
+                      const uint32_t* d_sa_b, const uint32_t* d_da_b /* may be NULL */, const uint32_t* d_lcp_b, uint64_t n_b,
+                      uint32_t match_limit, uint32_t* d_sa, uint32_t* d_da, uint32_t* d_lcp, uint64_t* longest_out,
+                      void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_gsa_merge_u32(const uint8_t* text, const uint64_t* doc_starts, uint64_t ndocs, uint64_t ndocs_a,
+                      const uint32_t* sa_a, const uint32_t* da_a /* may be NULL */, const uint32_t* lcp_a, uint64_t n_a,
+                      const uint32_t* sa_b, const uint32_t* da_b /* may be NULL */, const uint32_t* lcp_b, uint64_t n_b,
+                      uint32_t match_limit, uint32_t* sa_out, uint32_t* da_out, uint32_t* lcp_out, uint64_t* longest_out);
+int sfx_gsa_extend_u32(const uint8_t* text, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs, uint64_t ndocs_a,
+                       const uint32_t* sa_a, const uint32_t* da_a /* may be NULL */, const uint32_t* lcp_a,
+                       uint32_t match_limit, int rebuild_on_limit, uint32_t* sa_out, uint32_t* da_out, uint32_t* lcp_out,
+                       uint64_t* longest_out, uint32_t* route_out);
 /* Resident generalized index over (text, doc_starts, GSA, DA).  q matches at (i, o) iff |q| <= |D_i| - o and
  * D_i[o .. o + |q|) == q: matches never span documents and form one GSA interval.  Per query: start / end (0 / 0
  * when empty; the empty query is empty), found, any (a position, UINT32_MAX for none) and ndocs = the number of

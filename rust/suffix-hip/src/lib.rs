@@ -168,6 +168,21 @@ extern "C" {
                            d_child_lb: *mut u32, d_child_node: *mut u32, d_child_byte: *mut u8,
                            d_leaf_parent: *mut u32, nodes_out: *mut u64, children_out: *mut u64, ws: *mut c_void,
                            ws_bytes: u64, stream: *mut c_void) -> c_int;
+    // merge of two generalized suffix arrays (sfx_gsa_merge_*, sfx_gsa_extend_u32): documents added without a rebuild
+    fn sfx_gsa_extend_u32(text: *const u8, n: u64, doc_starts: *const u64, ndocs: u64, ndocs_a: u64, sa_a: *const u32,
+                          da_a: *const u32, lcp_a: *const u32, match_limit: u32, rebuild_on_limit: c_int, sa_out: *mut u32,
+                          da_out: *mut u32, lcp_out: *mut u32, longest_out: *mut u64, route_out: *mut u32) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_gsa_merge_u32(text: *const u8, doc_starts: *const u64, ndocs: u64, ndocs_a: u64, sa_a: *const u32, da_a: *const u32,
+                         lcp_a: *const u32, n_a: u64, sa_b: *const u32, da_b: *const u32, lcp_b: *const u32, n_b: u64,
+                         match_limit: u32, sa_out: *mut u32, da_out: *mut u32, lcp_out: *mut u32, longest_out: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn sfx_gsa_merge_workspace_bytes(n_a: u64, n_b: u64) -> u64;
+    #[allow(dead_code)]
+    fn sfx_gsa_merge_dev(d_text: *const u8, d_doc_starts: *const u64, ndocs: u64, ndocs_a: u64, d_sa_a: *const u32,
+                         d_da_a: *const u32, d_lcp_a: *const u32, n_a: u64, d_sa_b: *const u32, d_da_b: *const u32,
+                         d_lcp_b: *const u32, n_b: u64, match_limit: u32, d_sa: *mut u32, d_da: *mut u32, d_lcp: *mut u32,
+                         longest_out: *mut u64, d_workspace: *mut c_void, workspace_bytes: u64, stream: *mut c_void) -> c_int;
     // device-pointer variants (`*_dev`) take a hipStream_t as *mut c_void; omitted here.
     #[allow(dead_code)]
     fn sfx_build_sa_u32_dev(d_text: *const u8, n: u64, d_sa: *mut u32, ws: *mut c_void,
@@ -241,6 +256,34 @@ pub fn sais_table_with_lcp(text: &str) -> (Vec<u32>, Vec<u32>) {
         sfx_build_sa_lcp_u32(text.as_ptr(), text.len() as u64, sa.as_mut_ptr(), lcp.as_mut_ptr())
     }, "sfx_build_sa_lcp_u32");
     (sa, lcp)
+}
+
+/// What produced the arrays of `gsa_extend`: the merge, or -- an added suffix shared more than `match_limit` bytes with an
+/// old one -- one build of the whole collection.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum GsaRoute {
+    Merge,
+    Rebuild,
+}
+
+/// Additive API: the generalized suffix array, document array and LCP of `text` cut at `doc_starts`, from the arrays
+/// `(sa_a, da_a, lcp_a)` of its first `ndocs_a` documents: only the documents behind them are built, then merged in
+/// (`sfx_gsa_extend_u32`).  `match_limit` 0 never rebuilds.  -> (sa, da, lcp, the longest old/new match seen, route).
+pub fn gsa_extend(text: &[u8], doc_starts: &[u64], ndocs_a: usize, sa_a: &[u32], da_a: &[u32], lcp_a: &[u32],
+                  match_limit: u32) -> (Vec<u32>, Vec<u32>, Vec<u32>, u64, GsaRoute) {
+    assert!(text.len() <= u32::MAX as usize);
+    assert!(ndocs_a <= doc_starts.len());
+    let n_a = if ndocs_a < doc_starts.len() { doc_starts[ndocs_a] as usize } else { text.len() };
+    assert!(sa_a.len() == n_a && da_a.len() == n_a && lcp_a.len() == n_a);
+    let n = text.len();
+    let (mut sa, mut da, mut lcp) = (vec![0u32; n], vec![0u32; n], vec![0u32; n]);
+    let (mut longest, mut route) = (0u64, 0u32);
+    check(unsafe {
+        sfx_gsa_extend_u32(text.as_ptr(), n as u64, doc_starts.as_ptr(), doc_starts.len() as u64, ndocs_a as u64, sa_a.as_ptr(),
+                           da_a.as_ptr(), lcp_a.as_ptr(), match_limit, 1, sa.as_mut_ptr(), da.as_mut_ptr(), lcp.as_mut_ptr(),
+                           &mut longest, &mut route)
+    }, "sfx_gsa_extend_u32");
+    (sa, da, lcp, longest, if route == 2 { GsaRoute::Rebuild } else { GsaRoute::Merge })
 }
 
 /// Additive API: the Burrows-Wheeler transform of `text` with its suffix table, and the rows of the suffixes at every

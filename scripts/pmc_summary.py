@@ -90,6 +90,7 @@ NAMES = [
     ("k_hm_emit", "hm_emit"), ("k_hm_first", "hm_first"),
     ("k_ed_short", "ed_short"), ("k_ed_cand", "ed_cand"), ("k_ed_count", "ed_count"), ("k_ed_emit", "ed_emit"),
     ("k_ed_heads", "ed_heads"), ("k_ed_reduce", "ed_reduce"), ("k_ed_first", "ed_first"),
+    ("k_gm_check", "gmerge_check"), ("k_gm_rank", "gmerge_rank"), ("k_gm_rank_finish", "gmerge_rank"), ("k_gm_scatter", "gmerge_scatter"),
     ("k_fm_count", "fm_count"), ("k_fm_lookup", "fm_lookup"), ("k_fm_", "fm_build"),
     ("k_lce_check", "lce_check"), ("k_lce_scatter", "lce_scatter"), ("k_lce_verify", "lce_verify"), ("k_lce_levels", "lce_levels"),
     ("k_lce_query", "lce_query"), ("k_lce_range_min", "lce_range_min"), ("k_lce_ranks", "lce_ranks"),

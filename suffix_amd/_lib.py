@@ -97,6 +97,13 @@ ABI = [
     ("sfx_gsa_workspace_bytes", _u64, [_u64, _u64]),
     ("sfx_build_gsa_u32_dev", _int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
     ("sfx_build_gsa_u32", _int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    ("sfx_gsa_merge_workspace_bytes", _u64, [_u64, _u64]),
+    ("sfx_gsa_merge_dev", _int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp,
+                                 ctypes.POINTER(_u64), _vp, _u64, _vp]),
+    ("sfx_gsa_merge_u32", _int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp,
+                                 ctypes.POINTER(_u64)]),
+    ("sfx_gsa_extend_u32", _int, [_vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _u32, _int, _vp, _vp, _vp, ctypes.POINTER(_u64),
+                                  ctypes.POINTER(_u32)]),
     ("sfx_gindex_create_dev", _int, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
     ("sfx_gindex_create", _int, [_vp, _u64, _vp, _u64, _vp, _vp, ctypes.POINTER(_vp)]),
     ("sfx_gindex_query_dev", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -219,6 +226,7 @@ ABI = [
     ("sfx_get_option", _u64, [_int]),
 ]
 SFX_OPT_TINY_MAX = 1
+SFX_GSA_ROUTE_NONE, SFX_GSA_ROUTE_MERGE, SFX_GSA_ROUTE_REBUILD = 0, 1, 2
 SFX_REP_ANY, SFX_REP_EARLIER, SFX_REP_OTHER_DOC = 0, 1, 2
 REP_SCOPES = {"any": SFX_REP_ANY, "earlier": SFX_REP_EARLIER, "other_doc": SFX_REP_OTHER_DOC}
 

@@ -22,6 +22,7 @@
 #include "sfx_runs.hip"  // Lyndon arrays and maximal repetitions (runs) of a plain text, likewise (over sfx_lce.hip's tables)
 #include "sfx_docs.hip"  // document counts per lcp-interval and k-common substrings, likewise (over sfx_lce.hip's levels)
 #include "sfx_doclist.hip"  // document listing with term frequencies and top-k, likewise
+#include "sfx_gsamerge.hip"  // merge of two generalized suffix arrays, likewise
 
 namespace sfx {
 
@@ -1924,6 +1925,135 @@ int sfx_build_gsa_u32(const uint8_t* text, uint64_t n, const uint64_t* doc_start
     SFX_HIP(hipMemcpyAsync(sa_out, ds.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (da_out) SFX_HIP(hipMemcpyAsync(da_out, dd.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (lcp_out) SFX_HIP(hipMemcpyAsync(lcp_out, dl.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+
+// ---- merge of two generalized suffix arrays (include/suffix_hip.h) -----------------
+uint64_t sfx_gsa_merge_workspace_bytes(uint64_t n_a, uint64_t n_b) { return gsa_merge_workspace_bytes(n_a, n_b); }
+int sfx_gsa_merge_dev(const uint8_t* d_text, const uint64_t* d_doc_starts, uint64_t ndocs, uint64_t ndocs_a, const uint32_t* d_sa_a,
+                      const uint32_t* d_da_a, const uint32_t* d_lcp_a, uint64_t n_a, const uint32_t* d_sa_b, const uint32_t* d_da_b,
+                      const uint32_t* d_lcp_b, uint64_t n_b, uint32_t match_limit, uint32_t* d_sa, uint32_t* d_da, uint32_t* d_lcp,
+                      uint64_t* longest_out, void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    if (n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull || n_a + n_b > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    SFX_NEED_U64(d_doc_starts);
+    SFX_NEED_U32(d_sa_a, d_da_a, d_lcp_a, d_sa_b, d_da_b, d_lcp_b, d_sa, d_da, d_lcp);
+    SFX_NEED_WS(d_workspace, workspace_bytes, gsa_merge_workspace_bytes(n_a, n_b));
+    const GmIn in{d_text, d_doc_starts, ndocs, ndocs_a, n_a + n_b, n_a, n_b, d_sa_a, d_da_a, d_lcp_a, d_sa_b, d_da_b, d_lcp_b};
+    return gsa_merge_dev(in, match_limit, d_sa, d_da, d_lcp, longest_out, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+// device copies of one array set; a NULL host array stays NULL on the device
+struct GsaSetBufs {
+    DevBuf sa, da, lcp;
+    int upload(const uint32_t* h_sa, const uint32_t* h_da, const uint32_t* h_lcp, uint64_t cnt, hipStream_t st)
+    {
+        const uint64_t bytes = cnt * sizeof(uint32_t);
+        const struct { DevBuf* d; const uint32_t* h; } all[] = {{&sa, h_sa}, {&da, h_da}, {&lcp, h_lcp}};
+        for (const auto& x : all) {
+            if (!x.h) continue;
+            SFX_TRY(x.d->alloc(bytes));
+            if (bytes) SFX_HIP(hipMemcpyAsync(x.d->p, x.h, bytes, hipMemcpyHostToDevice, st));
+        }
+        return SFX_OK;
+    }
+};
+int sfx_gsa_merge_u32(const uint8_t* text, const uint64_t* doc_starts, uint64_t ndocs, uint64_t ndocs_a, const uint32_t* sa_a,
+                      const uint32_t* da_a, const uint32_t* lcp_a, uint64_t n_a, const uint32_t* sa_b, const uint32_t* da_b,
+                      const uint32_t* lcp_b, uint64_t n_b, uint32_t match_limit, uint32_t* sa_out, uint32_t* da_out, uint32_t* lcp_out,
+                      uint64_t* longest_out)
+{
+    if (n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull || n_a + n_b > 0xFFFFFFFFull || ndocs > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (!longest_out || ndocs_a > ndocs) return SFX_ERR_ARG;
+    *longest_out = 0;
+    const uint64_t n = n_a + n_b, bytes = n * sizeof(uint32_t);
+    if (n == 0) return SFX_OK;
+    if (ndocs == 0 || !text || !doc_starts || !sa_out) return SFX_ERR_ARG;
+    if ((n_a && (!sa_a || (lcp_out && !lcp_a))) || (n_b && (!sa_b || (lcp_out && !lcp_b)))) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    DevBuf dt, dst, ds, dd, dl, dw;
+    GsaSetBufs A, B;
+    const uint64_t wsb = gsa_merge_workspace_bytes(n_a, n_b);
+    SFX_TRY(dt.alloc(n));
+    SFX_TRY(dst.alloc(ndocs * sizeof(uint64_t)));
+    SFX_TRY(ds.alloc(bytes));
+    if (da_out) SFX_TRY(dd.alloc(bytes));
+    if (lcp_out) SFX_TRY(dl.alloc(bytes));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(dt.p, text, n, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dst.p, doc_starts, ndocs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(A.upload(n_a ? sa_a : nullptr, n_a ? da_a : nullptr, n_a ? lcp_a : nullptr, n_a, st));
+    SFX_TRY(B.upload(n_b ? sa_b : nullptr, n_b ? da_b : nullptr, n_b ? lcp_b : nullptr, n_b, st));
+    const GmIn in{(const uint8_t*)dt.p, (const uint64_t*)dst.p, ndocs, ndocs_a, n, n_a, n_b, (const uint32_t*)A.sa.p, (const uint32_t*)A.da.p,
+                  (const uint32_t*)A.lcp.p, (const uint32_t*)B.sa.p, (const uint32_t*)B.da.p, (const uint32_t*)B.lcp.p};
+    SFX_TRY(gsa_merge_dev(in, match_limit, (uint32_t*)ds.p, (uint32_t*)dd.p, (uint32_t*)dl.p, longest_out, dw.p, wsb, st));
+    if (match_limit && *longest_out > match_limit) return SFX_OK;        // refused: the outputs stay as they are
+    SFX_HIP(hipMemcpyAsync(sa_out, ds.p, bytes, hipMemcpyDeviceToHost, st));
+    if (da_out) SFX_HIP(hipMemcpyAsync(da_out, dd.p, bytes, hipMemcpyDeviceToHost, st));
+    if (lcp_out) SFX_HIP(hipMemcpyAsync(lcp_out, dl.p, bytes, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+int sfx_gsa_extend_u32(const uint8_t* text, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs, uint64_t ndocs_a, const uint32_t* sa_a,
+                       const uint32_t* da_a, const uint32_t* lcp_a, uint32_t match_limit, int rebuild_on_limit, uint32_t* sa_out,
+                       uint32_t* da_out, uint32_t* lcp_out, uint64_t* longest_out, uint32_t* route_out)
+{
+    if (n > 0xFFFFFFFFull || ndocs > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (!longest_out || !route_out || ndocs_a > ndocs) return SFX_ERR_ARG;
+    *longest_out = 0;
+    *route_out = SFX_GSA_ROUTE_NONE;
+    if (n == 0) { *route_out = SFX_GSA_ROUTE_MERGE; return SFX_OK; }
+    if (ndocs == 0 || !text || !doc_starts || !sa_out) return SFX_ERR_ARG;
+    const uint64_t n_a = ndocs_a < ndocs ? doc_starts[ndocs_a] : n;
+    if (n_a > n) return SFX_ERR_ARG;
+    const uint64_t n_b = n - n_a, ndocs_b = ndocs - ndocs_a, bytes = n * sizeof(uint32_t);
+    if (n_a && (!sa_a || !lcp_a)) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    std::vector<uint64_t> starts_b(ndocs_b);
+    for (uint64_t d = 0; d < ndocs_b; d++) starts_b[d] = doc_starts[ndocs_a + d] - n_a;   // (a start below n_a wraps: the build's check names it)
+    DevBuf dt, dst, dsb, ds, dd, dl, dw, dbs, dbd, dbl;
+    GsaSetBufs A;
+    const uint64_t build_b = gsa_workspace_bytes(n_b), wsb = dmax(build_b, gsa_merge_workspace_bytes(n_a, n_b));
+    SFX_TRY(dt.alloc(n));
+    SFX_TRY(dst.alloc(ndocs * sizeof(uint64_t)));
+    SFX_TRY(dsb.alloc(ndocs_b * sizeof(uint64_t)));
+    SFX_TRY(ds.alloc(bytes));
+    SFX_TRY(dd.alloc(bytes));
+    SFX_TRY(dl.alloc(bytes));
+    SFX_TRY(dbs.alloc(n_b * sizeof(uint32_t)));
+    SFX_TRY(dbd.alloc(n_b * sizeof(uint32_t)));
+    SFX_TRY(dbl.alloc(n_b * sizeof(uint32_t)));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};            // (declared after the buffers: runs before they return to the pool)
+    SFX_HIP(hipMemcpyAsync(dt.p, text, n, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dst.p, doc_starts, ndocs * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (ndocs_b) SFX_HIP(hipMemcpyAsync(dsb.p, starts_b.data(), ndocs_b * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SFX_TRY(A.upload(n_a ? sa_a : nullptr, n_a ? da_a : nullptr, n_a ? lcp_a : nullptr, n_a, st));
+    if (n_b) {
+        if (ndocs_b == 0) return SFX_ERR_ARG;
+        SFX_TRY(gsa_build_dev((const uint8_t*)dt.p + n_a, n_b, (const uint64_t*)dsb.p, ndocs_b, (uint32_t*)dbs.p, (uint32_t*)dbd.p, (uint32_t*)dbl.p,
+                              dw.p, wsb, st));
+    }
+    const GmIn in{(const uint8_t*)dt.p, (const uint64_t*)dst.p, ndocs, ndocs_a, n, n_a, n_b, (const uint32_t*)A.sa.p, (const uint32_t*)A.da.p,
+                  (const uint32_t*)A.lcp.p, (const uint32_t*)dbs.p, (const uint32_t*)dbd.p, (const uint32_t*)dbl.p};
+    SFX_TRY(gsa_merge_dev(in, match_limit, (uint32_t*)ds.p, (uint32_t*)dd.p, (uint32_t*)dl.p, longest_out, dw.p, wsb, st));
+    if (match_limit && *longest_out > match_limit) {
+        if (!rebuild_on_limit) return SFX_OK;                            // refused: the outputs stay as they are
+        SFX_HIP(hipStreamSynchronize(st));
+        dw.release();
+        const uint64_t whole = gsa_workspace_bytes(n);
+        SFX_TRY(dw.alloc(whole));
+        SFX_TRY(gsa_build_dev((const uint8_t*)dt.p, n, (const uint64_t*)dst.p, ndocs, (uint32_t*)ds.p, (uint32_t*)dd.p, (uint32_t*)dl.p, dw.p, whole, st));
+        *route_out = SFX_GSA_ROUTE_REBUILD;
+    } else {
+        *route_out = SFX_GSA_ROUTE_MERGE;
+    }
+    SFX_HIP(hipMemcpyAsync(sa_out, ds.p, bytes, hipMemcpyDeviceToHost, st));
+    if (da_out) SFX_HIP(hipMemcpyAsync(da_out, dd.p, bytes, hipMemcpyDeviceToHost, st));
+    if (lcp_out) SFX_HIP(hipMemcpyAsync(lcp_out, dl.p, bytes, hipMemcpyDeviceToHost, st));
     SFX_HIP(hipStreamSynchronize(st));
     return SFX_OK;
 }

@@ -500,6 +500,60 @@ def _check_u32(t, name, n=None):
         raise ValueError(f"{name} must hold {n} entries")
 
 
+def gsa_merge_workspace(n_a, n_b, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_gsa_merge_workspace_bytes(int(n_a), int(n_b))), dtype=torch.uint8, device=device)
+
+
+def gsa_merge(text, doc_starts, ndocs_a, sa_a, lcp_a, sa_b, lcp_b, da_a=None, da_b=None, match_limit=0, out_sa=None, out_da=None,
+              out_lcp=None, want_da=True, want_lcp=True, workspace=None, engine=None):
+    """The arrays of a whole collection from those of its first ndocs_a documents (sa_a, lcp_a[, da_a]) and of the documents
+    behind them (sa_b, lcp_b[, da_b], as build_gsa returns them for those documents alone): a stable merge, no sort.  text
+    and doc_starts describe the whole collection.  -> (sa, da, lcp, longest); da / lcp are None unless wanted.  longest =
+    the longest common prefix of a new suffix with an old one; with match_limit > 0 a longer one refuses the merge --
+    (None, None, None, longest) with longest == match_limit + 1 and the outputs untouched -- because its cost grows with
+    the square of such a match; build_gsa of the whole collection is the answer then.  Synchronises the current stream
+    twice.  See include/suffix_hip.h."""
+    eng = engine or default_engine()
+    _check_u8(text)
+    if doc_starts.dtype != torch.int64 or doc_starts.dim() != 1 or not doc_starts.is_contiguous():
+        raise TypeError("doc_starts must be a contiguous 1-D int64 tensor")
+    dev = text.device
+    _check_u32(sa_a, "sa_a")
+    _check_u32(sa_b, "sa_b")
+    n_a, n_b = sa_a.numel(), sa_b.numel()
+    n = text.numel()
+    if n_a + n_b != n:
+        raise ValueError(f"sa_a and sa_b hold {n_a} + {n_b} entries, the text {n} bytes")
+    for t, name, cnt in ((lcp_a, "lcp_a", n_a), (lcp_b, "lcp_b", n_b), (da_a, "da_a", n_a), (da_b, "da_b", n_b),
+                         (out_sa, "out_sa", n), (out_da, "out_da", n), (out_lcp, "out_lcp", n)):
+        if t is not None:
+            _check_u32(t, name, cnt)
+    if any(t is not None and t.device != dev for t in (doc_starts, sa_a, lcp_a, sa_b, lcp_b, da_a, da_b, out_sa, out_da, out_lcp)):
+        raise ValueError(f"all arrays must be on the text's device ({dev})")
+    match_limit = int(match_limit)
+    if not 0 <= match_limit <= 0xFFFFFFFF:
+        raise ValueError("match_limit must be in 0 .. 2^32 - 1")
+    if text.is_cuda:
+        eng.require_device()
+    if out_sa is None:
+        out_sa = torch.empty(n, dtype=torch.int32, device=dev)
+    if want_da and out_da is None:
+        out_da = torch.empty(n, dtype=torch.int32, device=dev)
+    if want_lcp and out_lcp is None:
+        out_lcp = torch.empty(n, dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = gsa_merge_workspace(n_a, n_b, dev, eng)
+    longest = ctypes.c_uint64(0)
+    with _on(text):
+        eng.check(eng.lib.sfx_gsa_merge_dev(_p(text), _p(doc_starts), doc_starts.numel(), int(ndocs_a), _p(sa_a), _p(da_a), _p(lcp_a), n_a,
+                                            _p(sa_b), _p(da_b), _p(lcp_b), n_b, match_limit, _p(out_sa), _p(out_da), _p(out_lcp),
+                                            ctypes.byref(longest), _p(workspace), workspace.numel(), _stream_ptr(text)), "sfx_gsa_merge_dev")
+    if match_limit and longest.value > match_limit:
+        return None, None, None, int(longest.value)
+    return out_sa, out_da, out_lcp, int(longest.value)
+
+
 def repeat_lens_workspace(n, scope, device, engine=None):
     eng = engine or default_engine()
     return torch.empty(int(eng.lib.sfx_repeat_lens_workspace_bytes(int(n), REP_SCOPES[scope])), dtype=torch.uint8, device=device)

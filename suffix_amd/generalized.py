@@ -23,6 +23,8 @@ no match spans two documents.
     mems(query, min_len, unique)  the maximal exact matches of a NEW text, each inside one document
     approx_positions(query, k)    the occurrences with up to k differing bytes, each inside one document
     lce((doc, off), (doc, off), mismatches)   how far two suffixes of the collection agree, never past a document end
+    extend(docs, match_limit)     a NEW table over these documents followed by `docs`: only the added ones are built, then merged in
+    merge(other, match_limit)     the same for two existing tables, from the arrays both already hold
 
 Construction and queries run on the GPU through the C ABI (sfx_build_gsa_u32, sfx_gindex_*); there is no CPU
 path except `new_naive`, the definition itself.
@@ -96,6 +98,72 @@ class GeneralizedSuffixTable:
                 k += 1
             lcp[r] = k
         return cls(docs, engine=engine, _arrays=(table, da, lcp))
+
+    # -- adding documents without a rebuild ----------------------------------------------------
+    last_extend_route = None                             # "merge" | "rebuild": what made this table in extend() / merge()
+
+    def _grown(self, docs, arrays, route):
+        g = type(self)(docs, engine=self._eng, _arrays=arrays)
+        g.last_extend_route = route
+        return g
+
+    def extend(self, docs, match_limit=1 << 16):
+        """A NEW table over this table's documents followed by `docs`, equal in all three arrays to new() of all of them;
+        this one stays as it is.  Only the added documents are built; their suffixes are then ranked among the old ones
+        and the arrays merged in one pass (sfx_gsa_extend_u32).  An added suffix that shares more than match_limit bytes
+        with an old one (a near-copy of a long document: the ranking would compare a number of bytes quadratic in its
+        length) makes the call build the whole collection instead; match_limit 0 never does.  The new table's
+        last_extend_route says which ran: "merge" or "rebuild"."""
+        docs = list(docs)
+        whole = [self.document(i) for i in range(self.num_docs())] + docs
+        bdocs = self._docs + [_as_bytes(d) for d in docs]
+        n = sum(len(d) for d in bdocs)
+        if n > 0xFFFFFFFF:
+            raise OverflowError("GeneralizedSuffixTable.extend: more than u32::MAX bytes in all")
+        match_limit = int(match_limit)
+        if not 0 <= match_limit <= _NONE:
+            raise ValueError("match_limit must be in 0 .. 2^32 - 1")
+        table, da, lcp = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        route = ctypes.c_uint32(1)
+        if n:
+            self._eng.require_device()
+            text = np.frombuffer(b"".join(bdocs), dtype=np.uint8)
+            starts = np.zeros(len(bdocs), dtype=np.uint64)
+            starts[1:] = np.cumsum([len(d) for d in bdocs[:-1]], dtype=np.uint64)
+            longest = ctypes.c_uint64(0)
+            self._eng.check(self._eng.lib.sfx_gsa_extend_u32(_ptr(text), n, _ptr(starts), starts.size, len(self._docs), _ptr(self._table),
+                                                              _ptr(self._da), _ptr(self._lcp), match_limit, 1, _ptr(table), _ptr(da), _ptr(lcp),
+                                                              ctypes.byref(longest), ctypes.byref(route)), "sfx_gsa_extend_u32")
+        return self._grown(whole, (table, da, lcp), {1: "merge", 2: "rebuild"}[int(route.value)])
+
+    def merge(self, other, match_limit=1 << 16):
+        """As extend() for two existing tables: a NEW table over this table's documents followed by `other`'s, from the
+        arrays both already hold (sfx_gsa_merge_u32); beyond match_limit, one build of the whole collection."""
+        whole = [t.document(i) for t in (self, other) for i in range(t.num_docs())]
+        bdocs = self._docs + other._docs
+        n_a, n_b = self.len(), other.len()
+        n = n_a + n_b
+        if n > 0xFFFFFFFF:
+            raise OverflowError("GeneralizedSuffixTable.merge: more than u32::MAX bytes in all")
+        match_limit = int(match_limit)
+        if not 0 <= match_limit <= _NONE:
+            raise ValueError("match_limit must be in 0 .. 2^32 - 1")
+        table, da, lcp = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        if n:
+            self._eng.require_device()
+            text = np.frombuffer(b"".join(bdocs), dtype=np.uint8)
+            starts = np.zeros(len(bdocs), dtype=np.uint64)
+            starts[1:] = np.cumsum([len(d) for d in bdocs[:-1]], dtype=np.uint64)
+            longest = ctypes.c_uint64(0)
+            self._eng.check(self._eng.lib.sfx_gsa_merge_u32(_ptr(text), _ptr(starts), starts.size, len(self._docs), _ptr(self._table),
+                                                             _ptr(self._da), _ptr(self._lcp), n_a, _ptr(other._table), _ptr(other._da),
+                                                             _ptr(other._lcp), n_b, match_limit, _ptr(table), _ptr(da), _ptr(lcp),
+                                                             ctypes.byref(longest)), "sfx_gsa_merge_u32")
+            if match_limit and longest.value > match_limit:
+                g = type(self)(whole, engine=self._eng)
+                g.last_extend_route = "rebuild"
+                return g
+        return self._grown(whole, (table, da, lcp), "merge")
 
     def __del__(self):
         ix, self._index = getattr(self, "_index", None), None
