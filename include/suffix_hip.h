@@ -219,7 +219,8 @@ int sfx_lcp_intervals_dev(const uint32_t* d_lcp, uint64_t n, uint32_t* d_lb, uin
  * other arrays (leaf_parent excepted) when the capacities suffice; SFX_ERR_TOO_LARGE: n > u32::MAX.
  * For ANY lcp contents and any table with entries < n nothing is read or written out of bounds; what the arrays hold
  * for an lcp array that is not the table's is unspecified.
- * Not covered: generalized tables (truncated suffixes give a node several terminals), suffix links, preorder numbers. */
+ * Suffix links of the internal nodes: sfx_suffix_links_dev below (over an sfx_lce handle).
+ * Not covered: generalized tables (truncated suffixes give a node several terminals), preorder numbers. */
 uint64_t sfx_suffix_tree_workspace_bytes(uint64_t n);
 int sfx_suffix_tree_dev(const uint8_t* d_text /* may be NULL */, const uint32_t* d_sa, const uint32_t* d_lcp, uint64_t n,
                         uint64_t node_capacity, uint64_t child_capacity,
@@ -828,8 +829,9 @@ int sfx_gindex_edit(const sfx_gindex* gx, const uint8_t* qbytes, const uint64_t*
  * below sfx_inverse_table_workspace_bytes(n) is SFX_ERR_WORKSPACE.  sfx_lce_ranks*: rank[q] = isa[pos[q]], UINT32_MAX
  * for pos >= n.  sfx_lce_u32: create, query, destroy over host buffers.
  *
- * Not covered: the argmin of a range, suffix-tree LCA on top of it, LCE between a query text and the index (that is
- * sfx_match_stats), positions >= 2^32, the multi-GPU path. */
+ * The argmin of a range and the suffix-tree LCA on top of it are the navigation calls below (sfx_lce_range_argmin*,
+ * sfx_lce_lca*).  Not covered: LCE between a query text and the index (that is sfx_match_stats), positions >= 2^32, the
+ * multi-GPU path. */
 uint64_t sfx_inverse_table_workspace_bytes(uint64_t n);
 int sfx_inverse_table_dev(const uint32_t* d_sa, uint64_t n, uint32_t* d_isa, void* d_workspace, uint64_t workspace_bytes, void* stream);
 int sfx_inverse_table_u32(const uint32_t* sa, uint64_t n, uint32_t* isa_out);
@@ -849,6 +851,61 @@ int sfx_lce_ranks_dev(const sfx_lce* lx, const uint32_t* d_pos, uint64_t nq, uin
 int sfx_lce_ranks(const sfx_lce* lx, const uint32_t* pos, uint64_t nq, uint32_t* rank_out);
 int sfx_lce_u32(const uint32_t* sa, const uint32_t* lcp, uint64_t n, const uint64_t* doc_starts, uint64_t ndocs,
                 const uint32_t* a, const uint32_t* b, uint64_t nq, uint32_t max_mismatches, uint32_t* len_out);
+
+/* ---- suffix-tree navigation over the LCE handle: substring loci, LCA, argmin, suffix links ----
+ * How often does T[pos .. pos+len) occur and where, what is the lowest common ancestor of two suffixes, where does a
+ * node's suffix link point?  All from the handle above: no new index, no memory added to it.  end(p) as above;
+ * B[p] = the LCP value of boundary p with B[0] = 0 whatever lcp[0] holds (the convention of sfx_lcp_intervals_dev);
+ * NONE = UINT32_MAX.
+ *
+ *   bounds(r, d)     for a rank r < n and d >= 1: lo = the largest p <= r with B[p] < d (boundary 0 always qualifies),
+ *                    hi = the smallest p > r with B[p] < d, or n.  bounds(r, 0) = [0, n).  Always lo <= r < hi.
+ *   substr(pos,len)  len == 0 and pos <= n: [0, n), depth 0.  pos < n and 1 <= len <= end(pos) - pos:
+ *                    [lo, hi) = bounds(isa[pos], len), exactly the ranks whose (truncated) suffix starts with
+ *                    T[pos..pos+len): hi - lo occurrences, at sa[lo..hi).  depth = the string depth of the lowest
+ *                    node at or below the locus: end(pos) - pos if hi - lo == 1, else min lcp[lo+1 .. hi).
+ *                    Anything else: lo = hi = depth = NONE.
+ *   lca(i, j)        i, j < n.  i == j: [isa[i], isa[i] + 1), depth end(i) - i.  Otherwise with a < b the two ranks
+ *                    and d = min lcp[a+1 .. b+1): bounds(a, d), depth d (d == 0: the root [0, n)).  A position >= n:
+ *                    all three NONE.
+ *   argmin(lo, hi)   the smallest index that attains min lcp[lo .. hi), lcp[0] as stored (like range_min); NONE for
+ *                    an empty range or hi > n.
+ *   slink[k]         for node k of sfx_suffix_tree_dev's table (plain tables only) with string depth d: the dense id
+ *                    of the node that spells k's string without its first byte.  It always exists and has depth d - 1.
+ *                    slink[root] = NONE; every node of depth 1 links to the root, id 0.
+ * An interval does not identify a node: in a unary text the root and the depth-1 node share [0, n).  A node is
+ * (interval, depth), or its home boundary: the leftmost p in (lb, rb] with lcp[p] == depth, which is its
+ * sfx_lcp_intervals_dev id and the leftmost argmin of lcp[lb+1 .. rb+1).  The root is decided by depth == 0.
+ *
+ * The three query calls work on collection handles too (intervals of the generalized table), queue on the caller's
+ * stream, take no workspace, allocate nothing and do not synchronise; d_depth may be NULL.  Each query reads one
+ * inverse-table entry and, per side of the search, at most 2 levels - 1 lines of the min-tree, whatever len is.
+ * sfx_suffix_links_dev: d_sa is the table the handle was made from; SFX_ERR_ARG for a collection handle, a workspace
+ * below sfx_suffix_links_workspace_bytes(n) (<= 4 n + 64 KiB; may hold anything on entry) is SFX_ERR_WORKSPACE.  It
+ * queues two kernels and does not synchronise.  nq == 0, nodes == 0 and n == 0 succeed.  The node table is not
+ * verified: node_lb >= node_rb or node_rb >= n gives slink = NONE for that node (a node spans two ranks or more), and
+ * for a table that is not this lcp's every entry written is < nodes or NONE and nothing is accessed out of bounds.
+ * If the caller changes the borrowed lcp after creation the intervals are unspecified, within lo <= rank < hi <= n.
+ * Results are determined bit for bit by the inputs.  sfx_suffix_links_u32: create, link, destroy over host buffers.
+ *
+ * Not covered: suffix links of leaves and of collection trees, Weiner links, a walk of the matching statistics over
+ * suffix links, positions >= 2^32, the multi-GPU path. */
+int sfx_lce_substr_dev(const sfx_lce* lx, const uint32_t* d_pos, const uint32_t* d_len, uint64_t nq,
+                       uint32_t* d_lo, uint32_t* d_hi, uint32_t* d_depth /* may be NULL */, void* stream);
+int sfx_lce_substr(const sfx_lce* lx, const uint32_t* pos, const uint32_t* len, uint64_t nq,
+                   uint32_t* lo_out, uint32_t* hi_out, uint32_t* depth_out /* may be NULL */);
+int sfx_lce_lca_dev(const sfx_lce* lx, const uint32_t* d_a, const uint32_t* d_b, uint64_t nq,
+                    uint32_t* d_lo, uint32_t* d_hi, uint32_t* d_depth /* may be NULL */, void* stream);
+int sfx_lce_lca(const sfx_lce* lx, const uint32_t* a, const uint32_t* b, uint64_t nq,
+                uint32_t* lo_out, uint32_t* hi_out, uint32_t* depth_out /* may be NULL */);
+int sfx_lce_range_argmin_dev(const sfx_lce* lx, const uint32_t* d_lo, const uint32_t* d_hi, uint64_t nq, uint32_t* d_arg, void* stream);
+int sfx_lce_range_argmin(const sfx_lce* lx, const uint32_t* lo, const uint32_t* hi, uint64_t nq, uint32_t* arg_out);
+uint64_t sfx_suffix_links_workspace_bytes(uint64_t n);
+int sfx_suffix_links_dev(const sfx_lce* lx, const uint32_t* d_sa, uint64_t nodes, const uint32_t* d_node_lb,
+                         const uint32_t* d_node_rb, const uint32_t* d_node_depth, uint32_t* d_slink,
+                         void* d_workspace, uint64_t workspace_bytes, void* stream);
+int sfx_suffix_links_u32(const uint32_t* sa, const uint32_t* lcp, uint64_t n, uint64_t nodes, const uint32_t* node_lb,
+                         const uint32_t* node_rb, const uint32_t* node_depth, uint32_t* slink_out);
 
 /* ---- document counts of every lcp-interval, k-common substrings of a collection ----------
  * Which strings are shared by many documents?  da, lcp, n, ndocs are a collection's arrays as sfx_build_gsa_u32* writes

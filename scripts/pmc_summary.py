@@ -94,6 +94,8 @@ NAMES = [
     ("k_fm_count", "fm_count"), ("k_fm_lookup", "fm_lookup"), ("k_fm_", "fm_build"),
     ("k_lce_check", "lce_check"), ("k_lce_scatter", "lce_scatter"), ("k_lce_verify", "lce_verify"), ("k_lce_levels", "lce_levels"),
     ("k_lce_query", "lce_query"), ("k_lce_range_min", "lce_range_min"), ("k_lce_ranks", "lce_ranks"),
+    ("k_nav_substr", "nav_substr"), ("k_nav_lca", "nav_lca"), ("k_nav_argmin", "nav_argmin"), ("k_nav_home", "nav_home"),
+    ("k_nav_slink", "nav_slink"),
     ("k_docs_check", "docs_check"), ("k_docs_argmin", "docs_argmin"), ("k_docs_runs", "docs_runs"), ("k_docs_counts", "docs_counts"),
     ("k_docs_longest", "docs_longest"), ("k_docs_best", "docs_best"), ("k_docs_suffix_max", "docs_suffix_max"),
     ("k_dl_check", "doclist_check"), ("k_dl_work", "doclist_work"), ("k_dl_count<true>", "doclist_count_docs"), ("k_dl_count<false>", "doclist_count"),

@@ -184,6 +184,15 @@ ABI = [
     ("sfx_lce_ranks_dev", _int, [_vp, _vp, _u64, _vp, _vp]),
     ("sfx_lce_ranks", _int, [_vp, _vp, _u64, _vp]),
     ("sfx_lce_u32", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u32, _vp]),
+    ("sfx_lce_substr_dev", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    ("sfx_lce_substr", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    ("sfx_lce_lca_dev", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    ("sfx_lce_lca", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    ("sfx_lce_range_argmin_dev", _int, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    ("sfx_lce_range_argmin", _int, [_vp, _vp, _vp, _u64, _vp]),
+    ("sfx_suffix_links_workspace_bytes", _u64, [_u64]),
+    ("sfx_suffix_links_dev", _int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    ("sfx_suffix_links_u32", _int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     ("sfx_doc_counts_workspace_bytes", _u64, [_u64]),
     ("sfx_doc_counts_dev", _int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp]),
     ("sfx_doc_counts_u32", _int, [_vp, _vp, _u64, _u64, _vp, _vp]),

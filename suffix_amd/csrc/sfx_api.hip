@@ -19,6 +19,7 @@
 #include "sfx_hamming.hip"  // k-mismatch pattern search, likewise (over sfx_mem.hip's expansion)
 #include "sfx_edit.hip"  // k-error (edit distance) pattern search, likewise (over sfx_hamming.hip's pieces)
 #include "sfx_lce.hip"  // longest common extensions (inverse table + LCP min-tree), likewise
+#include "sfx_nav.hip"  // suffix-tree navigation: substring loci, LCA, argmin, suffix links, likewise (over sfx_lce.hip's handle)
 #include "sfx_runs.hip"  // Lyndon arrays and maximal repetitions (runs) of a plain text, likewise (over sfx_lce.hip's tables)
 #include "sfx_docs.hip"  // document counts per lcp-interval and k-common substrings, likewise (over sfx_lce.hip's levels)
 #include "sfx_doclist.hip"  // document listing with term frequencies and top-k, likewise
@@ -1080,6 +1081,117 @@ int sfx_lce_u32(const uint32_t* sa, const uint32_t* lcp, uint64_t n, const uint6
     const int rc = sfx_lce_query(lx, a, b, nq, max_mismatches, len_out);
     sfx_lce_destroy(lx);
     return rc;
+}
+
+// ---- suffix-tree navigation over the LCE handle: substring loci, LCA, argmin, suffix links (include/suffix_hip.h) ---
+int sfx_lce_substr_dev(const sfx_lce* lx, const uint32_t* d_pos, const uint32_t* d_len, uint64_t nq, uint32_t* d_lo, uint32_t* d_hi,
+                       uint32_t* d_depth, void* stream)
+{
+    SFX_NEED_U32(d_pos, d_len, d_lo, d_hi, d_depth);
+    return nav_substr_dev(lx, d_pos, d_len, nq, d_lo, d_hi, d_depth, (hipStream_t)stream);
+}
+int sfx_lce_lca_dev(const sfx_lce* lx, const uint32_t* d_a, const uint32_t* d_b, uint64_t nq, uint32_t* d_lo, uint32_t* d_hi,
+                    uint32_t* d_depth, void* stream)
+{
+    SFX_NEED_U32(d_a, d_b, d_lo, d_hi, d_depth);
+    return nav_lca_dev(lx, d_a, d_b, nq, d_lo, d_hi, d_depth, (hipStream_t)stream);
+}
+int sfx_lce_range_argmin_dev(const sfx_lce* lx, const uint32_t* d_lo, const uint32_t* d_hi, uint64_t nq, uint32_t* d_arg, void* stream)
+{
+    SFX_NEED_U32(d_lo, d_hi, d_arg);
+    return nav_argmin_dev(lx, d_lo, d_hi, nq, d_arg, (hipStream_t)stream);
+}
+// the host forms of the two interval queries: two inputs up, one launch, lo / hi / depth (nullptr: not wanted) down
+extern "C++" {
+template <class Run> static int nav_host_call(const sfx_lce* lx, const uint32_t* in0, const uint32_t* in1, uint64_t nq, uint32_t* lo, uint32_t* hi,
+                                              uint32_t* depth, Run run)
+{
+    if (!lx) return SFX_ERR_ARG;
+    if (nq == 0) return SFX_OK;
+    if (!in0 || !in1 || !lo || !hi) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    const uint64_t bytes = nq * sizeof(uint32_t);
+    DevBuf d0, d1, dl, dh, dd;
+    SFX_TRY(d0.alloc(bytes));
+    SFX_TRY(d1.alloc(bytes));
+    SFX_TRY(dl.alloc(bytes));
+    SFX_TRY(dh.alloc(bytes));
+    if (depth) SFX_TRY(dd.alloc(bytes));
+    hipStream_t st = call_stream();
+    StreamDrain drain{st};
+    SFX_HIP(hipMemcpyAsync(d0.p, in0, bytes, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(d1.p, in1, bytes, hipMemcpyHostToDevice, st));
+    SFX_TRY(run((const uint32_t*)d0.p, (const uint32_t*)d1.p, (uint32_t*)dl.p, (uint32_t*)dh.p, depth ? (uint32_t*)dd.p : nullptr, st));
+    SFX_HIP(hipMemcpyAsync(lo, dl.p, bytes, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipMemcpyAsync(hi, dh.p, bytes, hipMemcpyDeviceToHost, st));
+    if (depth) SFX_HIP(hipMemcpyAsync(depth, dd.p, bytes, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
+}
+}  // extern "C++"
+int sfx_lce_substr(const sfx_lce* lx, const uint32_t* pos, const uint32_t* len, uint64_t nq, uint32_t* lo_out, uint32_t* hi_out,
+                   uint32_t* depth_out)
+{
+    return nav_host_call(lx, pos, len, nq, lo_out, hi_out, depth_out,
+                         [&](const uint32_t* dp, const uint32_t* dn, uint32_t* dl, uint32_t* dh, uint32_t* dd, hipStream_t st) {
+                             return nav_substr_dev(lx, dp, dn, nq, dl, dh, dd, st);
+                         });
+}
+int sfx_lce_lca(const sfx_lce* lx, const uint32_t* a, const uint32_t* b, uint64_t nq, uint32_t* lo_out, uint32_t* hi_out, uint32_t* depth_out)
+{
+    return nav_host_call(lx, a, b, nq, lo_out, hi_out, depth_out,
+                         [&](const uint32_t* da, const uint32_t* db, uint32_t* dl, uint32_t* dh, uint32_t* dd, hipStream_t st) {
+                             return nav_lca_dev(lx, da, db, nq, dl, dh, dd, st);
+                         });
+}
+int sfx_lce_range_argmin(const sfx_lce* lx, const uint32_t* lo, const uint32_t* hi, uint64_t nq, uint32_t* arg_out)
+{
+    return lce_host_call(lx, lo, hi, true, nq, arg_out, [&](const uint32_t* dl, const uint32_t* dh, uint32_t* da, hipStream_t st) {
+        return nav_argmin_dev(lx, dl, dh, nq, da, st);
+    });
+}
+uint64_t sfx_suffix_links_workspace_bytes(uint64_t n) { return suffix_links_workspace_bytes(n); }
+int sfx_suffix_links_dev(const sfx_lce* lx, const uint32_t* d_sa, uint64_t nodes, const uint32_t* d_node_lb, const uint32_t* d_node_rb,
+                         const uint32_t* d_node_depth, uint32_t* d_slink, void* d_workspace, uint64_t workspace_bytes, void* stream)
+{
+    SFX_NEED_U32(d_sa, d_node_lb, d_node_rb, d_node_depth, d_slink);
+    SFX_NEED_WS(d_workspace, workspace_bytes, lx ? suffix_links_workspace_bytes(lx->n) : 0);
+    return suffix_links_dev(lx, d_sa, nodes, d_node_lb, d_node_rb, d_node_depth, d_slink, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+int sfx_suffix_links_u32(const uint32_t* sa, const uint32_t* lcp, uint64_t n, uint64_t nodes, const uint32_t* node_lb, const uint32_t* node_rb,
+                         const uint32_t* node_depth, uint32_t* slink_out)
+{
+    if (n > 0xFFFFFFFFull || nodes > 0xFFFFFFFFull) return SFX_ERR_TOO_LARGE;
+    if (n == 0 || nodes == 0) return SFX_OK;
+    if (!sa || !lcp || !node_lb || !node_rb || !node_depth || !slink_out) return SFX_ERR_ARG;
+    SFX_TRY(check_device());
+    const uint64_t bytes = n * sizeof(uint32_t), nbytes = nodes * sizeof(uint32_t), wsb = suffix_links_workspace_bytes(n);
+    DevBuf ds, dl, dlb, drb, ddp, dout, dw;
+    SFX_TRY(ds.alloc(bytes));
+    SFX_TRY(dl.alloc(bytes));
+    SFX_TRY(dlb.alloc(nbytes));
+    SFX_TRY(drb.alloc(nbytes));
+    SFX_TRY(ddp.alloc(nbytes));
+    SFX_TRY(dout.alloc(nbytes));
+    SFX_TRY(dw.alloc(wsb));
+    hipStream_t st = call_stream();
+    struct Handle {                    // (declared after the buffers: the handle borrows dl and goes first)
+        sfx_lce* lx = nullptr;
+        hipStream_t st;
+        ~Handle() { (void)hipStreamSynchronize(st); lce_destroy(lx); }
+    } h;
+    h.st = st;
+    SFX_HIP(hipMemcpyAsync(ds.p, sa, bytes, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dl.p, lcp, bytes, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(dlb.p, node_lb, nbytes, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(drb.p, node_rb, nbytes, hipMemcpyHostToDevice, st));
+    SFX_HIP(hipMemcpyAsync(ddp.p, node_depth, nbytes, hipMemcpyHostToDevice, st));
+    SFX_TRY(lce_create_pooled((const uint32_t*)ds.p, (const uint32_t*)dl.p, n, nullptr, 0, st, false, &h.lx));
+    SFX_TRY(suffix_links_dev(h.lx, (const uint32_t*)ds.p, nodes, (const uint32_t*)dlb.p, (const uint32_t*)drb.p, (const uint32_t*)ddp.p,
+                             (uint32_t*)dout.p, dw.p, wsb, st));
+    SFX_HIP(hipMemcpyAsync(slink_out, dout.p, nbytes, hipMemcpyDeviceToHost, st));
+    SFX_HIP(hipStreamSynchronize(st));
+    return SFX_OK;
 }
 
 // ---- document counts of every lcp-interval, k-common substrings of a collection (include/suffix_hip.h) -------------

@@ -1118,12 +1118,71 @@ class LceDeviceIndex:
                             "sfx_lce_ranks_dev")
         return out
 
+    def range_argmin(self, lo, hi):
+        """The smallest index that attains min lcp[lo[q] : hi[q]]; 0xFFFFFFFF for an empty range or hi > n."""
+        self._arg(lo, "lo")
+        self._arg(hi, "hi", lo.numel())
+        out = torch.empty(lo.numel(), dtype=torch.int32, device=self._dev)
+        with _on(self._on):
+            self._eng.check(self._eng.lib.sfx_lce_range_argmin_dev(self._h, _p(lo), _p(hi), lo.numel(), _p(out), _stream_ptr(self._on)),
+                            "sfx_lce_range_argmin_dev")
+        return out
+
+    def _intervals(self, name, a, b, what):
+        self._arg(a, what[0])
+        self._arg(b, what[1], a.numel())
+        lo, hi, depth = (torch.empty(a.numel(), dtype=torch.int32, device=self._dev) for _ in range(3))
+        with _on(self._on):
+            self._eng.check(getattr(self._eng.lib, name)(self._h, _p(a), _p(b), a.numel(), _p(lo), _p(hi), _p(depth), _stream_ptr(self._on)),
+                            name)
+        return lo, hi, depth
+
+    def substr(self, pos, len):
+        """(lo, hi, depth): sa[lo[q] : hi[q]] are the occurrences of the len[q] bytes at pos[q], depth the string depth of
+        the lowest suffix-tree node at or below that locus; len 0 gives (0, n, 0), a substring that leaves the text (its
+        document) 0xFFFFFFFF three times.  No byte of the text is read."""
+        return self._intervals("sfx_lce_substr_dev", pos, len, ("pos", "len"))
+
+    def lca(self, a, b):
+        """(lo, hi, depth): the lowest common ancestor of the suffixes at positions a[q] and b[q] as a rank interval with
+        its string depth; a[q] == b[q] gives the suffix's own rank, a position >= n 0xFFFFFFFF three times."""
+        return self._intervals("sfx_lce_lca_dev", a, b, ("a", "b"))
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
             self._eng.lib.sfx_lce_destroy(h)
 
     __del__ = close
+
+
+def suffix_links_workspace(n, device, engine=None):
+    eng = engine or default_engine()
+    return torch.empty(int(eng.lib.sfx_suffix_links_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def suffix_links(index, sa, node_lb, node_rb, node_depth, out=None, workspace=None):
+    """slink (uint32 in int32 storage): for every internal node of `suffix_tree`'s table the dense id of the node that
+    spells its string without the first byte; 0xFFFFFFFF for the root.  `index` is the LceDeviceIndex made from (sa, lcp)
+    -- a plain table's; sa is that table.  Queues on the current stream without a synchronisation
+    (sfx_suffix_links_dev)."""
+    if not isinstance(index, LceDeviceIndex):
+        raise TypeError("index must be an LceDeviceIndex")
+    eng = index._eng
+    index._arg(sa, "sa", index.n)
+    nodes = node_lb.numel()
+    for t, name in ((node_lb, "node_lb"), (node_rb, "node_rb"), (node_depth, "node_depth")):
+        index._arg(t, name, nodes)
+    if out is None:
+        out = torch.empty(nodes, dtype=torch.int32, device=index._dev)
+    else:
+        index._arg(out, "out", nodes)
+    if workspace is None:
+        workspace = suffix_links_workspace(index.n, index._dev, eng)
+    with _on(index._on):
+        eng.check(eng.lib.sfx_suffix_links_dev(index._h, _p(sa), nodes, _p(node_lb), _p(node_rb), _p(node_depth), _p(out), _p(workspace),
+                                               workspace.numel(), _stream_ptr(index._on)), "sfx_suffix_links_dev")
+    return out
 
 
 DOCLIST_ORDERS = {"doc": 0, "tf": 1}

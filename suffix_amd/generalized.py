@@ -497,3 +497,45 @@ class GeneralizedSuffixTable:
                 raise IndexError(f"({d}, {o}) is no position of the collection")
             pos.append(int(self._starts[d]) + o)
         return int(self.lce_batch([pos[0]], [pos[1]], mismatches)[0])
+
+    # -- suffix-tree navigation --------------------------------------------------------------------
+    def _text_pos(self, p):
+        d, o = int(p[0]), int(p[1])
+        if not 0 <= d < len(self._docs) or not 0 <= o < len(self._docs[d]):
+            raise IndexError(f"({d}, {o}) is no position of the collection")
+        return int(self._starts[d]) + o
+
+    def substring_intervals_batch(self, pos, length):
+        """(lo, hi, depth), uint32 each, for TEXT positions (doc_starts[doc] + offset): table()[lo[q]:hi[q]] are the
+        occurrences of the length[q] bytes at pos[q] in all documents; a substring that leaves its document gives
+        0xFFFFFFFF three times (sfx_lce_substr)."""
+        return self._lce.substr(self._lce_index, pos, length)
+
+    def substring_interval(self, pos, length):
+        """(lo, hi) for the `length` bytes at the (document, offset) position `pos`."""
+        lo, hi, _ = self.substring_intervals_batch([self._text_pos(pos)], [int(length)])
+        if int(lo[0]) == 0xFFFFFFFF:
+            raise IndexError(f"{int(length)} bytes from {tuple(pos)} leave the document")
+        return int(lo[0]), int(hi[0])
+
+    def substring_count(self, pos, length):
+        lo, hi = self.substring_interval(pos, length)
+        return hi - lo
+
+    def lca_batch(self, a, b):
+        """(lo, hi, depth), uint32 each, for pairs of TEXT positions: the lowest common ancestor of the two truncated
+        suffixes as a rank interval of the generalized table, with its string depth (sfx_lce_lca)."""
+        return self._lce.lca(self._lce_index, a, b)
+
+    def lca(self, a, b):
+        """(lo, hi, depth) for one pair of (document, offset) positions."""
+        lo, hi, d = self.lca_batch([self._text_pos(a)], [self._text_pos(b)])
+        return int(lo[0]), int(hi[0]), int(d[0])
+
+    def lcp_range_argmin_batch(self, lo, hi):
+        """The smallest index that attains min lcp_lens()[lo[q]:hi[q]] (uint32); 0xFFFFFFFF for an empty range or
+        hi > len()."""
+        return self._lce.range_argmin(self._lce_index, lo, hi)
+
+    def lcp_range_argmin(self, lo, hi):
+        return int(self.lcp_range_argmin_batch([int(lo)], [int(hi)])[0])

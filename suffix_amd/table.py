@@ -174,6 +174,30 @@ class _LceHandle:
             self._eng.check(self._eng.lib.sfx_lce_range_min(h(), _ptr(lo), _ptr(hi), int(lo.size), _ptr(out)), "sfx_lce_range_min")
         return out
 
+    def range_argmin(self, h, lo, hi):
+        lo, hi = _u32_arg(lo, "lo"), _u32_arg(hi, "hi")
+        if lo.size != hi.size:
+            raise ValueError("lo and hi must hold one bound per range")
+        out = np.zeros(lo.size, dtype=np.uint32)
+        if lo.size:
+            self._eng.check(self._eng.lib.sfx_lce_range_argmin(h(), _ptr(lo), _ptr(hi), int(lo.size), _ptr(out)), "sfx_lce_range_argmin")
+        return out
+
+    def _intervals(self, h, name, a, b, what):
+        a, b = _u32_arg(a, what[0]), _u32_arg(b, what[1])
+        if a.size != b.size:
+            raise ValueError(f"{what[0]} and {what[1]} must hold one entry per query")
+        lo, hi, depth = (np.zeros(a.size, dtype=np.uint32) for _ in range(3))
+        if a.size:
+            self._eng.check(getattr(self._eng.lib, name)(h(), _ptr(a), _ptr(b), int(a.size), _ptr(lo), _ptr(hi), _ptr(depth)), name)
+        return lo, hi, depth
+
+    def substr(self, h, pos, length):
+        return self._intervals(h, "sfx_lce_substr", pos, length, ("pos", "length"))
+
+    def lca(self, h, a, b):
+        return self._intervals(h, "sfx_lce_lca", a, b, ("a", "b"))
+
 
 class Mems:
     """The maximal exact matches of a query text (SuffixTable.mems, GeneralizedSuffixTable.mems): uint32 arrays qpos /
@@ -607,6 +631,47 @@ class SuffixTable:
 
     def lcp_range_min(self, lo, hi):
         return int(self.lcp_range_min_batch([int(lo)], [int(hi)])[0])
+
+    def lcp_range_argmin_batch(self, lo, hi):
+        """The smallest index that attains min lcp_lens()[lo[q]:hi[q]] (uint32); 0xFFFFFFFF for an empty range or
+        hi > len()."""
+        return self._lce.range_argmin(self._lce_index, lo, hi)
+
+    def lcp_range_argmin(self, lo, hi):
+        return int(self.lcp_range_argmin_batch([int(lo)], [int(hi)])[0])
+
+    # -- suffix-tree navigation --------------------------------------------------------------------
+    def substring_intervals_batch(self, pos, length):
+        """(lo, hi, depth), uint32 each: table()[lo[q]:hi[q]] are the occurrences of text[pos[q] : pos[q] + length[q]],
+        found from the position alone -- no byte of the substring is read (sfx_lce_substr).  depth is the string depth
+        of the lowest suffix-tree node at or below the substring's locus.  length 0 gives (0, len(), 0); a substring
+        that leaves the text gives 0xFFFFFFFF three times."""
+        return self._lce.substr(self._lce_index, pos, length)
+
+    def substring_interval(self, pos, length):
+        """(lo, hi) of one substring; raises IndexError for one that is not inside the text."""
+        lo, hi, _ = self.substring_intervals_batch([int(pos)], [int(length)])
+        if int(lo[0]) == _NONE:
+            raise IndexError(f"text[{int(pos)}:{int(pos) + int(length)}] is not inside the text")
+        return int(lo[0]), int(hi[0])
+
+    def substring_count(self, pos, length):
+        """How often text[pos : pos + length] occurs."""
+        lo, hi = self.substring_interval(pos, length)
+        return hi - lo
+
+    def lca_batch(self, a, b):
+        """(lo, hi, depth), uint32 each: the lowest common ancestor of the suffixes at positions a[q] and b[q] as a rank
+        interval with its string depth -- their longest common prefix (sfx_lce_lca).  a[q] == b[q] gives the suffix's own
+        rank; a position >= len() gives 0xFFFFFFFF three times."""
+        return self._lce.lca(self._lce_index, a, b)
+
+    def lca(self, i, j):
+        """(lo, hi, depth) for one pair of positions; raises IndexError for a position >= len()."""
+        lo, hi, d = self.lca_batch([int(i)], [int(j)])
+        if int(lo[0]) == _NONE:
+            raise IndexError(f"({int(i)}, {int(j)}): no positions of the text")
+        return int(lo[0]), int(hi[0]), int(d[0])
 
     # -- Burrows-Wheeler transform ----------------------------------------------------------------
     def bwt(self, sample_step=256):

@@ -118,6 +118,10 @@ class Node:
     def has_terminals(self):
         return bool(self.suffixes())
 
+    def suffix_link(self):
+        """The node that spells this node's string without its first byte (SuffixTree.suffix_link)."""
+        return self._t.suffix_link(self)
+
 
 class SuffixTree:
     def __init__(self, table, engine=None):
@@ -152,6 +156,7 @@ class SuffixTree:
             for k in ("child_lb", "child_node", "child_byte"):
                 arrays[k] = arrays[k][:nc]
         self.arrays = arrays                                      # the node table as numpy arrays (include/suffix_hip.h)
+        self._by = None                                           # (lb, rb, depth) -> dense id, made by the first lookup
         # plain lists for the traversals (Python ints: no numpy scalar per step)
         self._sa = sa.tolist()
         self._depth = arrays["node_depth"].tolist() if n else []
@@ -192,6 +197,89 @@ class SuffixTree:
             return self._sa[node.rank] + up, self._n
         s = self._sa[self._lb[node.id]]
         return s + up, s + self._depth[node.id]
+
+    # -- navigation (include/suffix_hip.h: sfx_lce_substr, sfx_lce_lca, sfx_suffix_links_u32) -----------
+    def _node(self, k):
+        """The view of internal node k."""
+        up = self._parent[k] if self._n else _NONE
+        return Node(self, k, None, None if up == _NONE else up)
+
+    def _by_interval(self, lb, rb, depth):
+        """The internal node (lb, rb, depth): an interval alone does not name a node (the root of a unary text)."""
+        if depth == 0:
+            return self.root()
+        if self._by is None:
+            a = self.arrays
+            self._by = {key: k for k, key in enumerate(zip(a["node_lb"].tolist(), a["node_rb"].tolist(), self._depth))}
+        return self._node(self._by[(lb, rb, depth)])
+
+    def _leaf(self, rank):
+        """The leaf of a rank under its parent; leaf_parent is asked of the table call on first use."""
+        if "leaf_parent" not in self.arrays:
+            eng, n, a = self._eng, self._n, self.arrays
+            nm, nc = len(self._depth), len(self._clb)
+            lcp = np.ascontiguousarray(self._table.lcp_lens(), dtype=np.uint32)
+            sa = np.ascontiguousarray(self._table.table(), dtype=np.uint32)
+            tmp = {k: np.zeros_like(a[k]) for k in ("node_lb", "node_rb", "node_depth", "node_parent", "node_terminal", "child_off")}
+            clb, cnode = np.zeros(max(nc, 1), dtype=np.uint32), np.zeros(max(nc, 1), dtype=np.uint32)
+            leaf_parent = np.zeros(n, dtype=np.uint32)
+            m, c = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            eng.check(eng.lib.sfx_suffix_tree_u32(None, _ptr(sa), _ptr(lcp), n, nm, nc, _ptr(tmp["node_lb"]), _ptr(tmp["node_rb"]),
+                                                  _ptr(tmp["node_depth"]), _ptr(tmp["node_parent"]), _ptr(tmp["node_terminal"]),
+                                                  _ptr(tmp["child_off"]), _ptr(clb), _ptr(cnode), None, _ptr(leaf_parent), ctypes.byref(m),
+                                                  ctypes.byref(c)), "sfx_suffix_tree_u32")
+            a["leaf_parent"] = leaf_parent
+        return Node(self, None, int(rank), int(self.arrays["leaf_parent"][rank]))
+
+    def suffix_link(self, node):
+        """The node that spells `node`'s string without its first byte; None for the root.  Computed for all internal
+        nodes on first use (sfx_suffix_links_u32) and kept as arrays["suffix_link"].  A leaf raises ValueError."""
+        if node.id is None:
+            raise ValueError("suffix links are kept for internal nodes only")
+        if node.parent_id is None:
+            return None
+        if "suffix_link" not in self.arrays:
+            a, nm = self.arrays, len(self._depth)
+            sa = np.ascontiguousarray(self._table.table(), dtype=np.uint32)
+            lcp = np.ascontiguousarray(self._table.lcp_lens(), dtype=np.uint32)
+            out = np.zeros(nm, dtype=np.uint32)
+            self._eng.check(self._eng.lib.sfx_suffix_links_u32(_ptr(sa), _ptr(lcp), self._n, nm, _ptr(a["node_lb"]), _ptr(a["node_rb"]),
+                                                               _ptr(a["node_depth"]), _ptr(out)), "sfx_suffix_links_u32")
+            a["suffix_link"] = out
+        return self._node(int(self.arrays["suffix_link"][node.id]))
+
+    def _ranks(self, node):
+        if node.id is None:
+            return node.rank, node.rank
+        return (self._lb[node.id], int(self.arrays["node_rb"][node.id])) if self._n else (0, 0)
+
+    def lca(self, a, b):
+        """The lowest common ancestor of two nodes of this tree (either may be a leaf; a node is its own ancestor): the
+        LCA of the suffixes at the smallest and the largest rank below them (SuffixTable.lca)."""
+        for nd in (a, b):
+            if not isinstance(nd, Node) or nd._t is not self:
+                raise ValueError("lca takes two nodes of this tree")
+        if a == b:
+            return a
+        if a.parent_id is None or b.parent_id is None:
+            return self.root()
+        (alo, ahi), (blo, bhi) = self._ranks(a), self._ranks(b)
+        lo, hi = min(alo, blo), max(ahi, bhi)
+        l, h, d = self._table.lca(self._sa[lo], self._sa[hi])
+        return self._by_interval(l, h - 1, d)
+
+    def locus(self, pos, length):
+        """The node at or below the locus of text[pos : pos + length]: the highest node whose string starts with it.
+        Raises IndexError for a substring that is not inside the text."""
+        lo, hi, d = self._table.substring_intervals_batch([int(pos)], [int(length)])
+        lo, hi, d = int(lo[0]), int(hi[0]), int(d[0])
+        if lo == _NONE:
+            raise IndexError(f"text[{int(pos)}:{int(pos) + int(length)}] is not inside the text")
+        if int(length) == 0:
+            return self.root()
+        if hi - lo == 1:                                          # (never a terminal: a terminal's string has two occurrences)
+            return self._leaf(lo)
+        return self._by_interval(lo, hi - 1, d)
 
     def _fanout(self, node):
         if node.id is None or not self._n:
